@@ -4,6 +4,12 @@
 Contract: `python bench.py --gpus N --steps K --warmup W`; for N > 1 the driver launches it
 under torch.distributed.run (one rank per GPU, RCCL).  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line (headline, roofline of the same
+K steps, QP statistics).  `--full` adds everything else listed below (weak-scaling run beside a strong
+one, CPU baseline, sensitivity runs).  `--dump-outputs DIR` writes what the timed path computed in its
+last timed step as DIR/<name>.npy (float64; fixed, seeded sample of the per-stage iterate), so that two
+builds can be compared output for output: the inputs depend on the arguments only.
+
 Workload (BASELINE.json metric: "NMPC RTI steps/sec (batch=65536, N=50, nx=13, nu=4) at 1/2/4/8
 MI355X"): a synthetic fleet of 65 536 Crazyflie hover-regulation
 problems, horizon N = 50, run CLOSED LOOP through the RK4 plant (device-resident):
@@ -22,6 +28,7 @@ weak-scaling figure (65 536 per GPU) is measured right after it and reported bes
 Also on the same line (rank 0, N = 1):
   roofline     -- one RTI step's algorithmic bytes / the duration of its kernels, measured with HIP
                   events on the launch stream over the SAME K timed steps (DESIGN.md section 6);
+With --full only:
   cpu_baseline -- BASELINE.md section 3: the plain-C CPU restatement of the same algorithm
                   (oracle/cfnmpc_ref.c, "port": acados itself cannot be built here) on this host's
                   cores: B-lat (1 instance, 1000 steps, median / p99), B-thr (4096 instances x 20
@@ -394,9 +401,50 @@ def timed_run(fleet, steps, warmup, barrier, profile=True):
                                         as_pct=pct(as_steps), step_pct=pct(step_kernels))
 
 
+DUMP_BYTES = 64 << 20      # --dump-outputs: at most 64 MB in all
+DUMP_SAMPLE_SEED = 20200104
+
+
+def _dump_sample(n, k):
+    """Fixed, seeded, sorted sample of k of n instances (all of them when k >= n)."""
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+
+
+def write_outputs(dirname, arrays, rank, world):
+    """--dump-outputs: arrays {name: array} -> dirname/<name>.npy as float64 (one file per rank with a _rank<r> suffix when N > 1)."""
+    os.makedirs(dirname, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def fleet_outputs(fleet):
+    """What a caller of the timed path receives after the last timed step (call right after it, before any other step): the
+    input applied to the plant, the plant state it led to, the QP status / solves / residual per vehicle and the whole iterate
+    (predicted states and inputs over the horizon).  Per-vehicle arrays are kept whole up to 128 Ki vehicles; the iterate is a
+    fixed, seeded sample of 4096 vehicles (iterate_index); everything else follows the same sample beyond 128 Ki."""
+    n = fleet.n
+    st, it, rs = fleet.solver.stats()
+    xs, us = fleet.solver.get_iterate()
+    per = _dump_sample(n, 1 << 17)
+    idx = _dump_sample(n, 4096)
+    out = {"u0": fleet.u0.cpu().numpy()[per], "x_next": fleet.x.cpu().numpy()[per],
+           "qp_status": st[per], "qp_solves": it[per], "qp_residual": rs[per],
+           "iterate_index": idx, "iterate_x": xs[idx], "iterate_u": us[idx]}
+    if len(per) < n:
+        out["per_vehicle_index"] = per
+    assert sum(np.asarray(a).size * 8 for a in out.values()) <= DUMP_BYTES
+    return out
+
+
 def _relaunch_under_torchrun(n, backend, ndev):
-    """exec torch.distributed.run with the same argv: --nnodes=1, one rank per GPU, rendezvous on 127.0.0.1 (the container's
-    hostname may not resolve).  Refuses (non-zero exit) when RCCL would need more devices than are visible."""
+    """Run torch.distributed.run with the same argv as a child process and exit with its status: --nnodes=1, one rank per GPU,
+    rendezvous on 127.0.0.1 (the container's hostname may not resolve).  A child, not an exec: this process has already opened
+    the GPU, and replacing such a process's program is unsafe on ROCm.  Refuses (non-zero exit) when RCCL would need more devices
+    than are visible."""
     if backend == "nccl" and ndev < n:
         raise SystemExit(f"bench.py: --gpus {n} with the nccl (RCCL) backend needs {n} visible HIP devices, found {ndev} "
                          "(--dist-backend gloo lets ranks share devices for functional checks only)")
@@ -408,8 +456,9 @@ def _relaunch_under_torchrun(n, backend, ndev):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush(); sys.stderr.flush()
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC: what RCCL needs on this host driver
-    os.execv(sys.executable, cmd)
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC: what RCCL needs on this host driver
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
 def main():
@@ -423,9 +472,13 @@ def main():
                     help="instances: in total with --scaling strong, per GPU with --scaling weak")
     ap.add_argument("--scaling", choices=["strong", "weak"], default=None,
                     help="strong (default for N > 1): --batch instances split over the GPUs; weak: --batch per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the weak run beside a strong one, the CPU baseline and the sensitivity runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy (float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-profile", action="store_true", help="no HIP events around the kernels of the timed steps (roofline fields from kernel time are then void)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the sensitivity runs (and the weak run beside a strong one)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the sensitivity runs (and the weak run beside a strong one)")
     ap.add_argument("--active-horizon", type=int, default=1)
     ap.add_argument("--active-set", type=int, default=1)
     ap.add_argument("--cond-n2", type=int, default=None, help="cfnmpc_opts.cond_N2 (partial condensing; default: library default)")
@@ -454,6 +507,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if not args.full:   # a plain run: the headline's K timed steps and nothing else
+        args.no_extras = args.no_cpu_baseline = True
 
     import torch
     if not torch.cuda.is_available():
@@ -506,12 +561,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    def measure(batch_rank, steps, warmup, workload=args.workload, kick_scale=args.kick_scale, seed_off=0, profile=True, **kw):
-        """One closed-loop run of `batch_rank` vehicles on this rank; aggregated over ranks."""
+    def measure(batch_rank, steps, warmup, workload=args.workload, kick_scale=args.kick_scale, seed_off=0, profile=True, dump=None, **kw):
+        """One closed-loop run of `batch_rank` vehicles on this rank; aggregated over ranks.  dump: --dump-outputs directory
+        (written right after the timed steps)."""
         okw = dict(opt_kw); okw.update(kw)
         fleet = Fleet(batch_rank, dev, np.random.default_rng(seed + 1000 * seed_off), workload, kick_scale, **okw)
         torch.cuda.synchronize(dev)
         elapsed, ms_lin, ms_qp, st = timed_run(fleet, steps, warmup, barrier, profile and not args.no_profile)
+        if dump is not None:
+            write_outputs(dump, fleet_outputs(fleet), rank, world)
         if not profile and not args.no_profile:
             # (sensitivity runs: the K timed steps carry NO events -- seven event records per step cost ~30 us, 4 - 8 % of a step
             #  at 2048 - 8192 instances, 0.5 % at 65 536 --; the per-kernel split comes from 10 more steps with them)
@@ -547,6 +605,9 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
         st, it, _rs = loop.stats()
+        if args.dump_outputs is not None:   # (config C5: the input applied, the plant state, the QP statistics per vehicle)
+            write_outputs(args.dump_outputs, {"u0": loop.u0, "x_next": loop.x, "qp_status": st, "qp_solves": it, "qp_residual": _rs},
+                          rank, world)
         loop.close()
         slots = np.zeros((world, 4))          # per-rank: sum N, bucket sizes -- one slot per rank, summed over ranks = gathered
         slots[rank] = [float(hz.sum())] + [float((hz == n).sum()) for n in (30, 50, 100)]
@@ -596,7 +657,7 @@ def main():
     # N = 1: HIP events around the kernels of the K timed steps themselves (the roofline's kernel time is measured over the timed
     # region).  N > 1: the timed steps carry no events -- seven records per step cost ~30 us, 4 % of a step at the 8192 instances
     # per GPU of the 8-GPU split -- and the per-kernel split comes from 10 more steps with them (roofline.kernel_ms_source)
-    main_run = measure(B_rank, args.steps, args.warmup, profile=(world == 1))
+    main_run = measure(B_rank, args.steps, args.warmup, profile=(world == 1), dump=args.dump_outputs)
     weak = None
     if world > 1 and scaling == "strong" and not args.no_extras:
         weak = measure(args.batch, args.steps, args.warmup, seed_off=1, profile=False)
@@ -744,7 +805,7 @@ def main():
         if traffic is None:
             out["roofline"]["traffic_source"] = ("n/a: the PMC passes (tools/profile_round.sh) were taken at 65536 instances per launch, this run's launches cover "
                                                  f"{B_launch}")
-        if world > 1:
+        if world > 1 and args.full:
             out["cpu_baseline"] = {"omitted": "timed on rank 0 at N = 1 only (one bounded sample of host-core work per report, bench.py --gpus 1)"}
         if not args.no_cpu_baseline and world == 1:   # the CPU restatement is timed at N = 1 only
             try:

@@ -24,7 +24,7 @@ def _free_port():
 def _run(extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-           "--batch", "8192", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"] + extra
+           "--batch", "8192", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline"] + extra
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -89,7 +89,7 @@ def _plain(extra, expect_ok=True):
 
 def test_plain_python_bench_gpus_2_means_two_ranks():
     """BASELINE.json's metric is quoted "at 1/2/4/8 MI355X": `python bench.py --gpus N` started WITHOUT torch.distributed.run
-    re-launches itself under it (one rank per GPU) -- it never benches one GPU and prints n_gpus 1."""
+    re-launches itself under it as a child process (one rank per GPU) -- it never benches one GPU and prints n_gpus 1."""
     d = _plain(["--dist-backend", "gloo", "--batch", "8192"])
     assert d["n_gpus"] == 2 and d["report_collective"]["world_size"] == 2 and d["report_collective"]["backend"] == "gloo"
     assert d["config"]["total_batch"] == 8192 and d["config"]["batch_per_gpu"] == 4096

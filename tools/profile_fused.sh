@@ -13,5 +13,5 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write --
 python $R/tools/pmc_traffic.py $O/pmc_fetch $O/pmc_write $O/pmc_traffic.json $O/pmc_summary.csv
 cp $O/stats/*/*kernel_stats.csv $O/kernel_stats.csv
 head -9 $O/kernel_stats.csv
-cd $R && python bench.py $A 2>/dev/null | tail -1 > $O/bench_line.json
+cd $R && python bench.py --full $A 2>/dev/null | tail -1 > $O/bench_line.json
 python -c "import json; d=json.load(open('$O/bench_line.json')); print(d['value'], d['ms_per_step'], d['roofline']['kernels_ms'])"

@@ -13,5 +13,5 @@ python $R/tools/pmc_traffic.py $O/pmc_fetch $O/pmc_write $O/pmc_traffic.json $O/
 cp $O/pmc_traffic.json $R/profiles/pmc_traffic_latest.json   # so that the bench line below carries the fresh figure
 cp $O/stats/*/*kernel_stats.csv $O/kernel_stats.csv
 head -8 $O/kernel_stats.csv
-cd $R && python bench.py 2>/dev/null | tail -1 > $O/bench_line.json
+cd $R && python bench.py --full 2>/dev/null | tail -1 > $O/bench_line.json
 cat $O/bench_line.json
