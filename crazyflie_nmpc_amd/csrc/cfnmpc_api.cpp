@@ -15,6 +15,7 @@
 #include "../../include/cfnmpc.h"
 #include "cfnmpc_model.hpp"
 #include "cfnmpc_ws.hpp"
+#include "cfnmpc_sqp.h"
 #ifdef CFN_DEV
 #include "cfnmpc_dev.h"
 #endif
@@ -53,6 +54,11 @@ struct cfnmpc_solver {
     int reinit_failed;           // cfnmpc_opts.reinit_failed
     double *lbs_keep, *ubs_keep; // per-stage boxes (cfnmpc_set_box_stages), allocated at the first call
     double* box_blk[4];          // ... the four blocks behind them (home lb / ub, compact lb / ub); a failed attempt keeps what it got
+    // full SQP solve (cfnmpc_solve_sqp): per-instance results and counters of k_sqp_check (sqp.j / max_iter / tolerances of the
+    // running solve), the pinned word the host reads the count of open rows through, and the event it waits for
+    cfn::SqpArgs sqp;
+    unsigned* h_sqp_cnt;
+    hipEvent_t sqp_ev;
 };
 
 namespace {
@@ -280,6 +286,9 @@ int cfnmpc_create(cfnmpc_solver** out, int batch, const cfnmpc_opts* opts) {
     s->lbs_keep = s->ubs_keep = nullptr;
     for (double*& q : s->box_blk) q = nullptr;
     s->reinit_failed = o.reinit_failed ? 1 : 0;
+    std::memset(&s->sqp, 0, sizeof s->sqp);
+    s->h_sqp_cnt = nullptr;
+    s->sqp_ev = nullptr;
     int simds = 1024;   // SIMDs of the device the solver is created on
     {
         hipDeviceProp_t prop;
@@ -448,6 +457,12 @@ int cfnmpc_create(cfnmpc_solver** out, int batch, const cfnmpc_opts* opts) {
     if (P.fwd_split) { ALLOC(fs_dx, ((size_t)(batch + 63) / 64) * 13 * 64); ALLOC(fs_st, ((size_t)(batch + 63) / 64) * 4 * 64); }
     if (P.as_passes != 0) ALLOC(aslist, (size_t)3 * 7 * NW * 4);
     if (cond_N2) ALLOC(cb, NW * 4 * (size_t)cond_N2 * cfn::cb_size(cfn::cond_mmax(P)));
+    // full SQP solve (cfnmpc_solve_sqp): residuals, status, sqp_iter, done flags, the two counters of open rows
+    if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->sqp.res, (size_t)batch * 3);
+    if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->sqp.status, (size_t)batch);
+    if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->sqp.iter, (size_t)batch);
+    if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->sqp.done, (size_t)batch);
+    if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->sqp.cnt, 2);
     if (s->overlap) {
         if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->AR2, NW16 * N * cfn::SZ_A);
         if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->BR2, NW16 * N * cfn::SZ_B);
@@ -492,8 +507,10 @@ int cfnmpc_free(cfnmpc_solver* s) {
     if (s->cap) (void)hipStreamDestroy(s->cap);
     if (s->ev_start) (void)hipEventDestroy(s->ev_start);
     if (s->ev_aux) (void)hipEventDestroy(s->ev_aux);
+    if (s->sqp_ev) (void)hipEventDestroy(s->sqp_ev);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->h_io) (void)hipHostFree(s->h_io);
+    if (s->h_sqp_cnt) (void)hipHostFree(s->h_sqp_cnt);
     for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
     delete s;
     return CFNMPC_OK;
@@ -646,111 +663,212 @@ int cfnmpc_get_iterate(cfnmpc_solver* s, double* x, double* u, int on_device, vo
     return get_field(s, u, on_device, s->P.N, 4, 0, 0, s->P.N, s->P.uit, (hipStream_t)stream);
 }
 
+}  // extern "C"
+
+namespace {
+
+// One RTI step (linearise -> QP -> full step) on `st`, the body of cfnmpc_solve's loop and one iteration of the full SQP solve.
+// reinit: cfnmpc_opts.reinit_failed applies (cfnmpc_solve; not inside an SQP solve, whose failed rows stop instead).
+// chk (may be NULL): the SQP solve's convergence check, launched behind the step's kernels and BEFORE the host swaps the
+// iterate buffers (it reads both); the launches of the step itself are the same with or without it.
+int rti_step(cfnmpc_solver* s, hipStream_t st, bool reinit, const cfn::SqpArgs* chk) {
+    hipEvent_t* e = nullptr;
+    if (s->profiling && s->ev_used < EV_PER_STEP * MAX_PROFILED_STEPS) {   // bounded: later steps go untimed
+        while (s->ev.size() < s->ev_used + EV_PER_STEP) {
+            hipEvent_t ne;
+            HIP_TRY(hipEventCreate(&ne));
+            s->ev.push_back(ne);
+        }
+        e = &s->ev[s->ev_used];
+        s->ev_used += EV_PER_STEP;
+    }
+    if (reinit) { cfn::launch_reinit_failed(s->P, st); s->lin_valid = false; }
+    if (!s->overlap && s->use_graph && !e) {
+        // the step's launches replayed from a captured graph (one per parity of the iterate buffers)
+        const int p = s->parity;
+        bool ok = true;
+        if (!s->gvalid[p]) {
+            if (!s->cap) HIP_TRY(hipStreamCreateWithFlags(&s->cap, hipStreamNonBlocking));
+            if (!s->glaunched[p]) HIP_TRY(hipEventCreateWithFlags(&s->glaunched[p], hipEventDisableTiming));
+            if (s->gexec[p]) {   // a launch of the old exec may still be running (cfnmpc_solve is asynchronous)
+                HIP_TRY(hipEventSynchronize(s->glaunched[p]));
+                (void)hipGraphExecDestroy(s->gexec[p]);
+                s->gexec[p] = nullptr;
+            }
+            hipGraph_t g = nullptr;
+            ok = hipStreamBeginCapture(s->cap, hipStreamCaptureModeThreadLocal) == hipSuccess;
+            if (ok) {
+                if (s->P.fused != 1 || s->P.lbs) cfn::launch_linearise(s->P, s->chunks_all, s->cap);
+                if (s->P.cond_N2) cfn::launch_qp_cond(s->P, s->cap);
+                else cfn::launch_qp(s->P, s->cap);
+                ok = hipStreamEndCapture(s->cap, &g) == hipSuccess && g != nullptr;   // (always ends the capture)
+            }
+            if (ok) ok = hipGraphInstantiate(&s->gexec[p], g, nullptr, nullptr, 0) == hipSuccess;
+            if (g) (void)hipGraphDestroy(g);
+            if (!ok) {
+                // capture / instantiation failed: drop the capture stream (it may be left in an invalid capture
+                // state) and fall back to individual launches for good -- this step runs on the plain path below
+                (void)hipGetLastError();
+                (void)hipStreamDestroy(s->cap);
+                s->cap = nullptr;
+                s->gexec[p] = nullptr;
+                s->use_graph = 0;
+                std::fprintf(stderr, "cfnmpc: step_graph capture failed, launching the step's kernels individually\n");
+            } else {
+                s->gvalid[p] = true;
+            }
+        }
+        if (ok) {
+            HIP_TRY(hipGraphLaunch(s->gexec[p], st));
+            HIP_TRY(hipEventRecord(s->glaunched[p], st));
+            if (chk) cfn::launch_sqp_check(s->P, *chk, st);
+            std::swap(s->P.xit, s->P.xitn);
+            std::swap(s->P.uit, s->P.uitn);
+            s->parity ^= 1;
+            s->lin_valid = false;
+            return CFNMPC_OK;
+        }
+    }
+    if (!s->overlap) {
+        // linearise -> QP, everything on the caller's stream
+        if (e) HIP_TRY(hipEventRecord(e[0], st));
+        if (s->P.fused != 1 || s->P.lbs) cfn::launch_linearise(s->P, s->chunks_all, st);   // (fused start solve: k_linfactor linearises)
+        if (e) HIP_TRY(hipEventRecord(e[1], st));
+        if (s->P.cond_N2) {
+            cfn::launch_qp_cond(s->P, st);   // pcond -> condensed Riccati -> expand (-> interior point)
+            if (e) for (int j = 2; j < 6; j++) HIP_TRY(hipEventRecord(e[j], st));   // (no per-kernel split on this path)
+        } else {
+            cfn::launch_qp(s->P, st, e ? e + 2 : nullptr);
+        }
+        if (e) HIP_TRY(hipEventRecord(e[6], st));
+        if (chk) cfn::launch_sqp_check(s->P, *chk, st);
+        std::swap(s->P.xit, s->P.xitn);   // the step's kernels wrote every instance's new iterate there
+        std::swap(s->P.uit, s->P.uitn);
+        s->parity ^= 1;
+        s->lin_valid = false;   // the iterate moved
+        return CFNMPC_OK;
+    }
+#ifdef CFN_DEV   // overlapped preparation: development builds only (CFNMPC_OVERLAP=1); s->overlap is 0 in the product
+    // feedback phase on the linearisation prepared by the previous step ...
+    if (!s->lin_valid) cfn::launch_linearise(s->P, s->chunks_all, st);
+    if (e) HIP_TRY(hipEventRecord(e[0], st));
+    cfn::launch_qp_start(s->P, st);
+    HIP_TRY(hipEventRecord(s->ev_start, st));
+    cfn::launch_qp_ipm(s->P, st);
+    if (e) { for (int j = 1; j < 6; j++) HIP_TRY(hipEventRecord(e[j], st)); }   // (phases only on the overlapped path)
+    // ... and preparation of the next step into the alternate set: an early pass over ALL
+    // instances runs beside the interior-point kernel (the instances still inside it are
+    // linearised around a stale iterate there and redone by the list pass afterwards)
+    std::swap(s->P.xit, s->P.xitn);   // (host-side: kernel arguments are by value)
+    std::swap(s->P.uit, s->P.uitn);
+    cfn::Params Q = s->P;
+    Q.AR = s->AR2; Q.BR = s->BR2; Q.b = s->b2;
+    HIP_TRY(hipStreamWaitEvent(s->aux, s->ev_start, 0));
+    cfn::launch_linearise(Q, s->chunks_all, s->aux);
+    HIP_TRY(hipEventRecord(s->ev_aux, s->aux));
+    HIP_TRY(hipStreamWaitEvent(st, s->ev_aux, 0));
+    cfn::launch_linearise_list(Q, s->chunks_list, st);
+    if (e) HIP_TRY(hipEventRecord(e[6], st));
+    s->AR2 = s->P.AR; s->BR2 = s->P.BR; s->b2 = s->P.b;
+    s->P.AR = Q.AR; s->P.BR = Q.BR; s->P.b = Q.b;
+    s->lin_valid = true;
+#endif
+    return CFNMPC_OK;
+}
+
+}  // namespace
+
+// ---- full SQP solve, per solver (cfnmpc_sqp.h): cfnmpc_solve_sqp and cfnmpc_fleet_solve_sqp drive these ----------------
+namespace cfn {
+
+int sqp_check_args(const cfnmpc_solver* s, int max_iter, double tol_step, double tol_eq, double tol_ineq) {
+    if (!s || s->overlap || max_iter < 1) return CFNMPC_EINVAL;
+    for (double t : {tol_step, tol_eq, tol_ineq})
+        if (!(t > 0.0) || !std::isfinite(t)) return CFNMPC_EINVAL;
+    return CFNMPC_OK;
+}
+
+int sqp_begin(cfnmpc_solver* s, int max_iter, double tol_step, double tol_eq, double tol_ineq, void* stream) {
+    const int rc = sqp_check_args(s, max_iter, tol_step, tol_eq, tol_ineq);
+    if (rc != CFNMPC_OK) return rc;
+    DeviceGuard dg(s);
+    if (!s->h_sqp_cnt) HIP_TRY(hipHostMalloc((void**)&s->h_sqp_cnt, 2 * sizeof(unsigned), hipHostMallocDefault));
+    if (!s->sqp_ev) HIP_TRY(hipEventCreateWithFlags(&s->sqp_ev, hipEventDisableTiming));
+    s->sqp.max_iter = max_iter;
+    s->sqp.tol_step = tol_step; s->sqp.tol_eq = tol_eq; s->sqp.tol_ineq = tol_ineq;
+    s->sqp.j = 0;
+    // once per solve: both counters to zero (the check kernel of iteration j clears the counter of iteration j + 1 itself);
+    // the done flags need no reset, iteration 1 ignores them
+    HIP_TRY(hipMemsetAsync(s->sqp.cnt, 0, 2 * sizeof(unsigned), (hipStream_t)stream));
+    return CFNMPC_OK;
+}
+
+// enqueues SQP iteration s->sqp.j + 1 (step + check) and the read-back of its count of open rows; records s->sqp_ev behind it
+int sqp_iterate(cfnmpc_solver* s, void* stream) {
+    DeviceGuard dg(s);
+    hipStream_t st = (hipStream_t)stream;
+    s->sqp.j++;
+    const int rc = rti_step(s, st, false, &s->sqp);
+    if (rc != CFNMPC_OK) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(s->h_sqp_cnt, s->sqp.cnt + (s->sqp.j & 1), sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(s->sqp_ev, st));
+    return CFNMPC_OK;
+}
+
+// waits for the last enqueued iteration; *open = its rows not yet done
+int sqp_wait(cfnmpc_solver* s, unsigned* open) {
+    DeviceGuard dg(s);
+    HIP_TRY(hipEventSynchronize(s->sqp_ev));
+    *open = *(volatile unsigned*)s->h_sqp_cnt;
+    return CFNMPC_OK;
+}
+
+int sqp_iterations(const cfnmpc_solver* s) { return s->sqp.j; }
+
+int sqp_get_stats(cfnmpc_solver* s, int* status, int* sqp_iter, double* res, int on_device, void* stream) {
+    if (!s) return CFNMPC_EINVAL;
+    DeviceGuard dg(s);
+    hipStream_t st = (hipStream_t)stream;
+    const hipMemcpyKind kind = !is_host(on_device) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const size_t B = s->P.B;
+    if (status) HIP_TRY(hipMemcpyAsync(status, s->sqp.status, B * sizeof(int), kind, st));
+    if (sqp_iter) HIP_TRY(hipMemcpyAsync(sqp_iter, s->sqp.iter, B * sizeof(int), kind, st));
+    if (res) HIP_TRY(hipMemcpyAsync(res, s->sqp.res, B * 3 * sizeof(double), kind, st));
+    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
+
+}  // namespace cfn
+
+extern "C" {
+
 int cfnmpc_solve(cfnmpc_solver* s, int n_rti, void* stream) {
     if (!s || n_rti < 1) return CFNMPC_EINVAL;
     DeviceGuard dg(s);
     hipStream_t st = (hipStream_t)stream;
     for (int it = 0; it < n_rti; it++) {
-        hipEvent_t* e = nullptr;
-        if (s->profiling && s->ev_used < EV_PER_STEP * MAX_PROFILED_STEPS) {   // bounded: later steps go untimed
-            while (s->ev.size() < s->ev_used + EV_PER_STEP) {
-                hipEvent_t ne;
-                HIP_TRY(hipEventCreate(&ne));
-                s->ev.push_back(ne);
-            }
-            e = &s->ev[s->ev_used];
-            s->ev_used += EV_PER_STEP;
-        }
-        if (s->reinit_failed) { cfn::launch_reinit_failed(s->P, st); s->lin_valid = false; }
-        if (!s->overlap && s->use_graph && !e) {
-            // the step's launches replayed from a captured graph (one per parity of the iterate buffers)
-            const int p = s->parity;
-            if (!s->gvalid[p]) {
-                if (!s->cap) HIP_TRY(hipStreamCreateWithFlags(&s->cap, hipStreamNonBlocking));
-                if (!s->glaunched[p]) HIP_TRY(hipEventCreateWithFlags(&s->glaunched[p], hipEventDisableTiming));
-                if (s->gexec[p]) {   // a launch of the old exec may still be running (cfnmpc_solve is asynchronous)
-                    HIP_TRY(hipEventSynchronize(s->glaunched[p]));
-                    (void)hipGraphExecDestroy(s->gexec[p]);
-                    s->gexec[p] = nullptr;
-                }
-                hipGraph_t g = nullptr;
-                bool ok = hipStreamBeginCapture(s->cap, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                if (ok) {
-                    if (s->P.fused != 1 || s->P.lbs) cfn::launch_linearise(s->P, s->chunks_all, s->cap);
-                    if (s->P.cond_N2) cfn::launch_qp_cond(s->P, s->cap);
-                    else cfn::launch_qp(s->P, s->cap);
-                    ok = hipStreamEndCapture(s->cap, &g) == hipSuccess && g != nullptr;   // (always ends the capture)
-                }
-                if (ok) ok = hipGraphInstantiate(&s->gexec[p], g, nullptr, nullptr, 0) == hipSuccess;
-                if (g) (void)hipGraphDestroy(g);
-                if (!ok) {
-                    // capture / instantiation failed: drop the capture stream (it may be left in an invalid capture
-                    // state) and fall back to individual launches for good
-                    (void)hipGetLastError();
-                    (void)hipStreamDestroy(s->cap);
-                    s->cap = nullptr;
-                    s->gexec[p] = nullptr;
-                    s->use_graph = 0;
-                    std::fprintf(stderr, "cfnmpc: step_graph capture failed, launching the step's kernels individually\n");
-                    it--;          // redo this step on the plain path
-                    continue;
-                }
-                s->gvalid[p] = true;
-            }
-            HIP_TRY(hipGraphLaunch(s->gexec[p], st));
-            HIP_TRY(hipEventRecord(s->glaunched[p], st));
-            std::swap(s->P.xit, s->P.xitn);
-            std::swap(s->P.uit, s->P.uitn);
-            s->parity ^= 1;
-            s->lin_valid = false;
-            continue;
-        }
-        if (!s->overlap) {
-            // linearise -> QP, everything on the caller's stream
-            if (e) HIP_TRY(hipEventRecord(e[0], st));
-            if (s->P.fused != 1 || s->P.lbs) cfn::launch_linearise(s->P, s->chunks_all, st);   // (fused start solve: k_linfactor linearises)
-            if (e) HIP_TRY(hipEventRecord(e[1], st));
-            if (s->P.cond_N2) {
-                cfn::launch_qp_cond(s->P, st);   // pcond -> condensed Riccati -> expand (-> interior point)
-                if (e) for (int j = 2; j < 6; j++) HIP_TRY(hipEventRecord(e[j], st));   // (no per-kernel split on this path)
-            } else {
-                cfn::launch_qp(s->P, st, e ? e + 2 : nullptr);
-            }
-            if (e) HIP_TRY(hipEventRecord(e[6], st));
-            std::swap(s->P.xit, s->P.xitn);   // the step's kernels wrote every instance's new iterate there
-            std::swap(s->P.uit, s->P.uitn);
-            s->parity ^= 1;
-            s->lin_valid = false;   // the iterate moved
-            continue;
-        }
-#ifdef CFN_DEV   // overlapped preparation: development builds only (CFNMPC_OVERLAP=1); s->overlap is 0 in the product
-        // feedback phase on the linearisation prepared by the previous step ...
-        if (!s->lin_valid) cfn::launch_linearise(s->P, s->chunks_all, st);
-        if (e) HIP_TRY(hipEventRecord(e[0], st));
-        cfn::launch_qp_start(s->P, st);
-        HIP_TRY(hipEventRecord(s->ev_start, st));
-        cfn::launch_qp_ipm(s->P, st);
-        if (e) { for (int j = 1; j < 6; j++) HIP_TRY(hipEventRecord(e[j], st)); }   // (phases only on the overlapped path)
-        // ... and preparation of the next step into the alternate set: an early pass over ALL
-        // instances runs beside the interior-point kernel (the instances still inside it are
-        // linearised around a stale iterate there and redone by the list pass afterwards)
-        std::swap(s->P.xit, s->P.xitn);   // (host-side: kernel arguments are by value)
-        std::swap(s->P.uit, s->P.uitn);
-        cfn::Params Q = s->P;
-        Q.AR = s->AR2; Q.BR = s->BR2; Q.b = s->b2;
-        HIP_TRY(hipStreamWaitEvent(s->aux, s->ev_start, 0));
-        cfn::launch_linearise(Q, s->chunks_all, s->aux);
-        HIP_TRY(hipEventRecord(s->ev_aux, s->aux));
-        HIP_TRY(hipStreamWaitEvent(st, s->ev_aux, 0));
-        cfn::launch_linearise_list(Q, s->chunks_list, st);
-        if (e) HIP_TRY(hipEventRecord(e[6], st));
-        s->AR2 = s->P.AR; s->BR2 = s->P.BR; s->b2 = s->P.b;
-        s->P.AR = Q.AR; s->P.BR = Q.BR; s->P.b = Q.b;
-        s->lin_valid = true;
-#endif
+        const int rc = rti_step(s, st, s->reinit_failed != 0, nullptr);
+        if (rc != CFNMPC_OK) return rc;
     }
     HIP_TRY(hipGetLastError());
     return CFNMPC_OK;
+}
+
+int cfnmpc_solve_sqp(cfnmpc_solver* s, int max_iter, double tol_step, double tol_eq, double tol_ineq, int* n_iter, void* stream) {
+    int rc = cfn::sqp_begin(s, max_iter, tol_step, tol_eq, tol_ineq, stream);
+    if (rc != CFNMPC_OK) return rc;
+    for (int j = 1; j <= max_iter; j++) {
+        unsigned open = 0;
+        if ((rc = cfn::sqp_iterate(s, stream)) != CFNMPC_OK || (rc = cfn::sqp_wait(s, &open)) != CFNMPC_OK) return rc;
+        if (open == 0) break;
+    }
+    if (n_iter) *n_iter = cfn::sqp_iterations(s);
+    return CFNMPC_OK;
+}
+
+int cfnmpc_get_sqp_stats(cfnmpc_solver* s, int* status, int* sqp_iter, double* res, int on_device, void* stream) {
+    return cfn::sqp_get_stats(s, status, sqp_iter, res, on_device, stream);
 }
 
 int cfnmpc_step_host(cfnmpc_solver* s, const double* x0, const double* yref, const double* yref_e, double* u,

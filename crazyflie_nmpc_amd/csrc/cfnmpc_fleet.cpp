@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/cfnmpc.h"
+#include "cfnmpc_sqp.h"
 
 namespace {
 
@@ -365,6 +366,72 @@ int cfnmpc_fleet_get_stats(cfnmpc_fleet* f, int* status, int* qp_iter, double* r
         if (status) rows<int, false>(b.d_ints, status, b.d_idx, b.count, 1, 1, st);
         if (qp_iter) rows<int, false>(b.d_ints + b.count, qp_iter, b.d_idx, b.count, 1, 1, st);
         if (res) rows<double, false>(b.d_rows, res, b.d_idx, b.count, 1, 1, st);
+        return (int)CFNMPC_OK;
+    });
+}
+
+// Full SQP solve over the buckets: every bucket still running enqueues its iteration (step + check + read-back of its count of
+// open rows) on its own stream, then the host waits for all of them -- one synchronisation per iteration for the fleet.  A
+// bucket whose rows are all done launches nothing more (the one place a fleet's SQP solve saves work).
+int cfnmpc_fleet_solve_sqp(cfnmpc_fleet* f, int max_iter, double tol_step, double tol_eq, double tol_ineq, int* n_iter, void* stream) {
+    if (!f) return CFNMPC_EINVAL;
+    for (Bucket& b : f->bk) RC_TRY(cfn::sqp_check_args(b.s, max_iter, tol_step, tol_eq, tol_ineq));   // nothing enqueued yet
+    FleetDevice fd(f);
+    hipStream_t user = (hipStream_t)stream;
+    HIP_TRY(hipEventRecord(f->fork, user));
+    std::vector<char> running(f->bk.size(), 1);
+    for (int bi : f->order) {
+        Bucket& b = f->bk[bi];
+        HIP_TRY(hipStreamWaitEvent(b.st, f->fork, 0));
+        RC_TRY(cfn::sqp_begin(b.s, max_iter, tol_step, tol_eq, tol_ineq, b.st));
+    }
+    int ran = 0;
+    for (int j = 1; j <= max_iter; j++) {
+        for (int bi : f->order)
+            if (running[bi]) RC_TRY(cfn::sqp_iterate(f->bk[bi].s, f->bk[bi].st));   // (heaviest bucket first)
+        ran = j;
+        bool any = false;
+        for (int bi : f->order) {
+            if (!running[bi]) continue;
+            unsigned open = 0;
+            RC_TRY(cfn::sqp_wait(f->bk[bi].s, &open));
+            running[bi] = open > 0;
+            any = any || open > 0;
+        }
+        if (!any) break;
+    }
+    // (every bucket's work has completed; the join keeps the caller's stream ordered behind it all the same)
+    for (Bucket& b : f->bk) {
+        HIP_TRY(hipEventRecord(b.done, b.st));
+        HIP_TRY(hipStreamWaitEvent(user, b.done, 0));
+    }
+    if (n_iter) *n_iter = ran;
+    return CFNMPC_OK;
+}
+
+int cfnmpc_fleet_get_sqp_stats(cfnmpc_fleet* f, int* status, int* sqp_iter, double* res, int on_device, void* stream) {
+    if (!f) return CFNMPC_EINVAL;
+    FleetDevice fd(f);
+    if (!on_device) {
+        for (Bucket& b : f->bk) {
+            f->h_ints.resize((size_t)2 * b.count);
+            f->h_rows.resize((size_t)3 * b.count);
+            int* hs = f->h_ints.data(), *hi = hs + b.count;
+            RC_TRY(cfn::sqp_get_stats(b.s, hs, hi, f->h_rows.data(), 0, stream));
+            for (int r = 0; r < b.count; r++) {
+                if (status) status[b.idx[r]] = hs[r];
+                if (sqp_iter) sqp_iter[b.idx[r]] = hi[r];
+                if (res) std::copy_n(f->h_rows.data() + (size_t)r * 3, 3, res + (long)b.idx[r] * 3);
+            }
+        }
+        return CFNMPC_OK;
+    }
+    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) {
+        RC_TRY(staging(b));
+        RC_TRY(cfn::sqp_get_stats(b.s, b.d_ints, b.d_ints + b.count, b.d_rows, 1, st));
+        if (status) rows<int, false>(b.d_ints, status, b.d_idx, b.count, 1, 1, st);
+        if (sqp_iter) rows<int, false>(b.d_ints + b.count, sqp_iter, b.d_idx, b.count, 1, 1, st);
+        if (res) rows<double, false>(b.d_rows, res, b.d_idx, b.count, 3, 3, st);
         return (int)CFNMPC_OK;
     });
 }

@@ -3069,6 +3069,122 @@ __global__ void k_reinit_failed(Params P) {
         for (int e = 0; e < 4; e++) P.uit[blk_index(i, k, e, P.N, 4, P.v4b)] = P.yref[blk_index(i, k, 13 + e, P.N, 17)];
 }
 
+// =============================================================================================
+// full SQP solve (cfnmpc_solve_sqp): convergence check behind SQP iteration j
+// =============================================================================================
+// Runs after the RTI step of iteration j, before the host swaps the iterate buffers: w_{j-1} is in P.xit / P.uit, w_j in
+// P.xitn / P.uitn.  Lane per instance, 64 per wavefront, the 13-vectors through an LDS tile as in k_forward (every global
+// access of the wave a contiguous run).  Per instance:
+//   res_step = max |w_j - w_{j-1}| over all x_k, u_k -- the Gauss-Newton step, zero iff w_j is a KKT point (Q, R > 0); the
+//              stationarity measure of this solve, NOT acados' res_stat;
+//   res_eq   = max(|x_0 - x0|, max_k |x_{k+1} - Phi(x_k, u_k)|) at w_j, Phi = one RK4 step over dt (f_expl, as k_linearise);
+//   res_ineq = largest violation of the input box at w_j (the scalar box, or the per-stage boxes while they are set).
+// Classification: QP status 4 in step j -> done, status 4 (the step kept the iterate); all three within their tolerances ->
+// done, status 0; otherwise status 2 (final once j = max_iter).  A row done at an EARLIER iteration is frozen: its old
+// iterate is copied over the new one, so that it leaves the solve with w_{sqp_iter}.  Rows not yet done are counted into
+// A.cnt[j & 1] (a ballot per wavefront, one atomic); the launch clears A.cnt[(j + 1) & 1], the next iteration's counter (the
+// host has read it before this launch: stream order), so no memset sits between the iterations.
+__device__ __forceinline__ double max_nan(double acc, double v) { return (v > acc || v != v) ? v : acc; }   // NaN sticks
+__global__ __launch_bounds__(64) void k_sqp_check(Params P, SqpArgs A) {
+    __shared__ double xs_o[64 * 13], xs_n[64 * 13];
+    __shared__ int sfrz[64];
+    const int N = P.N;
+    const int tid = threadIdx.x;
+    const int raw = blockIdx.x * 64 + tid;
+    const bool valid = raw < P.B;
+    const int inst = valid ? raw : P.NW * 4 + (tid & 3);   // idle lanes: spare block
+    const size_t w = (size_t)(inst >> 2);
+    const int q = inst & 3;
+    const int w0 = blockIdx.x * 16;
+    const double h = P.dt;
+    const size_t i4b = P.v4b ? ((size_t)w * N * 4 + q) * 4 : (size_t)inst * N * 4;   // this lane's 4-vectors (Params.v4b)
+    const size_t i4s = P.v4b ? 16 : 4;
+    auto el13 = [&](const double* f, int e, int stages, int k) -> gdouble* {   // (k_forward's accessor)
+        const int bk = (int)(__umul24((unsigned)e, div_magic(52)) >> 16), off = e - bk * 52;
+        const unsigned bo = (__umul24((unsigned)imin(bk, P.NW - w0), (unsigned)(stages * SZ_V13)) + (unsigned)off) * 8u;
+        const char* base = (const char*)(gm(f) + ((size_t)w0 * stages + k) * SZ_V13);
+        return (gdouble*)(base + bo);
+    };
+    const bool frozen = valid && A.j > 1 && gm(A.done)[raw] != 0;
+    sfrz[tid] = frozen ? 1 : 0;
+    __syncthreads();
+    const bool any_frozen = __any(frozen);
+    bool mine[13];   // element tid + 64 j of the group's tile belongs to a frozen instance
+    SFOR(j, 0, 13, { mine[j] = sfrz[(tid + 64 * j) / 13] != 0; });
+    struct Ld { double o[13], n[13], uo[4], un[4]; };   // stage k: old / new state (tile elements), old / new inputs
+    auto issue = [&](int k, Ld& L) {
+        SFOR(j, 0, 13, { L.o[j] = *el13(P.xit, tid + 64 * j, N + 1, k); L.n[j] = *el13(P.xitn, tid + 64 * j, N + 1, k); });
+        const size_t ku = (size_t)imin(k, N - 1);
+        SFOR(a, 0, 4, { L.uo[a] = gm(P.uit)[i4b + ku * i4s + a]; L.un[a] = gm(P.uitn)[i4b + ku * i4s + a]; });
+    };
+    double phi[13];   // what x_k must equal: x0 for k = 0, Phi(x_{k-1}, u_{k-1}) behind it (internal order)
+    {
+        double t[13];
+        SFOR(j, 0, 13, { t[j] = *el13(P.x0, tid + 64 * j, 1, 0); });
+        SFOR(j, 0, 13, { xs_n[tid + 64 * j] = t[j]; });
+        __syncthreads();
+        SFOR(i, 0, 13, { phi[i] = xs_n[tid * 13 + i]; });
+    }
+    double r_step = 0.0, r_eq = 0.0, r_ineq = 0.0;
+    Ld cur, nxt;
+    issue(0, cur);
+    for (int k = 0; k <= N; k++) {
+        __syncthreads();
+        SFOR(j, 0, 13, { xs_o[tid + 64 * j] = cur.o[j]; xs_n[tid + 64 * j] = cur.n[j]; });
+        __syncthreads();
+        double xo[13], xn[13];
+        SFOR(i, 0, 13, { xo[i] = xs_o[tid * 13 + i]; xn[i] = xs_n[tid * 13 + i]; });
+        // frozen rows: w_{j-1} over w_j (stage k has been read in full above)
+        if (any_frozen) {
+            SFOR(j, 0, 13, { if (mine[j]) *el13(P.xitn, tid + 64 * j, N + 1, k) = cur.o[j]; });
+            if (frozen && k < N) SFOR(a, 0, 4, { gm(P.uitn)[i4b + (size_t)k * i4s + a] = cur.uo[a]; });
+        }
+        double un[4];
+        SFOR(a, 0, 4, { un[a] = cur.un[a]; });
+        if (k < N) issue(k + 1, nxt);   // next stage's loads in flight during this stage's integration
+        SFOR(i, 0, 13, { r_step = max_nan(r_step, fabs(xn[i] - xo[i])); r_eq = max_nan(r_eq, fabs(xn[i] - phi[i])); });
+        if (k == N) break;
+        SFOR(a, 0, 4, {
+            r_step = max_nan(r_step, fabs(un[a] - cur.uo[a]));
+            double lo = P.u_min, hi = P.u_max;
+            if (P.lbs) { lo = gm(P.lbs)[i4b + (size_t)k * i4s + a]; hi = gm(P.ubs)[i4b + (size_t)k * i4s + a]; }
+            r_ineq = max_nan(r_ineq, fmax(lo - un[a], un[a] - hi));
+        });
+        // Phi(x_k, u_k): one RK4 step over dt (model vectors in the EXTERNAL order)
+        double x[13], xt[13], kk[13], ks[13];
+        SFOR(e, 0, 13, { x[e] = xn[int_of(e)]; });
+        f_expl(x, un, kk);
+        SFOR(e, 0, 13, { ks[e] = kk[e]; xt[e] = x[e] + 0.5 * h * kk[e]; });
+        f_expl(xt, un, kk);
+        SFOR(e, 0, 13, { ks[e] += 2.0 * kk[e]; xt[e] = x[e] + 0.5 * h * kk[e]; });
+        f_expl(xt, un, kk);
+        SFOR(e, 0, 13, { ks[e] += 2.0 * kk[e]; xt[e] = x[e] + h * kk[e]; });
+        f_expl(xt, un, kk);
+        SFOR(i, 0, 13, { constexpr int e = ext_of(i); phi[i] = x[e] + (h / 6.0) * (ks[e] + kk[e]); });
+        cur = nxt;
+    }
+    bool open = false;
+    if (valid && !frozen) {
+        int st;
+        bool dn;
+        if (gm(P.status)[raw] == 4) { st = 4; dn = true; }
+        else if (r_step <= A.tol_step && r_eq <= A.tol_eq && r_ineq <= A.tol_ineq) { st = 0; dn = true; }
+        else { st = 2; dn = A.j >= A.max_iter; }
+        gm(A.res)[(size_t)raw * 3 + 0] = r_step;
+        gm(A.res)[(size_t)raw * 3 + 1] = r_eq;
+        gm(A.res)[(size_t)raw * 3 + 2] = r_ineq;
+        gm(A.status)[raw] = st;
+        gm(A.iter)[raw] = A.j;
+        gm(A.done)[raw] = dn ? 1 : 0;
+        open = !dn;
+    }
+    const unsigned long long m = __ballot(open);
+    if (tid == 0) {
+        if (m) atomicAdd(A.cnt + (A.j & 1), (unsigned)__popcll(m));
+        if (blockIdx.x == 0) A.cnt[(A.j + 1) & 1] = 0u;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
@@ -3265,6 +3381,9 @@ void launch_postproc(const Params& P, double* cmd_vel, int* motvel, hipStream_t 
 }
 void launch_reinit_failed(const Params& P, hipStream_t st) {
     hipLaunchKernelGGL(k_reinit_failed, dim3((P.B + 255) / 256), dim3(256), 0, st, P);
+}
+void launch_sqp_check(const Params& P, const SqpArgs& A, hipStream_t st) {
+    hipLaunchKernelGGL(k_sqp_check, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
 }
 void launch_init_iterate(const Params& P, int mode, hipStream_t st) {
     hipLaunchKernelGGL(k_init_iterate, dim3((P.B + 255) / 256), dim3(256), 0, st, P, mode);

@@ -238,6 +238,17 @@ void launch_windows(const Params& P, const double* traj, int n_rows, int* mode, 
                     double uss, hipStream_t st);
 void launch_init_iterate(const Params& P, int mode, hipStream_t st);
 void launch_reinit_failed(const Params& P, hipStream_t st);   // cfnmpc_opts.reinit_failed
+// full SQP solve (cfnmpc_solve_sqp): per-instance state of the convergence check k_sqp_check, owned by
+// the solver (not part of Params: the RTI step's kernels never see it)
+struct SqpArgs {
+    double* res;                 // [B][3]: res_step, res_eq, res_ineq of the instance's last checked iterate
+    int *status, *iter, *done;   // [B]: SQP status (0 converged, 2 max. iterations, 4 QP failure), sqp_iter, 1 = done (frozen)
+    unsigned* cnt;               // [2]: rows not yet done after iteration j, counted into cnt[j & 1] (the launch clears the other)
+    int j, max_iter;             // this iteration (1-based), the cap
+    double tol_step, tol_eq, tol_ineq;
+};
+// after the step of iteration A.j, BEFORE the host swaps the iterate buffers (reads P.xit / P.uit and P.xitn / P.uitn)
+void launch_sqp_check(const Params& P, const SqpArgs& A, hipStream_t st);
 // output stage of the reference node for the fleet (cmd_vel [B][4] doubles, motvel [B][4] int32 or NULL)
 void launch_postproc(const Params& P, double* cmd_vel, int* motvel, hipStream_t st);
 

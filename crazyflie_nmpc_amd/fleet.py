@@ -129,6 +129,22 @@ class MixedHorizonFleet:
     def solve(self, n_rti=1, stream=None):
         _check(self._L.cfnmpc_fleet_solve(self._h, int(n_rti), _launch_stream(stream, self._device)), "cfnmpc_fleet_solve")
 
+    def solve_sqp(self, max_iter=100, tol_step=1e-6, tol_eq=1e-6, tol_ineq=1e-6, stream=None):
+        """Full SQP solve of every vehicle at its own horizon (cfnmpc_fleet_solve_sqp); returns the iterations run by the
+        longest-running bucket.  Per vehicle: sqp_stats()."""
+        n = C.c_int(0)
+        _check(self._L.cfnmpc_fleet_solve_sqp(self._h, int(max_iter), float(tol_step), float(tol_eq), float(tol_ineq), C.byref(n),
+                                              _launch_stream(stream, self._device)), "cfnmpc_fleet_solve_sqp")
+        return n.value
+
+    def sqp_stats(self):
+        """-> (status [B], sqp_iter [B], res [B, 3]) of the last solve_sqp, in the fleet's vehicle order"""
+        st = np.empty(self.B, dtype=np.int32); it = np.empty(self.B, dtype=np.int32); rs = np.empty((self.B, 3))
+        _check(self._L.cfnmpc_fleet_get_sqp_stats(self._h, st.ctypes.data_as(C.c_void_p), it.ctypes.data_as(C.c_void_p),
+                                                  rs.ctypes.data_as(C.c_void_p), 0, _launch_stream(None, self._device)),
+               "cfnmpc_fleet_get_sqp_stats")
+        return st, it, rs
+
     def get_u(self, stage, out=None):
         if out is None:
             out = np.empty((self.B, NU))

@@ -183,6 +183,24 @@ class BatchSolver:
         """acados_solve() for the batch; `stream` is a raw hipStream_t (int) or None = default."""
         _check(self._L.cfnmpc_solve(self._h, int(n_rti), _launch_stream(stream, self._device)), "cfnmpc_solve")
 
+    def solve_sqp(self, max_iter=100, tol_step=1e-6, tol_eq=1e-6, tol_ineq=1e-6, stream=None):
+        """Full SQP solve (acados' nlp_solver_type 'SQP'; include/cfnmpc.h: cfnmpc_solve_sqp): RTI steps with x0, yref,
+        weights and boxes fixed until every instance has converged (res_step <= tol_step, res_eq <= tol_eq,
+        res_ineq <= tol_ineq), failed (QP status 4) or max_iter steps have run.  Defaults: acados' SQP defaults.
+        Synchronises the stream.  Returns the number of iterations run; per instance: sqp_stats()."""
+        n = C.c_int(0)
+        _check(self._L.cfnmpc_solve_sqp(self._h, int(max_iter), float(tol_step), float(tol_eq), float(tol_ineq), C.byref(n),
+                                        _launch_stream(stream, self._device)), "cfnmpc_solve_sqp")
+        return n.value
+
+    def sqp_stats(self):
+        """-> (status [B] (0 converged, 2 max. iterations, 4 QP failure), sqp_iter [B], res [B, 3] = res_step, res_eq,
+        res_ineq) of the last solve_sqp"""
+        st = np.empty(self.B, dtype=np.int32); it = np.empty(self.B, dtype=np.int32); rs = np.empty((self.B, 3))
+        _check(self._L.cfnmpc_get_sqp_stats(self._h, st.ctypes.data_as(C.c_void_p), it.ctypes.data_as(C.c_void_p),
+                                            rs.ctypes.data_as(C.c_void_p), 0, _launch_stream(None, self._device)), "cfnmpc_get_sqp_stats")
+        return st, it, rs
+
     def step_host(self, x0, yref, yref_e, stream=None):
         """cfnmpc_step_host: host arrays in (x0 [B,13], yref [B,N,17], yref_e [B,13]), one RTI step,
         host arrays out -> (u [B,N,4], x [B,N+1,13], status, qp_iter, res); one synchronisation."""

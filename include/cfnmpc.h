@@ -264,6 +264,31 @@ int cfnmpc_get_iterate(cfnmpc_solver *s, double *x, double *u, int on_device, vo
  * `stream`.  The reference calls it with one step. */
 int cfnmpc_solve(cfnmpc_solver *s, int n_rti, void *stream);
 
+/* Full SQP solve (acados' nlp_solver_type = 'SQP', the one alternative the reference's generator names next to SQP_RTI,
+ * generate_c_code.py:146-147): iterates every instance to a converged NLP solution.  x0, yref, weights and boxes stay fixed
+ * during the solve.  One SQP iteration is exactly one RTI step as cfnmpc_solve runs it (linearise at the iterate, solve the
+ * QP, take the full step).  After iteration j every instance not yet done gets
+ *   res_step = max-norm of w_j - w_{j-1} over all x_k and u_k -- the STATIONARITY measure of this solve: for the Gauss-Newton
+ *              QP with Q, R > 0 the step is zero iff w is a KKT point (it is not acados' res_stat);
+ *   res_eq   = max(|x_0 - x0|, max_k |x_{k+1} - Phi(x_k, u_k)|) at w_j, Phi = the engine's RK4 step over dt;
+ *   res_ineq = the largest violation of the input box at w_j (the scalar box, or the per-stage boxes while they are set);
+ * and is classified: status 4 if the QP of step j failed (the step keeps its iterate; done, sqp_iter = j); else status 0 if
+ * res_step <= tol_step, res_eq <= tol_eq and res_ineq <= tol_ineq (done, sqp_iter = j, keeps w_j); else status 2 once
+ * j = max_iter.  A QP status 2 (QP iteration cap) does not stop an instance.  A done instance is FROZEN: later iterations
+ * still run it through the step's kernels but restore its iterate, so it leaves the solve with w_{sqp_iter}.  The loop ends
+ * when every instance is done or after max_iter iterations; *n_iter (may be NULL) = iterations run.  One read of the count
+ * of open instances (pinned memory, one event) per iteration; the call synchronises `stream`.  cfnmpc_opts.reinit_failed
+ * does not apply inside the solve (failed instances stop instead).  CFNMPC_EINVAL: max_iter < 1, a tolerance <= 0 or not
+ * finite, the overlapped preparation of development builds.  cfnmpc_get_stats keeps its meaning: the QP statistics of the
+ * LAST executed step (an instance frozen before it included). */
+int cfnmpc_solve_sqp(cfnmpc_solver *s, int max_iter, double tol_step, double tol_eq, double tol_ineq,
+                     int *n_iter /* iterations run, may be NULL */, void *stream);
+/* Per instance, of the last cfnmpc_solve_sqp: status (0 converged, 2 max. iterations, 4 QP failure), sqp_iter (the
+ * iteration whose iterate the instance kept) and res [B][3] = res_step, res_eq, res_ineq at that iterate.  Any pointer may
+ * be NULL; on_device as everywhere. */
+int cfnmpc_get_sqp_stats(cfnmpc_solver *s, int *status, int *sqp_iter, double *res /*[B][3]: step, eq, ineq*/,
+                         int on_device, void *stream);
+
 /* One complete control step from HOST buffers with a single synchronisation -- what the node
  * does per sample (acados_mpc.cpp:581-625: set lbx/ubx, N+1 yref rows, acados_solve(), read u/x):
  * x0 [B][13], yref [B][N][17], yref_e [B][13] in; one RTI step; the whole iterate out
@@ -284,7 +309,8 @@ int cfnmpc_get_x(cfnmpc_solver *s, int stage, double *x /*[B][13]*/, int on_devi
  * the interior-point ITERATIONS of a row that fell back (after 12 unsettled solves, or skipped by as_skip_viol; such a row runs
  * the interior point over all N stages) -- the two ranges overlap (twelve iterations are not twelve solves).  res tells them apart: exactly 0.0 for a row settled by active-set
  * solves (a stationary classification IS the KKT system), the interior point's final residual (> 0, <= tol at status 0)
- * for a row it solved. */
+ * for a row it solved.  These are the statistics of the last executed RTI step, also after cfnmpc_solve_sqp (its per-instance
+ * NLP results: cfnmpc_get_sqp_stats). */
 int cfnmpc_get_stats(cfnmpc_solver *s, int *status /*[B]*/, int *qp_iter /*[B]*/, double *res /*[B]*/, int on_device, void *stream);
 
 /* Output stage of the reference node for the whole fleet, on the device (NMPC::iteration,
@@ -388,6 +414,13 @@ int cfnmpc_fleet_get_u(cfnmpc_fleet *f, int stage, double *u /*[B][4]*/, int on_
 int cfnmpc_fleet_get_x(cfnmpc_fleet *f, int stage, double *x /*[B][13]*/, int on_device, void *stream);
 int cfnmpc_fleet_get_cmd(cfnmpc_fleet *f, double *cmd_vel /*[B][4]*/, int *motvel /*[B][4]*/, int on_device, void *stream);
 int cfnmpc_fleet_get_stats(cfnmpc_fleet *f, int *status, int *qp_iter, double *res, int on_device, void *stream);
+/* cfnmpc_solve_sqp for a fleet: every bucket still running takes its iteration on its own stream, then the host waits once;
+ * a bucket whose instances are all done launches nothing more.  *n_iter = iterations of the longest-running bucket.
+ * Synchronises `stream`. */
+int cfnmpc_fleet_solve_sqp(cfnmpc_fleet *f, int max_iter, double tol_step, double tol_eq, double tol_ineq, int *n_iter,
+                           void *stream);
+/* cfnmpc_get_sqp_stats in the fleet's vehicle order: status [B], sqp_iter [B], res [B][3] */
+int cfnmpc_fleet_get_sqp_stats(cfnmpc_fleet *f, int *status, int *sqp_iter, double *res, int on_device, void *stream);
 
 /* ---- one fleet across several GPUs of a node, from ONE process --------------------------------
  * The reference owns one vehicle per process (acados_mpc.cpp:76-82); instances are independent, so a
