@@ -24,6 +24,8 @@ SYMBOLS = [
     "cfnmpc_multi_set_x0", "cfnmpc_multi_set_yref", "cfnmpc_multi_set_weights", "cfnmpc_multi_init_iterate", "cfnmpc_multi_solve",
     "cfnmpc_multi_sync", "cfnmpc_multi_set_box", "cfnmpc_multi_set_box_stages", "cfnmpc_multi_get_u", "cfnmpc_multi_get_x", "cfnmpc_multi_get_cmd", "cfnmpc_multi_get_stats",
     "cfnmpc_multi_create_horizons", "cfnmpc_multi_shard_fleet", "cfnmpc_shard_by_horizon",
+    "cfnmpc_set_erk_steps", "cfnmpc_erk_steps", "cfnmpc_set_cost_scaling", "cfnmpc_fleet_set_erk_steps",
+    "cfnmpc_fleet_set_cost_scaling", "cfnmpc_multi_set_erk_steps", "cfnmpc_multi_set_cost_scaling",
 ]
 ABI_VERSION = 9   # CFNMPC_ABI_VERSION of the include/cfnmpc.h this binding was written against
 
@@ -103,6 +105,13 @@ def lib():
     L.cfnmpc_get_profile_kernels.argtypes = [vp, vp, vp]
     L.cfnmpc_get_profile_steps.argtypes = [vp, vp, i32, vp]
     L.cfnmpc_debug_linearise.argtypes = [vp, vp]
+    L.cfnmpc_set_erk_steps.argtypes = [vp, i32]
+    L.cfnmpc_erk_steps.argtypes = [vp]
+    L.cfnmpc_set_cost_scaling.argtypes = [vp, dbl, dbl]
+    L.cfnmpc_fleet_set_erk_steps.argtypes = [vp, i32]
+    L.cfnmpc_fleet_set_cost_scaling.argtypes = [vp, dbl, dbl]
+    L.cfnmpc_multi_set_erk_steps.argtypes = [vp, i32]
+    L.cfnmpc_multi_set_cost_scaling.argtypes = [vp, dbl, dbl]
     for name, at in (("cfnmpc_debug_chunked_pair", [vp, i32, i32, vp, vp]), ("cfnmpc_debug_checksum", [vp, vp]),
                      ("cfnmpc_debug_solve_part", [vp, i32, i32, vp])):   # development builds only (make DEV=1, csrc/cfnmpc_dev.h)
         if hasattr(L, name):

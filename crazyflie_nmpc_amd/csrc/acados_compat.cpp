@@ -29,7 +29,9 @@ struct Shim {
     double W[NY], WN[NX];
     double x[(N + 1) * NX], u[N * NU];  // host copy of the iterate after the last solve
     double lbu[N][NU], ubu[N][NU];      // per-stage input box as set through "lbu" / "ubu"
-    bool weights_dirty = false, box_dirty = false;
+    double scaling[N + 1];              // per-stage cost scaling as set through "scaling" (default 1)
+    int erk_steps = 1;                  // "sim_method_num_steps" as set through ocp_nlp_solver_opts_set
+    bool weights_dirty = false, box_dirty = false, disc_dirty = false;
     ocp_nlp_in in;
     ocp_nlp_out out;
     ocp_nlp_solver solver;
@@ -90,6 +92,7 @@ int acados_create(void) {
     for (int i = 0; i < NX; i++) h->WN[i] = h->opts.WN[i];
     for (int k = 0; k < N; k++)
         for (int i = 0; i < NU; i++) { h->lbu[k][i] = h->opts.u_min; h->ubu[k][i] = h->opts.u_max; }
+    for (int k = 0; k <= N; k++) h->scaling[k] = 1.0;
     for (int k = 0; k <= N; k++) { std::memset(h->x + k * NX, 0, sizeof(double) * NX); h->x[k * NX + 3] = 1.0; }
     std::memset(h->u, 0, sizeof h->u);
     h->dims = ocp_nlp_dims{N, NX, NU, NY, NX};
@@ -166,7 +169,21 @@ int ocp_nlp_cost_model_set(ocp_nlp_config*, ocp_nlp_dims*, ocp_nlp_in*, int stag
         g->weights_dirty = true;
         return 0;
     }
+    if (!std::strcmp(field, "scaling")) {   // one double per stage; acados_solve() applies it (cfnmpc_set_cost_scaling)
+        if (!(std::isfinite(v[0]) && v[0] > 0.0)) return 1;
+        g->scaling[stage] = v[0];
+        g->disc_dirty = true;
+        return 0;
+    }
     return 1;
+}
+
+void ocp_nlp_solver_opts_set(ocp_nlp_config*, void*, const char* field, void* value) {
+    if (!g || !field || !value) return;
+    if (!std::strcmp(field, "sim_method_num_steps")) {   // stored as given; acados_solve() checks and applies it
+        g->erk_steps = *static_cast<const int*>(value);
+        g->disc_dirty = true;
+    }
 }
 
 int acados_solve(void) {
@@ -174,6 +191,15 @@ int acados_solve(void) {
     const auto t0 = std::chrono::steady_clock::now();
     for (int i = 0; i < NX; i++)
         if (g->lbx[i] != g->ubx[i]) return 1;  // x0 must be pinned: lbx == ubx (acados_mpc.cpp:581-582)
+    if (g->disc_dirty) {
+        // the engine has ONE stage scale: stages 0..N-1 must agree (the terminal stage has its own)
+        for (int k = 1; k < N; k++)
+            if (g->scaling[k] != g->scaling[0]) return 1;
+        if (g->erk_steps < 1 || g->erk_steps > CFNMPC_ERK_STEPS_MAX) return 1;
+        if (cfnmpc_set_erk_steps(g->s, g->erk_steps) != CFNMPC_OK) return 1;
+        if (cfnmpc_set_cost_scaling(g->s, g->scaling[0], g->scaling[N]) != CFNMPC_OK) return 1;
+        g->disc_dirty = false;
+    }
     if (g->weights_dirty) {
         if (cfnmpc_set_weights(g->s, g->W, g->WN) != CFNMPC_OK) return 1;
         g->weights_dirty = false;

@@ -59,6 +59,10 @@ struct cfnmpc_solver {
     cfn::SqpArgs sqp;
     unsigned* h_sqp_cnt;
     hipEvent_t sqp_ev;
+    // stage-cost scaling (cfnmpc_set_cost_scaling): the weights as the caller set them; P.W = stage_scale * W_set,
+    // P.WN = terminal_scale * WN_set
+    double W_set[17], WN_set[13];
+    double stage_scale, terminal_scale;
 };
 
 namespace {
@@ -332,8 +336,10 @@ int cfnmpc_create(cfnmpc_solver** out, int batch, const cfnmpc_opts* opts) {
     P.NW = (batch + 3) / 4;
     P.N = o.N;
     P.dt = o.dt;
-    for (int i = 0; i < 17; i++) P.W[i] = o.W[i];
-    for (int i = 0; i < 13; i++) P.WN[i] = o.WN[i];
+    for (int i = 0; i < 17; i++) P.W[i] = s->W_set[i] = o.W[i];
+    for (int i = 0; i < 13; i++) P.WN[i] = s->WN_set[i] = o.WN[i];
+    s->stage_scale = s->terminal_scale = 1.0;
+    P.erk_steps = 1;
     P.u_min = o.u_min; P.u_max = o.u_max; P.tol = o.tol; P.tau = o.tau; P.thr0 = o.thr0;
     P.lam0_min = o.lam0_min; P.mu0_scale = o.mu0_scale; P.max_iter = o.max_iter;
     P.clip_viol = o.ipm_clip_viol; P.clip_margin = o.ipm_clip_margin; P.as_skip_viol = o.as_skip_viol;
@@ -551,11 +557,35 @@ static void invalidate_graphs(cfnmpc_solver* s) { s->gvalid[0] = s->gvalid[1] = 
 int cfnmpc_set_weights(cfnmpc_solver* s, const double* W, const double* WN) {
     if (!s || (!W && !WN)) return CFNMPC_EINVAL;
     if (!weights_ok(W, WN)) return CFNMPC_EINVAL;   // validated as a whole before anything is copied
-    if (W) for (int i = 0; i < 17; i++) s->P.W[i] = W[i];
-    if (WN) for (int i = 0; i < 13; i++) s->P.WN[i] = WN[i];
+    if (W) for (int i = 0; i < 17; i++) s->P.W[i] = s->stage_scale * (s->W_set[i] = W[i]);
+    if (WN) for (int i = 0; i < 13; i++) s->P.WN[i] = s->terminal_scale * (s->WN_set[i] = WN[i]);
     invalidate_graphs(s);
     return CFNMPC_OK;  // kernel arguments: take effect at the next cfnmpc_solve
 }
+
+int cfnmpc_set_cost_scaling(cfnmpc_solver* s, double stage_scale, double terminal_scale) {
+    if (!s || !(std::isfinite(stage_scale) && stage_scale > 0) || !(std::isfinite(terminal_scale) && terminal_scale > 0))
+        return CFNMPC_EINVAL;
+    s->stage_scale = stage_scale;
+    s->terminal_scale = terminal_scale;
+    for (int i = 0; i < 17; i++) s->P.W[i] = stage_scale * s->W_set[i];
+    for (int i = 0; i < 13; i++) s->P.WN[i] = terminal_scale * s->WN_set[i];
+    invalidate_graphs(s);
+    return CFNMPC_OK;
+}
+
+int cfnmpc_set_erk_steps(cfnmpc_solver* s, int num_steps) {
+    if (!s || num_steps < 1 || num_steps > CFNMPC_ERK_STEPS_MAX) return CFNMPC_EINVAL;
+    // the fused start solve (k_linfactor, k_linearise_clist) integrates one step per interval; the development build's
+    // overlapped preparation (k_linearise_list) likewise
+    if (num_steps > 1 && (s->P.fused || s->overlap)) return CFNMPC_EINVAL;
+    s->P.erk_steps = num_steps;
+    s->lin_valid = false;
+    invalidate_graphs(s);
+    return CFNMPC_OK;
+}
+
+int cfnmpc_erk_steps(const cfnmpc_solver* s) { return s ? s->P.erk_steps : CFNMPC_EINVAL; }
 
 int cfnmpc_set_box(cfnmpc_solver* s, double u_min, double u_max) {
     if (!s || !(u_max > u_min)) return CFNMPC_EINVAL;

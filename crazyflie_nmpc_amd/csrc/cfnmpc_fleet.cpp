@@ -251,6 +251,19 @@ int cfnmpc_fleet_set_weights(cfnmpc_fleet* f, const double* W, const double* WN)
     return CFNMPC_OK;
 }
 
+// (every bucket is created from the same options, so a value one bucket refuses the first one refuses: nothing changes)
+int cfnmpc_fleet_set_erk_steps(cfnmpc_fleet* f, int num_steps) {
+    if (!f) return CFNMPC_EINVAL;
+    for (Bucket& b : f->bk) RC_TRY(cfnmpc_set_erk_steps(b.s, num_steps));
+    return CFNMPC_OK;
+}
+
+int cfnmpc_fleet_set_cost_scaling(cfnmpc_fleet* f, double stage_scale, double terminal_scale) {
+    if (!f) return CFNMPC_EINVAL;
+    for (Bucket& b : f->bk) RC_TRY(cfnmpc_set_cost_scaling(b.s, stage_scale, terminal_scale));
+    return CFNMPC_OK;
+}
+
 int cfnmpc_fleet_set_box(cfnmpc_fleet* f, double u_min, double u_max) {
     if (!f || !(u_max > u_min)) return CFNMPC_EINVAL;
     for (Bucket& b : f->bk) RC_TRY(cfnmpc_set_box(b.s, u_min, u_max));

@@ -76,6 +76,72 @@ __device__ __forceinline__ void sens_column(const JacPoint (&J)[4], const double
     SFOR(i, 0, 13, { col[i] = s0[i] + (h / 6.0) * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]); });
 }
 
+// ERK with M sub-steps per interval (cfnmpc_set_erk_steps, k_linearise_erk): one column through ONE RK4 sub-step of h = dt / M from
+// a general start: col <- A_j col (+ B_j e_c for an input column), A_j / B_j the sensitivities of sub-step j at the points J.  The
+// column-type sparsity (HQ / HW) holds at every sub-step: d Phi / d x has the block pattern of cfnmpc_model.hpp for any explicit RK.
+template <bool HQ, bool HW, bool IS_U>
+__device__ __forceinline__ void sens_step(const JacPoint (&J)[4], const double* __restrict__ u, int c, double h,
+                                          double (&col)[13]) {
+    // (slopes summed as they come, k1 + 2 k2 + 2 k3 + k4 in acc: two 13-vectors live instead of five beside the four points)
+    double s[13], k[13], acc[13], ju[4] = {0, 0, 0, 0};
+    if (IS_U) {
+        const double uc = 2.0 * (c == 0 ? u[0] : (c == 1 ? u[1] : (c == 2 ? u[2] : u[3])));
+        const double sa = (c < 2) ? 1.0 : -1.0;
+        const double sb = (c == 0 || c == 3) ? 1.0 : -1.0;
+        const double sc_ = (c == 0 || c == 2) ? 1.0 : -1.0;
+        ju[0] = KT * uc; ju[1] = KA * sa * uc; ju[2] = KB * sb * uc; ju[3] = KC * sc_ * uc;
+    }
+    jvp<HQ, HW>(J[0], col, k);
+    SFOR(i, 0, 4, { k[9 + i] += ju[i]; });
+    SFOR(i, 0, 13, { acc[i] = k[i]; s[i] = col[i] + 0.5 * h * k[i]; });
+    jvp<HQ, HW>(J[1], s, k);
+    SFOR(i, 0, 4, { k[9 + i] += ju[i]; });
+    SFOR(i, 0, 13, { acc[i] += 2 * k[i]; s[i] = col[i] + 0.5 * h * k[i]; });
+    jvp<HQ, HW>(J[2], s, k);
+    SFOR(i, 0, 4, { k[9 + i] += ju[i]; });
+    SFOR(i, 0, 13, { acc[i] += 2 * k[i]; s[i] = col[i] + h * k[i]; });
+    jvp<HQ, HW>(J[3], s, k);
+    SFOR(i, 0, 4, { k[9 + i] += ju[i]; });
+    SFOR(i, 0, 13, { col[i] = col[i] + (h / 6.0) * (acc[i] + k[i]); });
+}
+
+// One column group (NC columns c0 .. c0 + NC - 1 of one type) through M sub-steps.  Per sub-step the nominal RK points are rebuilt
+// from the carried sub-step state xs (4 f_expl + 4 jac_point), then every column of the group advances by sens_step.  Between
+// sub-steps the columns are parked in the group's store tile (rows < NS in internal order at tile[4 NS j + r], the layout
+// CFN_COL writes: lane-private, so no barrier inside), from where CFN_STORE2 takes them once.  Returns Phi_M(x, u) in xe.
+template <bool HQ, bool HW, bool IS_U, int NC, int NS>
+__device__ __forceinline__ void erk_group(const double (&x)[13], const double (&u)[4], int c0, int M, double h,
+                                          double* __restrict__ tile, double (&xe)[13]) {
+#pragma unroll 1
+    for (int j = 0; j < NC; j++) SFOR(r, 0, NS, { tile[4 * NS * j + r] = (!IS_U && ext_of(r) == c0 + j) ? 1.0 : 0.0; });
+    SFOR(e, 0, 13, { xe[e] = x[e]; });
+#pragma unroll 1
+    for (int m = 0; m < M; m++) {
+        double xt[13], ks[13], kk[13];
+        JacPoint J[4];
+        f_expl(xe, u, kk);
+        jac_point(xe, J[0]);
+        SFOR(e, 0, 13, { ks[e] = kk[e]; xt[e] = xe[e] + 0.5 * h * kk[e]; });
+        f_expl(xt, u, kk);
+        jac_point(xt, J[1]);
+        SFOR(e, 0, 13, { ks[e] += 2 * kk[e]; xt[e] = xe[e] + 0.5 * h * kk[e]; });
+        f_expl(xt, u, kk);
+        jac_point(xt, J[2]);
+        SFOR(e, 0, 13, { ks[e] += 2 * kk[e]; xt[e] = xe[e] + h * kk[e]; });
+        f_expl(xt, u, kk);
+        jac_point(xt, J[3]);
+        SFOR(e, 0, 13, { xe[e] = xe[e] + (h / 6.0) * (ks[e] + kk[e]); });
+#pragma unroll 1
+        for (int j = 0; j < NC; j++) {
+            double col[13];
+            SFOR(e, 0, 13, { col[e] = 0.0; });
+            SFOR(r, 0, NS, { col[ext_of(r)] = tile[4 * NS * j + r]; });
+            sens_step<HQ, HW, IS_U>(J, u, c0 + j, h, col);
+            SFOR(r, 0, NS, { tile[4 * NS * j + r] = col[ext_of(r)]; });
+        }
+    }
+}
+
 // Lane-per-instance (work-efficient: nothing is computed twice); one workgroup = one wavefront
 // = 64 instances, blockIdx.y = a chunk of the (mutually independent) shooting intervals.  All
 // traffic to the wave-blocked layout goes through LDS tiles so that every global load / store
@@ -106,9 +172,11 @@ static_assert(div_ok(52, 64 * 13), "k_forward: e / 52 by multiply-shift");
 //                   written in the same contiguous runs as the home blocks) -- the fused start solve never stores
 //                   (A, B, b), so the instances whose QP needs them again get them here (k_linearise_clist);
 //                   which = 0: P.ilist (count P.nipm[0]), 1: P.ilist2 (P.nipm[NI_LISTED], the interior-point fall-back rows).
-template <bool GATHER, bool CSTORE = false>
+//   ERK (k_linearise_erk): M = P.erk_steps RK4 sub-steps of dt / M per interval (erk_group); whole fleet (GATHER = false) only.
+template <bool GATHER, bool CSTORE = false, bool ERK = false>
 __device__ __forceinline__ void linearise_body(const Params& P, double* sx, double (*sc)[64 * 13], int* sinst,
                                                const int which = 0) {
+    static_assert(!ERK || !GATHER, "ERK sub-steps: whole-fleet kernel only");
     constexpr bool PAIRS = !GATHER;   // 16-byte stores of whole column groups (below)
     const int tid = threadIdx.x;
     const double h = P.dt;
@@ -204,6 +272,7 @@ __device__ __forceinline__ void linearise_body(const Params& P, double* sx, doub
         }
         int tl = tid;  // opaque per-stage copy: keeps the store offsets (82, or 162 in the list kernels) from being hoisted out
         asm volatile("" : "+v"(tl));  // of the stage loop (they would occupy that many registers for its whole length)
+        if constexpr (!ERK) {   // (one RK4 step per interval; the M-step form below)
         // nominal RK4 (classic tableau, one step per interval)
         double xt[13], k1v[13], k2v[13], k3v[13], k4v[13];
         JacPoint J[4];
@@ -318,6 +387,38 @@ __device__ __forceinline__ void linearise_body(const Params& P, double* sx, doub
         if (PAIRS) { CFN_STORE2(P.BR, SZ_B, 208, 0); }
         else { SFOR(a, 0, 4, { CFN_STORE(CSTORE ? P.cBR : P.BR, SZ_B, a, 13, a * 52); }); }
         __syncthreads();
+        } else {
+        // M sub-steps: column groups outside, sub-steps inside (erk_group), each group parked in and stored from its tile as above;
+        // the last group's nominal end point is Phi_M, from which b is formed (b leaves last).  The barriers fence the tile between
+        // a group's lane-private sub-steps and CFN_STORE2, which reads other lanes' pieces.
+        double* const scf = &sc[0][0];
+        const int M = P.erk_steps;
+        const double hs = h / M;
+        double xe[13];
+        erk_group<false, false, false, 3, 6>(x, u, 7, M, hs, scf + CFN_TB(72, 6), xe);        // velocity columns: rows p, v
+        __syncthreads();
+        CFN_STORE2(P.AR, SZ_A, 72, 0);
+        __syncthreads();
+        erk_group<true, false, false, 4, 10>(x, u, 3, M, hs, scf + CFN_TB(160, 10), xe);      // quaternion columns: rows p, v, q
+        __syncthreads();
+        CFN_STORE2(P.AR, SZ_A, 160, 4 * ar_pre(3));
+        land_x(sxa, xr);   // x_{k+2} -> the tile x_k was read from; tiles swap roles (sxa = x_{k+1} from here)
+        { double* t_ = sxa; sxa = sxb; sxb = t_; }
+        __syncthreads();
+        erk_group<true, true, false, 3, 13>(x, u, 10, M, hs, scf + CFN_TB(156, 13), xe);      // rate columns: all rows
+        __syncthreads();
+        CFN_STORE2(P.AR, SZ_A, 156, 4 * ar_pre(7));
+        __syncthreads();
+        erk_group<true, true, true, 4, 13>(x, u, 0, M, hs, scf + CFN_TB(208, 13), xe);        // input columns: all rows
+        __syncthreads();
+        CFN_STORE2(P.BR, SZ_B, 208, 0);
+        __syncthreads();
+        // b = Phi_M - x_{k+1} through the tile (internal order)
+        SFOR(r, 0, 13, { sc[0][tid * 13 + r] = xe[ext_of(r)] - sxa[tid * 13 + r]; });
+        __syncthreads();
+        CFN_STORE2(P.b, SZ_V13, 52, 0);
+        __syncthreads();
+        }
 #undef CFN_STORE2
 #undef CFN_TB
 #undef CFN_STORE
@@ -336,6 +437,12 @@ KALIGN __global__ __launch_bounds__(64) void k_linearise(Params P) {
     __shared__ __attribute__((aligned(16))) double sc[4][64 * 13];    // the tile of a group of up to four sensitivity columns
     __shared__ int sinst[64];
     linearise_body<false>(P, sx, sc, sinst);
+}
+KALIGN __global__ __launch_bounds__(64) void k_linearise_erk(Params P) {   // the same with P.erk_steps > 1 RK4 sub-steps per interval
+    __shared__ double sx[2 * 64 * 13];
+    __shared__ __attribute__((aligned(16))) double sc[4][64 * 13];
+    __shared__ int sinst[64];
+    linearise_body<false, false, true>(P, sx, sc, sinst);
 }
 #ifdef CFN_DEV   // (overlapped preparation: development builds only)
 __global__ __launch_bounds__(64) void k_linearise_list(Params P) {
@@ -900,7 +1007,10 @@ __device__ __forceinline__ int head_want(const Params& P, int last_tight) {
 // (whose heads of at most H stages read nothing behind H).  An instance that is feasible over [0, H) and violates a bound
 // behind H is a LATE row: part 2 appends it to the compacted list behind its end (P.nipm[NI_LATE] counts them) with the head its
 // tight stages ask for and the flag k_as_retry picks up (P.done = 2).
-template <bool COND, bool FUSED_PT = false, int SPLIT = 0>
+// ERK (the _erk kernels, P.erk_steps = M > 1): the candidate is the directional derivative of M RK4 sub-steps of dt / M, each the
+// FUSED_PT form (lf_point) from the carried sub-step state and direction -- what the stored-block sweep computes from
+// k_linearise_erk's A, B, b up to rounding.
+template <bool COND, bool FUSED_PT = false, int SPLIT = 0, bool ERK = false>
 __device__ __forceinline__ void forward_body(const Params& P, double* xs, double* cs, int* sflag) {
     // 13-vectors travel through LDS tiles [instance][13] so that every global access of the wave
     // is a contiguous run (as in k_linearise); K, d, u, v are 32-byte runs per lane already.
@@ -1014,6 +1124,35 @@ __device__ __forceinline__ void forward_body(const Params& P, double* xs, double
             jud[3] = 2.0 * KC * (p0 - p1 + p2 - p3);
         }
         double dxp[13];   // dx_{k+1} + x_{k+1}
+        if constexpr (ERK) {
+            const int M = P.erk_steps;
+            const double hs = h / M;
+            double rot[4];
+            {
+                const double s1 = uc[0] * uc[0], s2 = uc[1] * uc[1], s3 = uc[2] * uc[2], s4 = uc[3] * uc[3];
+                rot[0] = KT * (s1 + s2 + s3 + s4);
+                rot[1] = KA * (s1 + s2 - s3 - s4);
+                rot[2] = KB * (s1 - s2 - s3 + s4);
+                rot[3] = KC * (s1 - s2 + s3 - s4);
+            }
+#pragma unroll 1
+            for (int m = 0; m < M; m++) {   // (x, s) <- (Phi_h(x), dPhi_h (s, du)) in the external order
+                double xq[10], sq[10];
+                SFOR(e, 0, 10, { xq[e] = x[e + 3]; sq[e] = s[e + 3]; });
+                lf_point(xq, sq, rot, jud, kk, dk);
+                SFOR(e, 0, 13, { acc[e] = dk[e]; ks[e] = kk[e]; });
+                SFOR(e, 0, 10, { xq[e] = x[e + 3] + 0.5 * hs * kk[e + 3]; sq[e] = s[e + 3] + 0.5 * hs * dk[e + 3]; });
+                lf_point(xq, sq, rot, jud, kk, dk);
+                SFOR(e, 0, 13, { acc[e] += 2.0 * dk[e]; ks[e] += 2.0 * kk[e]; });
+                SFOR(e, 0, 10, { xq[e] = x[e + 3] + 0.5 * hs * kk[e + 3]; sq[e] = s[e + 3] + 0.5 * hs * dk[e + 3]; });
+                lf_point(xq, sq, rot, jud, kk, dk);
+                SFOR(e, 0, 13, { acc[e] += 2.0 * dk[e]; ks[e] += 2.0 * kk[e]; });
+                SFOR(e, 0, 10, { xq[e] = x[e + 3] + hs * kk[e + 3]; sq[e] = s[e + 3] + hs * dk[e + 3]; });
+                lf_point(xq, sq, rot, jud, kk, dk);
+                SFOR(e, 0, 13, { x[e] += (hs / 6.0) * (ks[e] + kk[e]); s[e] += (hs / 6.0) * (acc[e] + dk[e]); });
+            }
+            SFOR(i, 0, 13, { constexpr int e = ext_of(i); dxp[i] = s[e] + x[e]; });
+        } else {
         if constexpr (FUSED_PT) {
             double rot[4];
             {
@@ -1067,6 +1206,7 @@ __device__ __forceinline__ void forward_body(const Params& P, double* xs, double
             const double phi = x[e] + (h / 6.0) * (ks[e] + kk[e]);
             dxp[i] = s[e] + (h / 6.0) * (acc[e] + dk[e]) + phi;
         });
+        }
         // candidate tile out, next stage's tiles in
         __syncthreads();
         {
@@ -1208,6 +1348,27 @@ __global__ __launch_bounds__(64) void k_cforward(Params P) {
     __shared__ double xs[64 * 13], cs[64 * 13];
     __shared__ int sflag[64];
     forward_body<true>(P, xs, cs, sflag);
+}
+// the same sweeps with P.erk_steps > 1 RK4 sub-steps per interval
+KALIGN __global__ __launch_bounds__(64) void k_forward_erk(Params P) {
+    __shared__ double xs[64 * 13], cs[64 * 13];
+    __shared__ int sflag[64];
+    forward_body<false, true, 0, true>(P, xs, cs, sflag);
+}
+KALIGN __global__ __launch_bounds__(64) void k_forward_p1_erk(Params P) {
+    __shared__ double xs[64 * 13], cs[64 * 13];
+    __shared__ int sflag[64];
+    forward_body<false, true, 1, true>(P, xs, cs, sflag);
+}
+KALIGN __global__ __launch_bounds__(64) void k_forward_p2_erk(Params P) {
+    __shared__ double xs[64 * 13], cs[64 * 13];
+    __shared__ int sflag[64];
+    forward_body<false, true, 2, true>(P, xs, cs, sflag);
+}
+__global__ __launch_bounds__(64) void k_cforward_erk(Params P) {
+    __shared__ double xs[64 * 13], cs[64 * 13];
+    __shared__ int sflag[64];
+    forward_body<true, false, 0, true>(P, xs, cs, sflag);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3077,7 +3238,7 @@ __global__ void k_reinit_failed(Params P) {
 // access of the wave a contiguous run).  Per instance:
 //   res_step = max |w_j - w_{j-1}| over all x_k, u_k -- the Gauss-Newton step, zero iff w_j is a KKT point (Q, R > 0); the
 //              stationarity measure of this solve, NOT acados' res_stat;
-//   res_eq   = max(|x_0 - x0|, max_k |x_{k+1} - Phi(x_k, u_k)|) at w_j, Phi = one RK4 step over dt (f_expl, as k_linearise);
+//   res_eq   = max(|x_0 - x0|, max_k |x_{k+1} - Phi(x_k, u_k)|) at w_j, Phi = P.erk_steps RK4 steps over dt (f_expl, as k_linearise);
 //   res_ineq = largest violation of the input box at w_j (the scalar box, or the per-stage boxes while they are set).
 // Classification: QP status 4 in step j -> done, status 4 (the step kept the iterate); all three within their tolerances ->
 // done, status 0; otherwise status 2 (final once j = max_iter).  A row done at an EARLIER iteration is frozen: its old
@@ -3096,7 +3257,8 @@ __global__ __launch_bounds__(64) void k_sqp_check(Params P, SqpArgs A) {
     const size_t w = (size_t)(inst >> 2);
     const int q = inst & 3;
     const int w0 = blockIdx.x * 16;
-    const double h = P.dt;
+    const int M = P.erk_steps;
+    const double h = P.dt / M;
     const size_t i4b = P.v4b ? ((size_t)w * N * 4 + q) * 4 : (size_t)inst * N * 4;   // this lane's 4-vectors (Params.v4b)
     const size_t i4s = P.v4b ? 16 : 4;
     auto el13 = [&](const double* f, int e, int stages, int k) -> gdouble* {   // (k_forward's accessor)
@@ -3150,17 +3312,21 @@ __global__ __launch_bounds__(64) void k_sqp_check(Params P, SqpArgs A) {
             if (P.lbs) { lo = gm(P.lbs)[i4b + (size_t)k * i4s + a]; hi = gm(P.ubs)[i4b + (size_t)k * i4s + a]; }
             r_ineq = max_nan(r_ineq, fmax(lo - un[a], un[a] - hi));
         });
-        // Phi(x_k, u_k): one RK4 step over dt (model vectors in the EXTERNAL order)
+        // Phi(x_k, u_k): M = P.erk_steps RK4 steps over h = dt / M (model vectors in the EXTERNAL order)
         double x[13], xt[13], kk[13], ks[13];
         SFOR(e, 0, 13, { x[e] = xn[int_of(e)]; });
-        f_expl(x, un, kk);
-        SFOR(e, 0, 13, { ks[e] = kk[e]; xt[e] = x[e] + 0.5 * h * kk[e]; });
-        f_expl(xt, un, kk);
-        SFOR(e, 0, 13, { ks[e] += 2.0 * kk[e]; xt[e] = x[e] + 0.5 * h * kk[e]; });
-        f_expl(xt, un, kk);
-        SFOR(e, 0, 13, { ks[e] += 2.0 * kk[e]; xt[e] = x[e] + h * kk[e]; });
-        f_expl(xt, un, kk);
-        SFOR(i, 0, 13, { constexpr int e = ext_of(i); phi[i] = x[e] + (h / 6.0) * (ks[e] + kk[e]); });
+#pragma unroll 1
+        for (int m = 0; m < M; m++) {
+            f_expl(x, un, kk);
+            SFOR(e, 0, 13, { ks[e] = kk[e]; xt[e] = x[e] + 0.5 * h * kk[e]; });
+            f_expl(xt, un, kk);
+            SFOR(e, 0, 13, { ks[e] += 2.0 * kk[e]; xt[e] = x[e] + 0.5 * h * kk[e]; });
+            f_expl(xt, un, kk);
+            SFOR(e, 0, 13, { ks[e] += 2.0 * kk[e]; xt[e] = x[e] + h * kk[e]; });
+            f_expl(xt, un, kk);
+            SFOR(e, 0, 13, { x[e] += (h / 6.0) * (ks[e] + kk[e]); });
+        }
+        SFOR(i, 0, 13, { constexpr int e = ext_of(i); phi[i] = x[e]; });
         cur = nxt;
     }
     bool open = false;
@@ -3191,7 +3357,8 @@ __global__ __launch_bounds__(64) void k_sqp_check(Params P, SqpArgs A) {
 static inline int imin_h(int a, int b) { return a < b ? a : b; }
 static inline int imax_h(int a, int b) { return a > b ? a : b; }
 void launch_linearise(const Params& P, int chunks, hipStream_t st) {
-    hipLaunchKernelGGL(k_linearise, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
+    if (P.erk_steps > 1) hipLaunchKernelGGL(k_linearise_erk, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
+    else hipLaunchKernelGGL(k_linearise, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
 }
 #ifdef CFN_DEV
 void launch_linearise_list(const Params& P, int chunks, hipStream_t st) {
@@ -3218,7 +3385,9 @@ void launch_qp_start(const Params& P, hipStream_t st, hipEvent_t* ev, bool skip_
 #ifdef CFN_DEV
         if (P.forward_half) { hipLaunchKernelGGL(k_forward_half, dim3((P.B + 63) / 64), dim3(64), 0, st, P); } else
 #endif
-        if (P.fwd_split) hipLaunchKernelGGL(k_forward_p1, dim3((P.B + 63) / 64), dim3(64), 0, st, P);   // part two: launch_qp_ipm
+        if (P.fwd_split && P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p1_erk, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
+        else if (P.fwd_split) hipLaunchKernelGGL(k_forward_p1, dim3((P.B + 63) / 64), dim3(64), 0, st, P);   // part two: launch_qp_ipm
+        else if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_erk, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
         else hipLaunchKernelGGL(k_forward, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
     }
     if (ev) (void)hipEventRecord(ev[1], st);
@@ -3238,7 +3407,12 @@ void launch_factor_only(const Params& P, hipStream_t st) {
     hipLaunchKernelGGL(k_factor, dim3(P.NW), dim3(64), 0, st, P);
 }
 void launch_cforward(const Params& P, hipStream_t st) {
-    hipLaunchKernelGGL(k_cforward, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
+    if (P.erk_steps > 1) hipLaunchKernelGGL(k_cforward_erk, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
+    else hipLaunchKernelGGL(k_cforward, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
+}
+static void launch_forward_p2(const Params& P, hipStream_t st) {   // second part of the split sweep
+    if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p2_erk, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
+    else hipLaunchKernelGGL(k_forward_p2, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
 }
 // ev (optional): event recorded after the active-set kernels (before the interior-point launch for what they left)
 void launch_qp_ipm(const Params& P, hipStream_t st, hipEvent_t* ev) {
@@ -3290,7 +3464,7 @@ void launch_qp_ipm(const Params& P, hipStream_t st, hipEvent_t* ev) {
                 Params PA = P;
                 PA.as_range = 1;
                 (void)hipStreamWaitEvent(side2, (hipEvent_t)P.as_fork, 0);
-                hipLaunchKernelGGL(k_forward_p2, dim3((P.B + 63) / 64), dim3(64), 0, side2, P);
+                launch_forward_p2(P, side2);
                 // (the rows with heads behind the split point -- PB's range: rare -- are left to k_as_retry below: a launch behind
                 //  part two, which is the longest chain of this group, cost 5 + 8 us per step whether it had work or not)
                 (void)hipEventRecord((hipEvent_t)P.as_join2, side2);
@@ -3298,7 +3472,7 @@ void launch_qp_ipm(const Params& P, hipStream_t st, hipEvent_t* ev) {
                 hipLaunchKernelGGL(k_as_solves, dim3(P.NW), dim3(64), 0, side, PA);
                 (void)hipEventRecord((hipEvent_t)P.as_join, side);
             } else {
-                if (p1_ran) hipLaunchKernelGGL(k_forward_p2, dim3((P.B + 63) / 64), dim3(64), 0, st, P);   // no side streams: in order
+                if (p1_ran) launch_forward_p2(P, st);   // no side streams: in order
                 if (side && !p1_ran) {
                     (void)hipStreamWaitEvent(side, (hipEvent_t)P.as_fork, 0);
                     hipLaunchKernelGGL(k_as_solves, dim3(P.NW), dim3(64), 0, side, P);

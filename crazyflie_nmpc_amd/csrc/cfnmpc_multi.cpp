@@ -261,6 +261,19 @@ int cfnmpc_multi_set_weights(cfnmpc_multi* m, const double* W, const double* WN)
     return CFNMPC_OK;
 }
 
+int cfnmpc_multi_set_erk_steps(cfnmpc_multi* m, int num_steps) {
+    if (!m) return CFNMPC_EINVAL;
+    for (Shard& s : m->sh) RC_TRY(m->mixed ? cfnmpc_fleet_set_erk_steps(s.f, num_steps) : cfnmpc_set_erk_steps(s.s, num_steps));
+    return CFNMPC_OK;
+}
+
+int cfnmpc_multi_set_cost_scaling(cfnmpc_multi* m, double stage_scale, double terminal_scale) {
+    if (!m) return CFNMPC_EINVAL;
+    for (Shard& s : m->sh)
+        RC_TRY(m->mixed ? cfnmpc_fleet_set_cost_scaling(s.f, stage_scale, terminal_scale) : cfnmpc_set_cost_scaling(s.s, stage_scale, terminal_scale));
+    return CFNMPC_OK;
+}
+
 int cfnmpc_multi_init_iterate(cfnmpc_multi* m, int mode) {
     if (!m) return CFNMPC_EINVAL;
     for (Shard& s : m->sh) RC_TRY(m->mixed ? cfnmpc_fleet_init_iterate(s.f, mode, s.st) : cfnmpc_init_iterate(s.s, mode, s.st));

@@ -179,6 +179,8 @@ struct Params {
                                  // 2 = k_linfactor for the factorisation, stored blocks for everything else (validation)
     int cond_N2, cond_M, cond_rem;
     double *cb;                  // condensed blocks, [instance][block][cb_size(w_max)] (layout: cfnmpc_pcond.hip)
+    int erk_steps;               // M: classic RK4 steps of dt / M per shooting interval (cfnmpc_set_erk_steps; 1 = k_linearise / k_forward,
+                                 // M > 1 = their _erk variants; k_sqp_check reads it either way)
 };
 
 // The linearisation (AR, BR, b) of the HOME blocks: [group of 16 blocks][stage][block of the group][sz] -- a lane-per-instance wave

@@ -98,6 +98,12 @@ class MixedHorizonFleet:
     def set_box(self, u_min, u_max):
         _check(self._L.cfnmpc_fleet_set_box(self._h, float(u_min), float(u_max)), "cfnmpc_fleet_set_box")
 
+    def set_erk_steps(self, n):
+        _check(self._L.cfnmpc_fleet_set_erk_steps(self._h, int(n)), "cfnmpc_fleet_set_erk_steps")
+
+    def set_cost_scaling(self, stage=1.0, terminal=1.0):
+        _check(self._L.cfnmpc_fleet_set_cost_scaling(self._h, float(stage), float(terminal)), "cfnmpc_fleet_set_cost_scaling")
+
     def set_box_stages(self, lb=None, ub=None):
         """per-stage / per-input boxes, host arrays [B][Nmax][4] (vehicle i uses rows 0..N_i-1); None, None: scalar box"""
         if lb is None and ub is None:

@@ -127,6 +127,16 @@ class MultiGpuFleet:
     def set_box(self, u_min, u_max):
         assert self._L.cfnmpc_multi_set_box(self._h, float(u_min), float(u_max)) == 0
 
+    def set_erk_steps(self, n):
+        rc = self._L.cfnmpc_multi_set_erk_steps(self._h, int(n))
+        if rc != 0:
+            raise ValueError(f"cfnmpc_multi_set_erk_steps failed with code {rc}")
+
+    def set_cost_scaling(self, stage=1.0, terminal=1.0):
+        rc = self._L.cfnmpc_multi_set_cost_scaling(self._h, float(stage), float(terminal))
+        if rc != 0:
+            raise ValueError(f"cfnmpc_multi_set_cost_scaling failed with code {rc}")
+
     def set_box_stages(self, lb=None, ub=None):
         """per-stage / per-input boxes [B][N][4] of the whole fleet; None, None: back to the scalar box"""
         if lb is None and ub is None:

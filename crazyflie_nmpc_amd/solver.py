@@ -158,6 +158,18 @@ class BatchSolver:
     def set_box(self, u_min, u_max):
         _check(self._L.cfnmpc_set_box(self._h, float(u_min), float(u_max)), "cfnmpc_set_box")
 
+    def set_erk_steps(self, n):
+        """RK4 steps of dt / n per shooting interval (acados sim_method_num_steps), 1 <= n <= 8; default 1."""
+        _check(self._L.cfnmpc_set_erk_steps(self._h, int(n)), "cfnmpc_set_erk_steps")
+
+    @property
+    def erk_steps(self):
+        return int(self._L.cfnmpc_erk_steps(self._h))
+
+    def set_cost_scaling(self, stage=1.0, terminal=1.0):
+        """Effective weights stage * W (stages 0..N-1) and terminal * WN; newer acados uses (dt, 1)."""
+        _check(self._L.cfnmpc_set_cost_scaling(self._h, float(stage), float(terminal)), "cfnmpc_set_cost_scaling")
+
     def set_box_stages(self, lb=None, ub=None):
         """Per-stage, per-input box [B][N][4] (acados' "lbu" / "ubu" on individual stages); None, None: back to
         the scalar box."""

@@ -64,11 +64,18 @@ int acados_free(void);
  *                if they are inadmissible (lb > ub or NaN somewhere)
  *   cost:        "yref" (17 doubles for stage < N, 13 for stage N); "W" (17x17 resp. 13x13,
  *                diagonal read from either major order; applies to every stage; state weights
- *                >= 0, input weights > 0, checked as a whole before anything is stored) */
+ *                >= 0, input weights > 0, checked as a whole before anything is stored); "scaling" (1 double,
+ *                stage 0..N, finite and > 0, default 1: the factor of that stage's cost, acados' cost_scaling --
+ *                newer acados sets dt for stages < N and 1 for stage N).  Stored; the next acados_solve() applies
+ *                it and returns 1 without solving if stages 0..N-1 hold different values (the engine has one
+ *                stage scale and one terminal scale) */
 int ocp_nlp_constraints_model_set(ocp_nlp_config *config, ocp_nlp_dims *dims, ocp_nlp_in *in, int stage,
                                   const char *field, void *value);
 int ocp_nlp_cost_model_set(ocp_nlp_config *config, ocp_nlp_dims *dims, ocp_nlp_in *in, int stage,
                            const char *field, void *value);
+/* ---- solver options: "sim_method_num_steps" (int: RK4 steps per shooting interval, default 1).  Stored; the next
+ *      acados_solve() applies it and returns 1 without solving if it is outside 1..8.  Other fields are ignored. */
+void ocp_nlp_solver_opts_set(ocp_nlp_config *config, void *opts_, const char *field, void *value);
 /* ---- getter (copy-out), acados_mpc.cpp:619-625, 681-682: "x" (13) stage 0..N, "u" (4) stage 0..N-1 */
 void ocp_nlp_out_get(ocp_nlp_config *config, ocp_nlp_dims *dims, ocp_nlp_out *out, int stage,
                      const char *field, void *value);

@@ -244,6 +244,20 @@ int cfnmpc_set_weights(cfnmpc_solver *s, const double *W /*[17]*/, const double 
  * inputs, stages and instances (generate_c_code.py:133-134).  Takes effect at the next
  * cfnmpc_solve.  Per-stage, per-input boxes: cfnmpc_set_box_stages below. */
 int cfnmpc_set_box(cfnmpc_solver *s, double u_min, double u_max);
+/* Discretisation and cost scaling of the OCP, to match a given acados build.  A bad value returns
+ * CFNMPC_EINVAL and changes nothing; both setters invalidate captured step graphs, as cfnmpc_set_weights does.
+ *   cfnmpc_set_erk_steps: num_steps = M classic RK4 steps of dt / M per shooting interval (acados sim_method_num_steps),
+ *     1 <= M <= CFNMPC_ERK_STEPS_MAX, default 1.  The linearisation, the matrix-free forward sweep and the SQP residual
+ *     (cfnmpc_solve_sqp: res_eq) use Phi_M.  M > 1 is refused beside start_solve 2 or 3 (the fused start solve integrates one
+ *     step per interval); every other option works with it.  cfnmpc_erk_steps returns M (CFNMPC_EINVAL for NULL).
+ *   cfnmpc_set_cost_scaling: the stage cost of stages 0..N-1 is multiplied by stage_scale, the terminal cost by
+ *     terminal_scale (both finite and > 0; default 1, 1).  It scales whatever W / WN are set, before and after later
+ *     cfnmpc_set_weights calls: the effective weights are stage_scale * W and terminal_scale * WN.  Newer acados scales
+ *     by (dt, 1). */
+#define CFNMPC_ERK_STEPS_MAX 8
+int cfnmpc_set_erk_steps(cfnmpc_solver *s, int num_steps);
+int cfnmpc_erk_steps(const cfnmpc_solver *s);
+int cfnmpc_set_cost_scaling(cfnmpc_solver *s, double stage_scale, double terminal_scale);
 /* Per-stage, per-input box: lb, ub [B][N][4] (what "lbu" / "ubu" on INDIVIDUAL stages set in acados -- the reference's
  * FIXED_U0 variant pins stage 0 to the input in flight, lbu = ubu = u1, acados_mpc.cpp:605-608).  lb[i] = ub[i] makes
  * that input an equality (the active-set solves keep it fixed whatever its multiplier's sign; the interior-point
@@ -405,6 +419,9 @@ int cfnmpc_fleet_set_x0(cfnmpc_fleet *f, const double *x0, int on_device, void *
 int cfnmpc_fleet_set_yref(cfnmpc_fleet *f, const double *yref, const double *yref_e, int on_device, void *stream);
 int cfnmpc_fleet_set_weights(cfnmpc_fleet *f, const double *W /*[17]*/, const double *WN /*[13]*/);
 int cfnmpc_fleet_set_box(cfnmpc_fleet *f, double u_min, double u_max);
+/* cfnmpc_set_erk_steps / cfnmpc_set_cost_scaling for every bucket */
+int cfnmpc_fleet_set_erk_steps(cfnmpc_fleet *f, int num_steps);
+int cfnmpc_fleet_set_cost_scaling(cfnmpc_fleet *f, double stage_scale, double terminal_scale);
 /* cfnmpc_set_box_stages for a fleet: HOST arrays [B][Nmax][4] in the fleet's vehicle order (rows behind a vehicle's own
  * horizon are ignored); NULL, NULL: back to the scalar box */
 int cfnmpc_fleet_set_box_stages(cfnmpc_fleet *f, const double *lb, const double *ub);
@@ -463,6 +480,9 @@ int cfnmpc_multi_get_stats(cfnmpc_multi *m, int *status, int *qp_iter, double *r
 /* cfnmpc_set_box / cfnmpc_set_box_stages (host arrays [B][N][4] of the whole fleet) for every shard */
 int cfnmpc_multi_set_box(cfnmpc_multi *m, double u_min, double u_max);
 int cfnmpc_multi_set_box_stages(cfnmpc_multi *m, const double *lb, const double *ub);
+/* cfnmpc_set_erk_steps / cfnmpc_set_cost_scaling for every shard */
+int cfnmpc_multi_set_erk_steps(cfnmpc_multi *m, int num_steps);
+int cfnmpc_multi_set_cost_scaling(cfnmpc_multi *m, double stage_scale, double terminal_scale);
 
 const char *cfnmpc_version(void);
 
