@@ -26,6 +26,8 @@ SYMBOLS = [
     "cfnmpc_multi_create_horizons", "cfnmpc_multi_shard_fleet", "cfnmpc_shard_by_horizon",
     "cfnmpc_set_erk_steps", "cfnmpc_erk_steps", "cfnmpc_set_cost_scaling", "cfnmpc_fleet_set_erk_steps",
     "cfnmpc_fleet_set_cost_scaling", "cfnmpc_multi_set_erk_steps", "cfnmpc_multi_set_cost_scaling",
+    "cfnmpc_set_model_params", "cfnmpc_get_model_params", "cfnmpc_fleet_set_model_params", "cfnmpc_multi_set_model_params",
+    "cfnmpc_sim_params",
 ]
 ABI_VERSION = 9   # CFNMPC_ABI_VERSION of the include/cfnmpc.h this binding was written against
 
@@ -112,6 +114,11 @@ def lib():
     L.cfnmpc_fleet_set_cost_scaling.argtypes = [vp, dbl, dbl]
     L.cfnmpc_multi_set_erk_steps.argtypes = [vp, i32]
     L.cfnmpc_multi_set_cost_scaling.argtypes = [vp, dbl, dbl]
+    L.cfnmpc_set_model_params.argtypes = [vp, vp, i32, vp]
+    L.cfnmpc_get_model_params.argtypes = [vp, vp, i32, vp]
+    L.cfnmpc_fleet_set_model_params.argtypes = [vp, vp]
+    L.cfnmpc_multi_set_model_params.argtypes = [vp, vp]
+    L.cfnmpc_sim_params.argtypes = [i32, vp, vp, vp, dbl, i32, vp, i32, vp]
     for name, at in (("cfnmpc_debug_chunked_pair", [vp, i32, i32, vp, vp]), ("cfnmpc_debug_checksum", [vp, vp]),
                      ("cfnmpc_debug_solve_part", [vp, i32, i32, vp])):   # development builds only (make DEV=1, csrc/cfnmpc_dev.h)
         if hasattr(L, name):

@@ -63,6 +63,10 @@ struct cfnmpc_solver {
     // P.WN = terminal_scale * WN_set
     double W_set[17], WN_set[13];
     double stage_scale, terminal_scale;
+    // per-instance model parameters (cfnmpc_set_model_params): the caller's rows [B][NPAR] while set (empty: nominal) and the
+    // device block of derived constants P.mpar points to while set (allocated at the first call, kept for later ones)
+    std::vector<double> mp_rows;
+    double* mpar_buf;
 };
 
 namespace {
@@ -587,6 +591,68 @@ int cfnmpc_set_erk_steps(cfnmpc_solver* s, int num_steps) {
 
 int cfnmpc_erk_steps(const cfnmpc_solver* s) { return s ? s->P.erk_steps : CFNMPC_EINVAL; }
 
+static_assert(CFNMPC_NP == cfn::NPAR, "parameter row");
+int cfnmpc_set_model_params(cfnmpc_solver* s, const double* p, int on_device, void* stream) {
+    if (!s) return CFNMPC_EINVAL;
+    DeviceGuard dg(s);
+    cfn::Params& P = s->P;
+    if (!p) {   // back to the folded constants (the default kernels)
+        if (P.mpar) { P.mpar = nullptr; s->lin_valid = false; invalidate_graphs(s); }
+        s->mp_rows.clear();
+        return CFNMPC_OK;
+    }
+    // the fused start solve (k_linfactor, k_linearise_clist) and the development build's overlapped preparation
+    // (k_linearise_list) integrate with the folded constants
+    if (P.fused || s->overlap) return CFNMPC_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t B = P.B, n = B * cfn::NPAR;
+    std::vector<double> rows(n);
+    if (is_host(on_device)) {
+        std::copy_n(p, n, rows.data());
+    } else {   // device rows: one copy to the host to validate them
+        HIP_TRY(hipMemcpyAsync(rows.data(), p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (!cfn::model_params_ok(rows.data(), n)) return CFNMPC_EINVAL;
+    // derived constants, [NK][S] structure-of-arrays over every workspace row (padding rows and the spare block: nominal)
+    const size_t S = ((size_t)P.NW + 1) * 4;
+    std::vector<double> k((size_t)cfn::NK * S);
+    for (size_t i = 0; i < S; i++) {
+        double ki[cfn::NK];
+        cfn::derive_k(i < B ? rows.data() + i * cfn::NPAR : cfn::NOM_P, ki);
+        for (int j = 0; j < cfn::NK; j++) k[(size_t)j * S + i] = ki[j];
+    }
+    if (!s->mpar_buf) {
+        const int rc = dev_alloc(s, &s->mpar_buf, k.size());
+        if (rc != CFNMPC_OK) return rc;
+    }
+    // in place, in stream order, complete on return: a captured step graph (which holds the pointer) replays with the new values
+    HIP_TRY(hipMemcpyAsync(s->mpar_buf, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (!P.mpar) { P.mpar = s->mpar_buf; invalidate_graphs(s); }   // other kernels from here on
+    s->lin_valid = false;
+    s->mp_rows = std::move(rows);
+    return CFNMPC_OK;
+}
+
+int cfnmpc_get_model_params(cfnmpc_solver* s, double* p, int on_device, void* stream) {
+    if (!s || !p) return CFNMPC_EINVAL;
+    DeviceGuard dg(s);
+    const size_t B = s->P.B, n = B * cfn::NPAR;
+    std::vector<double> nom;
+    const double* src = s->mp_rows.data();
+    if (s->mp_rows.empty()) {
+        nom.resize(n);
+        for (size_t i = 0; i < B; i++) std::copy_n(cfn::NOM_P, cfn::NPAR, nom.data() + i * cfn::NPAR);
+        src = nom.data();
+    }
+    if (is_host(on_device)) { std::copy_n(src, n, p); return CFNMPC_OK; }
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(p, src, n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (src is a host temporary)
+    return CFNMPC_OK;
+}
+
 int cfnmpc_set_box(cfnmpc_solver* s, double u_min, double u_max) {
     if (!s || !(u_max > u_min)) return CFNMPC_EINVAL;
     s->P.u_min = u_min;   // kernel arguments: take effect at the next cfnmpc_solve
@@ -974,12 +1040,16 @@ int cfnmpc_get_stats(cfnmpc_solver* s, int* status, int* qp_iter, double* res, i
     return CFNMPC_OK;
 }
 
-int cfnmpc_sim(int batch, const double* x, const double* u, double T, int steps, double* xn, int on_device,
-               void* stream) {
+namespace {
+// cfnmpc_sim (p = NULL: the folded constants) and cfnmpc_sim_params (p [batch][NPAR])
+int sim_impl(int batch, const double* x, const double* u, const double* p, double T, int steps, double* xn, int on_device,
+             void* stream) {
     if (batch <= 0 || !x || !u || !xn || steps < 1 || !(T > 0)) return CFNMPC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
+    if (p && is_host(on_device) && !cfn::model_params_ok(p, (size_t)batch * cfn::NPAR)) return CFNMPC_EINVAL;
     if (!is_host(on_device)) {
-        cfn::launch_sim(batch, x, u, T, steps, xn, st);
+        if (p) cfn::launch_sim_par(batch, x, u, p, T, steps, xn, st);
+        else cfn::launch_sim(batch, x, u, T, steps, xn, st);
         HIP_TRY(hipGetLastError());
         return CFNMPC_OK;
     }
@@ -992,7 +1062,7 @@ int cfnmpc_sim(int batch, const double* x, const double* u, double T, int steps,
     HIP_TRY(hipGetDevice(&devi));
     if (devi < 0 || devi >= 64) return CFNMPC_EHIP;
     std::lock_guard<std::mutex> lock(mtx[devi]);
-    const size_t B = batch, need = B * 30;
+    const size_t B = batch, need = B * (30 + (p ? cfn::NPAR : 0));
     if (cap[devi] < need) {
         if (scratch[devi]) (void)hipFree(scratch[devi]);
         scratch[devi] = nullptr; cap[devi] = 0;
@@ -1002,11 +1072,29 @@ int cfnmpc_sim(int batch, const double* x, const double* u, double T, int steps,
     double *dx = scratch[devi], *du = dx + B * 13, *dn = du + B * 4;
     HIP_TRY(hipMemcpyAsync(dx, x, B * 13 * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(du, u, B * 4 * 8, hipMemcpyHostToDevice, st));
-    cfn::launch_sim(batch, dx, du, T, steps, dn, st);
+    if (p) {
+        double* dp = dn + B * 13;
+        HIP_TRY(hipMemcpyAsync(dp, p, B * cfn::NPAR * 8, hipMemcpyHostToDevice, st));
+        cfn::launch_sim_par(batch, dx, du, dp, T, steps, dn, st);
+    } else {
+        cfn::launch_sim(batch, dx, du, T, steps, dn, st);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(xn, dn, B * 13 * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return CFNMPC_OK;
+}
+}  // namespace
+
+int cfnmpc_sim(int batch, const double* x, const double* u, double T, int steps, double* xn, int on_device,
+               void* stream) {
+    return sim_impl(batch, x, u, nullptr, T, steps, xn, on_device, stream);
+}
+
+int cfnmpc_sim_params(int batch, const double* x, const double* u, const double* p, double T, int steps, double* xn,
+                      int on_device, void* stream) {
+    if (!p) return CFNMPC_EINVAL;
+    return sim_impl(batch, x, u, p, T, steps, xn, on_device, stream);
 }
 
 int cfnmpc_estimate(int batch, const double* meas, double* filt, const double* u, double dt, int use_lpf, double delay,
@@ -1157,6 +1245,7 @@ int cfnmpc_debug_start_factor(cfnmpc_solver* s, int mode, int reps, double* ms, 
     // k_factor / k_linfactor address the home 4-vectors in the wave-blocked layout (Params.v4b): a partial-condensing solver
     // keeps them instance-major and never runs these kernels -- refuse instead of reading and writing in the wrong layout
     if (s->P.cond_N2 || !s->P.v4b) return CFNMPC_EINVAL;
+    if (mode == 2 && s->P.mpar) return CFNMPC_EINVAL;   // (k_linfactor integrates with the folded model constants)
     DeviceGuard dg(s);
     hipStream_t st = (hipStream_t)stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/cfnmpc.h"
+#include "cfnmpc_model.hpp"
 #include "cfnmpc_sqp.h"
 
 namespace {
@@ -261,6 +262,24 @@ int cfnmpc_fleet_set_erk_steps(cfnmpc_fleet* f, int num_steps) {
 int cfnmpc_fleet_set_cost_scaling(cfnmpc_fleet* f, double stage_scale, double terminal_scale) {
     if (!f) return CFNMPC_EINVAL;
     for (Bucket& b : f->bk) RC_TRY(cfnmpc_set_cost_scaling(b.s, stage_scale, terminal_scale));
+    return CFNMPC_OK;
+}
+
+// per-instance model parameters: rows in the fleet's vehicle order -> each bucket's order, each bucket's copy on its own
+// stream (complete when the call returns).  The rows are validated as a whole first, so a bad row leaves every bucket
+// unchanged.  A bucket refuses parameters only for options every bucket shares (start_solve 2 / 3), so the FIRST bucket
+// refuses and nothing has changed either (cfnmpc_fleet_set_erk_steps relies on the same).
+int cfnmpc_fleet_set_model_params(cfnmpc_fleet* f, const double* p) {
+    if (!f) return CFNMPC_EINVAL;
+    if (p && !cfn::model_params_ok(p, (size_t)f->B * CFNMPC_NP)) return CFNMPC_EINVAL;
+    FleetDevice fd(f);
+    std::vector<double> h;
+    for (Bucket& b : f->bk) {
+        if (!p) { RC_TRY(cfnmpc_set_model_params(b.s, nullptr, CFNMPC_ON_HOST, b.st)); continue; }
+        h.resize((size_t)b.count * CFNMPC_NP);
+        for (int r = 0; r < b.count; r++) std::copy_n(p + (size_t)b.idx[r] * CFNMPC_NP, CFNMPC_NP, h.data() + (size_t)r * CFNMPC_NP);
+        RC_TRY(cfnmpc_set_model_params(b.s, h.data(), CFNMPC_ON_HOST, b.st));
+    }
     return CFNMPC_OK;
 }
 

@@ -50,9 +50,9 @@ namespace cfn {
 // One sensitivity column through the four RK stages (HQ / HW: its q- / w-part can be non-zero;
 // IS_U: input column, driven by df/du).  Column-type sparsity is exploited at compile time
 // because all 64 lanes (= 64 instances) integrate the SAME column.
-template <bool HQ, bool HW, bool IS_U>
+template <bool HQ, bool HW, bool IS_U, class K = NomK>
 __device__ __forceinline__ void sens_column(const JacPoint (&J)[4], const double* __restrict__ u, int c, double h,
-                                            double* __restrict__ col) {
+                                            double* __restrict__ col, const K& mk = K()) {
     double s0[13], s[13], k1[13], k2[13], k3[13], k4[13], ju[4] = {0, 0, 0, 0};
     SFOR(i, 0, 13, { s0[i] = (!IS_U && i == c) ? 1.0 : 0.0; });
     if (IS_U) {
@@ -60,18 +60,18 @@ __device__ __forceinline__ void sens_column(const JacPoint (&J)[4], const double
         const double sa = (c < 2) ? 1.0 : -1.0;             // w1 w2 | -w3 -w4
         const double sb = (c == 0 || c == 3) ? 1.0 : -1.0;  // w1 -w2 -w3 w4
         const double sc_ = (c == 0 || c == 2) ? 1.0 : -1.0; // w1 -w2 w3 -w4
-        ju[0] = KT * uc; ju[1] = KA * sa * uc; ju[2] = KB * sb * uc; ju[3] = KC * sc_ * uc;
+        ju[0] = mk.kt() * uc; ju[1] = mk.ka() * sa * uc; ju[2] = mk.kb() * sb * uc; ju[3] = mk.kc() * sc_ * uc;
     }
-    jvp<HQ, HW>(J[0], s0, k1);
+    jvp<HQ, HW>(J[0], s0, k1, mk);
     SFOR(i, 0, 4, { k1[9 + i] += ju[i]; });
     SFOR(i, 0, 13, { s[i] = s0[i] + 0.5 * h * k1[i]; });
-    jvp<HQ, HW>(J[1], s, k2);
+    jvp<HQ, HW>(J[1], s, k2, mk);
     SFOR(i, 0, 4, { k2[9 + i] += ju[i]; });
     SFOR(i, 0, 13, { s[i] = s0[i] + 0.5 * h * k2[i]; });
-    jvp<HQ, HW>(J[2], s, k3);
+    jvp<HQ, HW>(J[2], s, k3, mk);
     SFOR(i, 0, 4, { k3[9 + i] += ju[i]; });
     SFOR(i, 0, 13, { s[i] = s0[i] + h * k3[i]; });
-    jvp<HQ, HW>(J[3], s, k4);
+    jvp<HQ, HW>(J[3], s, k4, mk);
     SFOR(i, 0, 4, { k4[9 + i] += ju[i]; });
     SFOR(i, 0, 13, { col[i] = s0[i] + (h / 6.0) * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]); });
 }
@@ -79,9 +79,9 @@ __device__ __forceinline__ void sens_column(const JacPoint (&J)[4], const double
 // ERK with M sub-steps per interval (cfnmpc_set_erk_steps, k_linearise_erk): one column through ONE RK4 sub-step of h = dt / M from
 // a general start: col <- A_j col (+ B_j e_c for an input column), A_j / B_j the sensitivities of sub-step j at the points J.  The
 // column-type sparsity (HQ / HW) holds at every sub-step: d Phi / d x has the block pattern of cfnmpc_model.hpp for any explicit RK.
-template <bool HQ, bool HW, bool IS_U>
+template <bool HQ, bool HW, bool IS_U, class K = NomK>
 __device__ __forceinline__ void sens_step(const JacPoint (&J)[4], const double* __restrict__ u, int c, double h,
-                                          double (&col)[13]) {
+                                          double (&col)[13], const K& mk = K()) {
     // (slopes summed as they come, k1 + 2 k2 + 2 k3 + k4 in acc: two 13-vectors live instead of five beside the four points)
     double s[13], k[13], acc[13], ju[4] = {0, 0, 0, 0};
     if (IS_U) {
@@ -89,18 +89,18 @@ __device__ __forceinline__ void sens_step(const JacPoint (&J)[4], const double* 
         const double sa = (c < 2) ? 1.0 : -1.0;
         const double sb = (c == 0 || c == 3) ? 1.0 : -1.0;
         const double sc_ = (c == 0 || c == 2) ? 1.0 : -1.0;
-        ju[0] = KT * uc; ju[1] = KA * sa * uc; ju[2] = KB * sb * uc; ju[3] = KC * sc_ * uc;
+        ju[0] = mk.kt() * uc; ju[1] = mk.ka() * sa * uc; ju[2] = mk.kb() * sb * uc; ju[3] = mk.kc() * sc_ * uc;
     }
-    jvp<HQ, HW>(J[0], col, k);
+    jvp<HQ, HW>(J[0], col, k, mk);
     SFOR(i, 0, 4, { k[9 + i] += ju[i]; });
     SFOR(i, 0, 13, { acc[i] = k[i]; s[i] = col[i] + 0.5 * h * k[i]; });
-    jvp<HQ, HW>(J[1], s, k);
+    jvp<HQ, HW>(J[1], s, k, mk);
     SFOR(i, 0, 4, { k[9 + i] += ju[i]; });
     SFOR(i, 0, 13, { acc[i] += 2 * k[i]; s[i] = col[i] + 0.5 * h * k[i]; });
-    jvp<HQ, HW>(J[2], s, k);
+    jvp<HQ, HW>(J[2], s, k, mk);
     SFOR(i, 0, 4, { k[9 + i] += ju[i]; });
     SFOR(i, 0, 13, { acc[i] += 2 * k[i]; s[i] = col[i] + h * k[i]; });
-    jvp<HQ, HW>(J[3], s, k);
+    jvp<HQ, HW>(J[3], s, k, mk);
     SFOR(i, 0, 4, { k[9 + i] += ju[i]; });
     SFOR(i, 0, 13, { col[i] = col[i] + (h / 6.0) * (acc[i] + k[i]); });
 }
@@ -109,9 +109,9 @@ __device__ __forceinline__ void sens_step(const JacPoint (&J)[4], const double* 
 // from the carried sub-step state xs (4 f_expl + 4 jac_point), then every column of the group advances by sens_step.  Between
 // sub-steps the columns are parked in the group's store tile (rows < NS in internal order at tile[4 NS j + r], the layout
 // CFN_COL writes: lane-private, so no barrier inside), from where CFN_STORE2 takes them once.  Returns Phi_M(x, u) in xe.
-template <bool HQ, bool HW, bool IS_U, int NC, int NS>
+template <bool HQ, bool HW, bool IS_U, int NC, int NS, class K = NomK>
 __device__ __forceinline__ void erk_group(const double (&x)[13], const double (&u)[4], int c0, int M, double h,
-                                          double* __restrict__ tile, double (&xe)[13]) {
+                                          double* __restrict__ tile, double (&xe)[13], const K& mk = K()) {
 #pragma unroll 1
     for (int j = 0; j < NC; j++) SFOR(r, 0, NS, { tile[4 * NS * j + r] = (!IS_U && ext_of(r) == c0 + j) ? 1.0 : 0.0; });
     SFOR(e, 0, 13, { xe[e] = x[e]; });
@@ -119,16 +119,16 @@ __device__ __forceinline__ void erk_group(const double (&x)[13], const double (&
     for (int m = 0; m < M; m++) {
         double xt[13], ks[13], kk[13];
         JacPoint J[4];
-        f_expl(xe, u, kk);
+        f_expl(xe, u, kk, mk);
         jac_point(xe, J[0]);
         SFOR(e, 0, 13, { ks[e] = kk[e]; xt[e] = xe[e] + 0.5 * h * kk[e]; });
-        f_expl(xt, u, kk);
+        f_expl(xt, u, kk, mk);
         jac_point(xt, J[1]);
         SFOR(e, 0, 13, { ks[e] += 2 * kk[e]; xt[e] = xe[e] + 0.5 * h * kk[e]; });
-        f_expl(xt, u, kk);
+        f_expl(xt, u, kk, mk);
         jac_point(xt, J[2]);
         SFOR(e, 0, 13, { ks[e] += 2 * kk[e]; xt[e] = xe[e] + h * kk[e]; });
-        f_expl(xt, u, kk);
+        f_expl(xt, u, kk, mk);
         jac_point(xt, J[3]);
         SFOR(e, 0, 13, { xe[e] = xe[e] + (h / 6.0) * (ks[e] + kk[e]); });
 #pragma unroll 1
@@ -136,11 +136,40 @@ __device__ __forceinline__ void erk_group(const double (&x)[13], const double (&
             double col[13];
             SFOR(e, 0, 13, { col[e] = 0.0; });
             SFOR(r, 0, NS, { col[ext_of(r)] = tile[4 * NS * j + r]; });
-            sens_step<HQ, HW, IS_U>(J, u, c0 + j, h, col);
+            sens_step<HQ, HW, IS_U>(J, u, c0 + j, h, col, mk);
             SFOR(r, 0, NS, { tile[4 * NS * j + r] = col[ext_of(r)]; });
         }
     }
 }
+
+// Model constants of instance `inst` (P.mpar, [NK][(NW + 1) * 4]: one coalesced load per constant for a lane-per-instance wave);
+// PAR = false: the folded constants, nothing read.
+template <bool PAR> using ModelK = typename std::conditional<PAR, ParK, NomK>::type;
+template <bool PAR>
+__device__ __forceinline__ ModelK<PAR> model_k(const Params& P, int inst) {
+    ModelK<PAR> mk;
+    if constexpr (PAR) {
+        const gdouble* mp = gm(P.mpar) + inst;
+        const size_t S = ((size_t)P.NW + 1) * 4;
+        SFOR(j, 0, 8, { mk.c[j] = mp[j * S]; });
+    }
+    return mk;
+}
+
+// The same constants read where they are used (k_linearise_par): a load per use from the L1 / L2 instead of 16 registers
+// live beside the four Jacobian points and the column, where the folded kernel already needs the whole register file.
+struct ParKG {
+    const gdouble* p;   // this lane's instance in row 0 of P.mpar
+    unsigned S;         // row stride
+    __device__ double g0() const { return p[0]; }
+    __device__ double kt() const { return p[S]; }
+    __device__ double ka() const { return p[2 * S]; }
+    __device__ double kb() const { return p[3 * S]; }
+    __device__ double kc() const { return p[4 * S]; }
+    __device__ double kwx() const { return p[5 * S]; }
+    __device__ double kwy() const { return p[6 * S]; }
+    __device__ double kwz() const { return p[7 * S]; }
+};
 
 // Lane-per-instance (work-efficient: nothing is computed twice); one workgroup = one wavefront
 // = 64 instances, blockIdx.y = a chunk of the (mutually independent) shooting intervals.  All
@@ -173,10 +202,12 @@ static_assert(div_ok(52, 64 * 13), "k_forward: e / 52 by multiply-shift");
 //                   (A, B, b), so the instances whose QP needs them again get them here (k_linearise_clist);
 //                   which = 0: P.ilist (count P.nipm[0]), 1: P.ilist2 (P.nipm[NI_LISTED], the interior-point fall-back rows).
 //   ERK (k_linearise_erk): M = P.erk_steps RK4 sub-steps of dt / M per interval (erk_group); whole fleet (GATHER = false) only.
-template <bool GATHER, bool CSTORE = false, bool ERK = false>
+//   PAR (the _par kernels): the model constants of each lane's instance (P.mpar, model_k) instead of the folded ones; whole fleet only.
+template <bool GATHER, bool CSTORE = false, bool ERK = false, bool PAR = false>
 __device__ __forceinline__ void linearise_body(const Params& P, double* sx, double (*sc)[64 * 13], int* sinst,
                                                const int which = 0) {
     static_assert(!ERK || !GATHER, "ERK sub-steps: whole-fleet kernel only");
+    static_assert(!PAR || !GATHER, "per-instance parameters: whole-fleet kernel only");
     constexpr bool PAIRS = !GATHER;   // 16-byte stores of whole column groups (below)
     const int tid = threadIdx.x;
     const double h = P.dt;
@@ -190,6 +221,10 @@ __device__ __forceinline__ void linearise_body(const Params& P, double* sx, doub
     }
     __syncthreads();
     const int inst = sinst[tid];
+    // PAR: the instance's constants read at their uses (ParKG)
+    using LinK = typename std::conditional<PAR, ParKG, NomK>::type;
+    LinK mk{};
+    if constexpr (PAR) mk = ParKG{gm(P.mpar) + inst, (unsigned)(P.NW + 1) * 4u};
 #ifdef CFN_DEV   // (P.lin_k1 > 0: only the shooting intervals [lin_k0, lin_k1) -- the stage-chunked hand-over experiment)
     const int ka = P.lin_k1 > 0 ? P.lin_k0 : 0, kb = P.lin_k1 > 0 ? P.lin_k1 : N;
 #else
@@ -276,16 +311,16 @@ __device__ __forceinline__ void linearise_body(const Params& P, double* sx, doub
         // nominal RK4 (classic tableau, one step per interval)
         double xt[13], k1v[13], k2v[13], k3v[13], k4v[13];
         JacPoint J[4];
-        f_expl(x, u, k1v);
+        f_expl(x, u, k1v, mk);
         jac_point(x, J[0]);
         SFOR(e, 0, 13, { xt[e] = x[e] + 0.5 * h * k1v[e]; });
-        f_expl(xt, u, k2v);
+        f_expl(xt, u, k2v, mk);
         jac_point(xt, J[1]);
         SFOR(e, 0, 13, { xt[e] = x[e] + 0.5 * h * k2v[e]; });
-        f_expl(xt, u, k3v);
+        f_expl(xt, u, k3v, mk);
         jac_point(xt, J[2]);
         SFOR(e, 0, 13, { xt[e] = x[e] + h * k3v[e]; });
-        f_expl(xt, u, k4v);
+        f_expl(xt, u, k4v, mk);
         jac_point(xt, J[3]);
         SFOR(e, 0, 13, { xn[e] = sxb[tid * 13 + int_of(e)]; });
         // b = Phi - x_{k+1} through the tile (internal order)
@@ -354,7 +389,7 @@ __device__ __forceinline__ void linearise_body(const Params& P, double* sx, doub
         // (runtime loops on purpose: one column at a time keeps the register footprint small)
 #pragma unroll 1
         for (int j = 0; j < 3; j++) {  // velocity columns: rows p, v
-            CFN_COL((sens_column<false, false, false>(J, u, 7 + j, h, col)), j, 72, 6);
+            CFN_COL((sens_column<false, false, false>(J, u, 7 + j, h, col, mk)), j, 72, 6);
         }
         __syncthreads();
         if (PAIRS) { CFN_STORE2(P.AR, SZ_A, 72, 0); }
@@ -362,7 +397,7 @@ __device__ __forceinline__ void linearise_body(const Params& P, double* sx, doub
         __syncthreads();
 #pragma unroll 1
         for (int j = 0; j < 4; j++) {  // quaternion columns: rows p, v, q
-            CFN_COL((sens_column<true, false, false>(J, u, 3 + j, h, col)), j, 160, 10);
+            CFN_COL((sens_column<true, false, false>(J, u, 3 + j, h, col, mk)), j, 160, 10);
         }
         __syncthreads();
         if (PAIRS) { CFN_STORE2(P.AR, SZ_A, 160, 4 * ar_pre(3)); }
@@ -373,7 +408,7 @@ __device__ __forceinline__ void linearise_body(const Params& P, double* sx, doub
         __syncthreads();
 #pragma unroll 1
         for (int j = 0; j < 3; j++) {  // rate columns: all rows
-            CFN_COL((sens_column<true, true, false>(J, u, 10 + j, h, col)), j, 156, 13);
+            CFN_COL((sens_column<true, true, false>(J, u, 10 + j, h, col, mk)), j, 156, 13);
         }
         __syncthreads();
         if (PAIRS) { CFN_STORE2(P.AR, SZ_A, 156, 4 * ar_pre(7)); }
@@ -381,7 +416,7 @@ __device__ __forceinline__ void linearise_body(const Params& P, double* sx, doub
         __syncthreads();
 #pragma unroll 1
         for (int a = 0; a < 4; a++) {  // input columns: all rows
-            CFN_COL((sens_column<true, true, true>(J, u, a, h, col)), a, 208, 13);
+            CFN_COL((sens_column<true, true, true>(J, u, a, h, col, mk)), a, 208, 13);
         }
         __syncthreads();
         if (PAIRS) { CFN_STORE2(P.BR, SZ_B, 208, 0); }
@@ -395,21 +430,21 @@ __device__ __forceinline__ void linearise_body(const Params& P, double* sx, doub
         const int M = P.erk_steps;
         const double hs = h / M;
         double xe[13];
-        erk_group<false, false, false, 3, 6>(x, u, 7, M, hs, scf + CFN_TB(72, 6), xe);        // velocity columns: rows p, v
+        erk_group<false, false, false, 3, 6>(x, u, 7, M, hs, scf + CFN_TB(72, 6), xe, mk);        // velocity columns: rows p, v
         __syncthreads();
         CFN_STORE2(P.AR, SZ_A, 72, 0);
         __syncthreads();
-        erk_group<true, false, false, 4, 10>(x, u, 3, M, hs, scf + CFN_TB(160, 10), xe);      // quaternion columns: rows p, v, q
+        erk_group<true, false, false, 4, 10>(x, u, 3, M, hs, scf + CFN_TB(160, 10), xe, mk);      // quaternion columns: rows p, v, q
         __syncthreads();
         CFN_STORE2(P.AR, SZ_A, 160, 4 * ar_pre(3));
         land_x(sxa, xr);   // x_{k+2} -> the tile x_k was read from; tiles swap roles (sxa = x_{k+1} from here)
         { double* t_ = sxa; sxa = sxb; sxb = t_; }
         __syncthreads();
-        erk_group<true, true, false, 3, 13>(x, u, 10, M, hs, scf + CFN_TB(156, 13), xe);      // rate columns: all rows
+        erk_group<true, true, false, 3, 13>(x, u, 10, M, hs, scf + CFN_TB(156, 13), xe, mk);      // rate columns: all rows
         __syncthreads();
         CFN_STORE2(P.AR, SZ_A, 156, 4 * ar_pre(7));
         __syncthreads();
-        erk_group<true, true, true, 4, 13>(x, u, 0, M, hs, scf + CFN_TB(208, 13), xe);        // input columns: all rows
+        erk_group<true, true, true, 4, 13>(x, u, 0, M, hs, scf + CFN_TB(208, 13), xe, mk);        // input columns: all rows
         __syncthreads();
         CFN_STORE2(P.BR, SZ_B, 208, 0);
         __syncthreads();
@@ -443,6 +478,19 @@ KALIGN __global__ __launch_bounds__(64) void k_linearise_erk(Params P) {   // th
     __shared__ __attribute__((aligned(16))) double sc[4][64 * 13];
     __shared__ int sinst[64];
     linearise_body<false, false, true>(P, sx, sc, sinst);
+}
+// the same two with per-instance model constants (cfnmpc_set_model_params)
+KALIGN __global__ __launch_bounds__(64) void k_linearise_par(Params P) {
+    __shared__ double sx[2 * 64 * 13];
+    __shared__ __attribute__((aligned(16))) double sc[4][64 * 13];
+    __shared__ int sinst[64];
+    linearise_body<false, false, false, true>(P, sx, sc, sinst);
+}
+KALIGN __global__ __launch_bounds__(64) void k_linearise_erk_par(Params P) {
+    __shared__ double sx[2 * 64 * 13];
+    __shared__ __attribute__((aligned(16))) double sc[4][64 * 13];
+    __shared__ int sinst[64];
+    linearise_body<false, false, true, true>(P, sx, sc, sinst);
 }
 #ifdef CFN_DEV   // (overlapped preparation: development builds only)
 __global__ __launch_bounds__(64) void k_linearise_list(Params P) {
@@ -1010,7 +1058,8 @@ __device__ __forceinline__ int head_want(const Params& P, int last_tight) {
 // ERK (the _erk kernels, P.erk_steps = M > 1): the candidate is the directional derivative of M RK4 sub-steps of dt / M, each the
 // FUSED_PT form (lf_point) from the carried sub-step state and direction -- what the stored-block sweep computes from
 // k_linearise_erk's A, B, b up to rounding.
-template <bool COND, bool FUSED_PT = false, int SPLIT = 0, bool ERK = false>
+// PAR (the _par kernels): the model constants of each lane's instance (P.mpar, model_k).
+template <bool COND, bool FUSED_PT = false, int SPLIT = 0, bool ERK = false, bool PAR = false>
 __device__ __forceinline__ void forward_body(const Params& P, double* xs, double* cs, int* sflag) {
     // 13-vectors travel through LDS tiles [instance][13] so that every global access of the wave
     // is a contiguous run (as in k_linearise); K, d, u, v are 32-byte runs per lane already.
@@ -1023,6 +1072,13 @@ __device__ __forceinline__ void forward_body(const Params& P, double* xs, double
     const int q = inst & 3;
     const int w0 = blockIdx.x * 16;
     const double h = P.dt;
+    // PAR: the instance's constants, loaded once (the one-step condensed sweep: read at their uses instead, ParKG -- carried,
+    // they spill more in that form)
+    constexpr bool LAZY = PAR && COND && !ERK;
+    using FwdK = typename std::conditional<PAR, typename std::conditional<LAZY, ParKG, ParK>::type, NomK>::type;
+    FwdK mk{};
+    if constexpr (PAR && !LAZY) mk = model_k<PAR>(P, inst);
+    if constexpr (LAZY) mk = FwdK{gm(P.mpar) + inst, (unsigned)(P.NW + 1) * 4u};
     const double margin = P.ah_margin * (P.u_max - P.u_min);
     const gdouble* kp = gm(P.KR) + w * N * SZ_K + q * 4;
     // this lane's 4-vectors: element a of stage k at i4b + k * i4s + a (Params.v4b: wave-blocked or instance-major)
@@ -1118,10 +1174,10 @@ __device__ __forceinline__ void forward_body(const Params& P, double* xs, double
         double jud[4];
         {
             const double p0 = uc[0] * du[0], p1 = uc[1] * du[1], p2 = uc[2] * du[2], p3 = uc[3] * du[3];
-            jud[0] = 2.0 * KT * (p0 + p1 + p2 + p3);
-            jud[1] = 2.0 * KA * (p0 + p1 - p2 - p3);
-            jud[2] = 2.0 * KB * (p0 - p1 - p2 + p3);
-            jud[3] = 2.0 * KC * (p0 - p1 + p2 - p3);
+            jud[0] = 2.0 * mk.kt() * (p0 + p1 + p2 + p3);
+            jud[1] = 2.0 * mk.ka() * (p0 + p1 - p2 - p3);
+            jud[2] = 2.0 * mk.kb() * (p0 - p1 - p2 + p3);
+            jud[3] = 2.0 * mk.kc() * (p0 - p1 + p2 - p3);
         }
         double dxp[13];   // dx_{k+1} + x_{k+1}
         if constexpr (ERK) {
@@ -1130,25 +1186,25 @@ __device__ __forceinline__ void forward_body(const Params& P, double* xs, double
             double rot[4];
             {
                 const double s1 = uc[0] * uc[0], s2 = uc[1] * uc[1], s3 = uc[2] * uc[2], s4 = uc[3] * uc[3];
-                rot[0] = KT * (s1 + s2 + s3 + s4);
-                rot[1] = KA * (s1 + s2 - s3 - s4);
-                rot[2] = KB * (s1 - s2 - s3 + s4);
-                rot[3] = KC * (s1 - s2 + s3 - s4);
+                rot[0] = mk.kt() * (s1 + s2 + s3 + s4);
+                rot[1] = mk.ka() * (s1 + s2 - s3 - s4);
+                rot[2] = mk.kb() * (s1 - s2 - s3 + s4);
+                rot[3] = mk.kc() * (s1 - s2 + s3 - s4);
             }
 #pragma unroll 1
             for (int m = 0; m < M; m++) {   // (x, s) <- (Phi_h(x), dPhi_h (s, du)) in the external order
                 double xq[10], sq[10];
                 SFOR(e, 0, 10, { xq[e] = x[e + 3]; sq[e] = s[e + 3]; });
-                lf_point(xq, sq, rot, jud, kk, dk);
+                lf_point(xq, sq, rot, jud, kk, dk, mk);
                 SFOR(e, 0, 13, { acc[e] = dk[e]; ks[e] = kk[e]; });
                 SFOR(e, 0, 10, { xq[e] = x[e + 3] + 0.5 * hs * kk[e + 3]; sq[e] = s[e + 3] + 0.5 * hs * dk[e + 3]; });
-                lf_point(xq, sq, rot, jud, kk, dk);
+                lf_point(xq, sq, rot, jud, kk, dk, mk);
                 SFOR(e, 0, 13, { acc[e] += 2.0 * dk[e]; ks[e] += 2.0 * kk[e]; });
                 SFOR(e, 0, 10, { xq[e] = x[e + 3] + 0.5 * hs * kk[e + 3]; sq[e] = s[e + 3] + 0.5 * hs * dk[e + 3]; });
-                lf_point(xq, sq, rot, jud, kk, dk);
+                lf_point(xq, sq, rot, jud, kk, dk, mk);
                 SFOR(e, 0, 13, { acc[e] += 2.0 * dk[e]; ks[e] += 2.0 * kk[e]; });
                 SFOR(e, 0, 10, { xq[e] = x[e + 3] + hs * kk[e + 3]; sq[e] = s[e + 3] + hs * dk[e + 3]; });
-                lf_point(xq, sq, rot, jud, kk, dk);
+                lf_point(xq, sq, rot, jud, kk, dk, mk);
                 SFOR(e, 0, 13, { x[e] += (hs / 6.0) * (ks[e] + kk[e]); s[e] += (hs / 6.0) * (acc[e] + dk[e]); });
             }
             SFOR(i, 0, 13, { constexpr int e = ext_of(i); dxp[i] = s[e] + x[e]; });
@@ -1157,48 +1213,48 @@ __device__ __forceinline__ void forward_body(const Params& P, double* xs, double
             double rot[4];
             {
                 const double s1 = uc[0] * uc[0], s2 = uc[1] * uc[1], s3 = uc[2] * uc[2], s4 = uc[3] * uc[3];
-                rot[0] = KT * (s1 + s2 + s3 + s4);
-                rot[1] = KA * (s1 + s2 - s3 - s4);
-                rot[2] = KB * (s1 - s2 - s3 + s4);
-                rot[3] = KC * (s1 - s2 + s3 - s4);
+                rot[0] = mk.kt() * (s1 + s2 + s3 + s4);
+                rot[1] = mk.ka() * (s1 + s2 - s3 - s4);
+                rot[2] = mk.kb() * (s1 - s2 - s3 + s4);
+                rot[3] = mk.kc() * (s1 - s2 + s3 - s4);
             }
             double xq[10], sq[10];
             SFOR(e, 0, 10, { xq[e] = x[e + 3]; sq[e] = s[e + 3]; });
-            lf_point(xq, sq, rot, jud, kk, dk);
+            lf_point(xq, sq, rot, jud, kk, dk, mk);
             SFOR(e, 0, 13, { acc[e] = dk[e]; ks[e] = kk[e]; });
             SFOR(e, 0, 10, { xq[e] = x[e + 3] + 0.5 * h * kk[e + 3]; sq[e] = s[e + 3] + 0.5 * h * dk[e + 3]; });
-            lf_point(xq, sq, rot, jud, kk, dk);
+            lf_point(xq, sq, rot, jud, kk, dk, mk);
             SFOR(e, 0, 13, { acc[e] += 2.0 * dk[e]; ks[e] += 2.0 * kk[e]; });
             SFOR(e, 0, 10, { xq[e] = x[e + 3] + 0.5 * h * kk[e + 3]; sq[e] = s[e + 3] + 0.5 * h * dk[e + 3]; });
-            lf_point(xq, sq, rot, jud, kk, dk);
+            lf_point(xq, sq, rot, jud, kk, dk, mk);
             SFOR(e, 0, 13, { acc[e] += 2.0 * dk[e]; ks[e] += 2.0 * kk[e]; });
             SFOR(e, 0, 10, { xq[e] = x[e + 3] + h * kk[e + 3]; sq[e] = s[e + 3] + h * dk[e + 3]; });
-            lf_point(xq, sq, rot, jud, kk, dk);
+            lf_point(xq, sq, rot, jud, kk, dk, mk);
         } else {
         JacPoint J;
         // stage 1
-        f_expl(x, uc, kk);
+        f_expl(x, uc, kk, mk);
         jac_point(x, J);
-        jvp<true, true>(J, s, dk);
+        jvp<true, true>(J, s, dk, mk);
         SFOR(i, 0, 4, { dk[9 + i] += jud[i]; });
         SFOR(e, 0, 13, { acc[e] = dk[e]; ks[e] = kk[e]; xt[e] = x[e] + 0.5 * h * kk[e]; st[e] = s[e] + 0.5 * h * dk[e]; });
         // stage 2
-        f_expl(xt, uc, kk);
+        f_expl(xt, uc, kk, mk);
         jac_point(xt, J);
-        jvp<true, true>(J, st, dk);
+        jvp<true, true>(J, st, dk, mk);
         SFOR(i, 0, 4, { dk[9 + i] += jud[i]; });
         SFOR(e, 0, 13, { acc[e] += 2.0 * dk[e]; ks[e] = ks[e] + 2 * kk[e]; xt[e] = x[e] + 0.5 * h * kk[e]; st[e] = s[e] + 0.5 * h * dk[e]; });
         // stage 3
-        f_expl(xt, uc, kk);
+        f_expl(xt, uc, kk, mk);
         jac_point(xt, J);
-        jvp<true, true>(J, st, dk);
+        jvp<true, true>(J, st, dk, mk);
         SFOR(i, 0, 4, { dk[9 + i] += jud[i]; });
         SFOR(e, 0, 13, { acc[e] += 2.0 * dk[e]; ks[e] = ks[e] + 2 * kk[e]; xt[e] = x[e] + h * kk[e]; st[e] = s[e] + h * dk[e]; });
         // stage 4 (the nominal slope too: b_k = Phi(x_k, u_k) - x_{k+1} is formed here, as k_linearise
         // forms it, instead of being read back)
-        f_expl(xt, uc, kk);
+        f_expl(xt, uc, kk, mk);
         jac_point(xt, J);
-        jvp<true, true>(J, st, dk);
+        jvp<true, true>(J, st, dk, mk);
         SFOR(i, 0, 4, { dk[9 + i] += jud[i]; });
         }
         SFOR(i, 0, 13, {
@@ -1370,6 +1426,22 @@ __global__ __launch_bounds__(64) void k_cforward_erk(Params P) {
     __shared__ int sflag[64];
     forward_body<true, false, 0, true>(P, xs, cs, sflag);
 }
+// the eight sweeps with per-instance model constants (cfnmpc_set_model_params)
+#define CFN_FWD_PAR(name, ...)                                                                          \
+    KALIGN __global__ __launch_bounds__(64) void name(Params P) {                                       \
+        __shared__ double xs[64 * 13], cs[64 * 13];                                                     \
+        __shared__ int sflag[64];                                                                       \
+        forward_body<__VA_ARGS__>(P, xs, cs, sflag);                                                    \
+    }
+CFN_FWD_PAR(k_forward_par, false, true, 0, false, true)
+CFN_FWD_PAR(k_forward_p1_par, false, true, 1, false, true)
+CFN_FWD_PAR(k_forward_p2_par, false, true, 2, false, true)
+CFN_FWD_PAR(k_cforward_par, true, false, 0, false, true)
+CFN_FWD_PAR(k_forward_erk_par, false, true, 0, true, true)
+CFN_FWD_PAR(k_forward_p1_erk_par, false, true, 1, true, true)
+CFN_FWD_PAR(k_forward_p2_erk_par, false, true, 2, true, true)
+CFN_FWD_PAR(k_cforward_erk_par, true, false, 0, true, true)
+#undef CFN_FWD_PAR
 
 // ---------------------------------------------------------------------------------------------
 // Start solve, forward sweep on the STORED stage blocks -- row groups, four instances per wave.
@@ -2994,10 +3066,19 @@ void debug_prof_read(unsigned long long* out, int reset) {
 // =============================================================================================
 // predictor / plant step, layout glue
 // =============================================================================================
-__global__ void k_sim(int B, const double* __restrict__ x, const double* __restrict__ u, double T, int steps,
-                      double* __restrict__ xn) {
+// p (PAR only): per-instance parameters [B][NPAR] (cfnmpc_sim_params), the constants derived per lane as on the host
+template <bool PAR>
+__device__ __forceinline__ void sim_body(int B, const double* __restrict__ x, const double* __restrict__ u,
+                                         const double* __restrict__ p, double T, int steps, double* __restrict__ xn) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B) return;
+    ModelK<PAR> mk;
+    if constexpr (PAR) {
+        double pr[NPAR], kr[NK];
+        SFOR(e, 0, NPAR, { pr[e] = p[(size_t)i * NPAR + e]; });
+        derive_k(pr, kr);
+        SFOR(e, 0, 8, { mk.c[e] = kr[e]; });
+    }
     double xc[13], uc[4], k1[13], k2[13], k3[13], k4[13], xt[13];
 #pragma unroll
     for (int e = 0; e < 13; e++) xc[e] = x[(size_t)i * 13 + e];
@@ -3005,21 +3086,29 @@ __global__ void k_sim(int B, const double* __restrict__ x, const double* __restr
     for (int e = 0; e < 4; e++) uc[e] = u[(size_t)i * 4 + e];
     const double h = T / steps;
     for (int s = 0; s < steps; s++) {
-        f_expl(xc, uc, k1);
+        f_expl(xc, uc, k1, mk);
 #pragma unroll
         for (int e = 0; e < 13; e++) xt[e] = xc[e] + 0.5 * h * k1[e];
-        f_expl(xt, uc, k2);
+        f_expl(xt, uc, k2, mk);
 #pragma unroll
         for (int e = 0; e < 13; e++) xt[e] = xc[e] + 0.5 * h * k2[e];
-        f_expl(xt, uc, k3);
+        f_expl(xt, uc, k3, mk);
 #pragma unroll
         for (int e = 0; e < 13; e++) xt[e] = xc[e] + h * k3[e];
-        f_expl(xt, uc, k4);
+        f_expl(xt, uc, k4, mk);
 #pragma unroll
         for (int e = 0; e < 13; e++) xc[e] += (h / 6.0) * (k1[e] + 2 * k2[e] + 2 * k3[e] + k4[e]);
     }
 #pragma unroll
     for (int e = 0; e < 13; e++) xn[(size_t)i * 13 + e] = xc[e];
+}
+__global__ void k_sim(int B, const double* __restrict__ x, const double* __restrict__ u, double T, int steps,
+                      double* __restrict__ xn) {
+    sim_body<false>(B, x, u, nullptr, T, steps, xn);
+}
+__global__ __launch_bounds__(256) void k_sim_par(int B, const double* __restrict__ x, const double* __restrict__ u, const double* __restrict__ p,
+                          double T, int steps, double* __restrict__ xn) {
+    sim_body<true>(B, x, u, p, T, steps, xn);
 }
 
 // State assembly + delay compensation of the reference estimator, batched, one vehicle per lane
@@ -3217,6 +3306,19 @@ __global__ void k_init_iterate(Params P, int mode) {
     for (int k = 0; k < P.N; k++)
         for (int e = 0; e < 4; e++) P.uit[blk_index(i, k, e, P.N, 4, P.v4b)] = (mode == 1) ? hov : 0.0;
 }
+// the same with each instance's own hover speed (row NK - 1 of P.mpar, cfnmpc_set_model_params)
+__global__ void k_init_iterate_par(Params P, int mode) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P.B) return;
+    const double hov = P.mpar[(size_t)(NK - 1) * ((size_t)P.NW + 1) * 4 + i];
+    for (int k = 0; k <= P.N; k++)
+        for (int e = 0; e < 13; e++) {
+            const double x0e = P.x0[blk_index(i, 0, int_of(e), 1, 13)];
+            P.xit[blk_index(i, k, int_of(e), P.N + 1, 13)] = (mode == 1) ? x0e : (e == 3 ? 1.0 : 0.0);
+        }
+    for (int k = 0; k < P.N; k++)
+        for (int e = 0; e < 4; e++) P.uit[blk_index(i, k, e, P.N, 4, P.v4b)] = (mode == 1) ? hov : 0.0;
+}
 
 // cfnmpc_opts.reinit_failed: an instance whose last step ended in status 4 (factorisation not positive definite / not
 // finite: its iterate has left the region where the Gauss-Newton QP is solvable, and re-linearising around the same iterate
@@ -3246,7 +3348,9 @@ __global__ void k_reinit_failed(Params P) {
 // A.cnt[j & 1] (a ballot per wavefront, one atomic); the launch clears A.cnt[(j + 1) & 1], the next iteration's counter (the
 // host has read it before this launch: stream order), so no memset sits between the iterations.
 __device__ __forceinline__ double max_nan(double acc, double v) { return (v > acc || v != v) ? v : acc; }   // NaN sticks
-__global__ __launch_bounds__(64) void k_sqp_check(Params P, SqpArgs A) {
+// PAR: Phi with the model constants of each lane's instance (P.mpar; k_sqp_check_par)
+template <bool PAR>
+__device__ __forceinline__ void sqp_check_body(const Params& P, const SqpArgs& A) {
     __shared__ double xs_o[64 * 13], xs_n[64 * 13];
     __shared__ int sfrz[64];
     const int N = P.N;
@@ -3259,6 +3363,7 @@ __global__ __launch_bounds__(64) void k_sqp_check(Params P, SqpArgs A) {
     const int w0 = blockIdx.x * 16;
     const int M = P.erk_steps;
     const double h = P.dt / M;
+    const ModelK<PAR> mk = model_k<PAR>(P, inst);
     const size_t i4b = P.v4b ? ((size_t)w * N * 4 + q) * 4 : (size_t)inst * N * 4;   // this lane's 4-vectors (Params.v4b)
     const size_t i4s = P.v4b ? 16 : 4;
     auto el13 = [&](const double* f, int e, int stages, int k) -> gdouble* {   // (k_forward's accessor)
@@ -3317,13 +3422,13 @@ __global__ __launch_bounds__(64) void k_sqp_check(Params P, SqpArgs A) {
         SFOR(e, 0, 13, { x[e] = xn[int_of(e)]; });
 #pragma unroll 1
         for (int m = 0; m < M; m++) {
-            f_expl(x, un, kk);
+            f_expl(x, un, kk, mk);
             SFOR(e, 0, 13, { ks[e] = kk[e]; xt[e] = x[e] + 0.5 * h * kk[e]; });
-            f_expl(xt, un, kk);
+            f_expl(xt, un, kk, mk);
             SFOR(e, 0, 13, { ks[e] += 2.0 * kk[e]; xt[e] = x[e] + 0.5 * h * kk[e]; });
-            f_expl(xt, un, kk);
+            f_expl(xt, un, kk, mk);
             SFOR(e, 0, 13, { ks[e] += 2.0 * kk[e]; xt[e] = x[e] + h * kk[e]; });
-            f_expl(xt, un, kk);
+            f_expl(xt, un, kk, mk);
             SFOR(e, 0, 13, { x[e] += (h / 6.0) * (ks[e] + kk[e]); });
         }
         SFOR(i, 0, 13, { constexpr int e = ext_of(i); phi[i] = x[e]; });
@@ -3350,6 +3455,8 @@ __global__ __launch_bounds__(64) void k_sqp_check(Params P, SqpArgs A) {
         if (blockIdx.x == 0) A.cnt[(A.j + 1) & 1] = 0u;
     }
 }
+__global__ __launch_bounds__(64) void k_sqp_check(Params P, SqpArgs A) { sqp_check_body<false>(P, A); }
+__global__ __launch_bounds__(64) void k_sqp_check_par(Params P, SqpArgs A) { sqp_check_body<true>(P, A); }
 
 // ---------------------------------------------------------------------------------------------
 // launchers
@@ -3357,7 +3464,9 @@ __global__ __launch_bounds__(64) void k_sqp_check(Params P, SqpArgs A) {
 static inline int imin_h(int a, int b) { return a < b ? a : b; }
 static inline int imax_h(int a, int b) { return a > b ? a : b; }
 void launch_linearise(const Params& P, int chunks, hipStream_t st) {
-    if (P.erk_steps > 1) hipLaunchKernelGGL(k_linearise_erk, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
+    if (P.mpar && P.erk_steps > 1) hipLaunchKernelGGL(k_linearise_erk_par, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
+    else if (P.mpar) hipLaunchKernelGGL(k_linearise_par, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
+    else if (P.erk_steps > 1) hipLaunchKernelGGL(k_linearise_erk, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
     else hipLaunchKernelGGL(k_linearise, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
 }
 #ifdef CFN_DEV
@@ -3385,6 +3494,10 @@ void launch_qp_start(const Params& P, hipStream_t st, hipEvent_t* ev, bool skip_
 #ifdef CFN_DEV
         if (P.forward_half) { hipLaunchKernelGGL(k_forward_half, dim3((P.B + 63) / 64), dim3(64), 0, st, P); } else
 #endif
+        if (P.mpar) {   // (per-instance model constants: the same choice among the _par twins)
+            if (P.fwd_split) { if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p1_erk_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_forward_p1_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
+            else { if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_erk_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_forward_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
+        } else
         if (P.fwd_split && P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p1_erk, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
         else if (P.fwd_split) hipLaunchKernelGGL(k_forward_p1, dim3((P.B + 63) / 64), dim3(64), 0, st, P);   // part two: launch_qp_ipm
         else if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_erk, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
@@ -3407,11 +3520,13 @@ void launch_factor_only(const Params& P, hipStream_t st) {
     hipLaunchKernelGGL(k_factor, dim3(P.NW), dim3(64), 0, st, P);
 }
 void launch_cforward(const Params& P, hipStream_t st) {
-    if (P.erk_steps > 1) hipLaunchKernelGGL(k_cforward_erk, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
+    if (P.mpar) { if (P.erk_steps > 1) hipLaunchKernelGGL(k_cforward_erk_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_cforward_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
+    else if (P.erk_steps > 1) hipLaunchKernelGGL(k_cforward_erk, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
     else hipLaunchKernelGGL(k_cforward, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
 }
 static void launch_forward_p2(const Params& P, hipStream_t st) {   // second part of the split sweep
-    if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p2_erk, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
+    if (P.mpar) { if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p2_erk_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_forward_p2_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
+    else if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p2_erk, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
     else hipLaunchKernelGGL(k_forward_p2, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
 }
 // ev (optional): event recorded after the active-set kernels (before the interior-point launch for what they left)
@@ -3529,6 +3644,9 @@ void launch_qp(const Params& P, hipStream_t st, hipEvent_t* ev) {
 void launch_sim(int B, const double* x, const double* u, double T, int steps, double* xn, hipStream_t st) {
     hipLaunchKernelGGL(k_sim, dim3((B + 255) / 256), dim3(256), 0, st, B, x, u, T, steps, xn);
 }
+void launch_sim_par(int B, const double* x, const double* u, const double* p, double T, int steps, double* xn, hipStream_t st) {
+    hipLaunchKernelGGL(k_sim_par, dim3((B + 255) / 256), dim3(256), 0, st, B, x, u, p, T, steps, xn);
+}
 void launch_estimate(int B, const double* meas, double* filt, const double* u, double dt, int use_lpf, double delay,
                      int steps, double* x_est, double* x_pred, hipStream_t st) {
     hipLaunchKernelGGL(k_estimate, dim3((B + 255) / 256), dim3(256), 0, st, B, meas, filt, u, dt, use_lpf, delay, steps,
@@ -3557,10 +3675,12 @@ void launch_reinit_failed(const Params& P, hipStream_t st) {
     hipLaunchKernelGGL(k_reinit_failed, dim3((P.B + 255) / 256), dim3(256), 0, st, P);
 }
 void launch_sqp_check(const Params& P, const SqpArgs& A, hipStream_t st) {
-    hipLaunchKernelGGL(k_sqp_check, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
+    if (P.mpar) hipLaunchKernelGGL(k_sqp_check_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
+    else hipLaunchKernelGGL(k_sqp_check, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
 }
 void launch_init_iterate(const Params& P, int mode, hipStream_t st) {
-    hipLaunchKernelGGL(k_init_iterate, dim3((P.B + 255) / 256), dim3(256), 0, st, P, mode);
+    if (P.mpar) hipLaunchKernelGGL(k_init_iterate_par, dim3((P.B + 255) / 256), dim3(256), 0, st, P, mode);
+    else hipLaunchKernelGGL(k_init_iterate, dim3((P.B + 255) / 256), dim3(256), 0, st, P, mode);
 }
 
 }  // namespace cfn

@@ -27,6 +27,52 @@ constexpr double G0 = 9.8066, MQ = 33e-3, IXX = 1.395e-5, IYY = 1.395e-5, IZZ = 
 constexpr double KWX = -(IZZ - IYY) / IXX, KWY = -(IXX - IZZ) / IYY, KWZ = -(IYY - IXX) / IZZ;
 constexpr double KT = CT / MQ, KA = -CT * ARM / IXX, KB = -CT * ARM / IYY, KC = -CD / IZZ;
 
+// ---- model constants (cfnmpc_set_model_params) ------------------------------------------------
+// The model functions below take the eight constants they use through K: NomK folds the ones above at compile time (the
+// default of every model function, so the folded-constant kernels compile to what they were without K); ParK holds one
+// instance's own values, derived on the host (derive_k) from a parameter row p = [g0, mq, Ixx, Iyy, Izz, Cd, Ct, l] by the
+// same expressions, so that the nominal row gives bit-identical constants.
+constexpr int NPAR = 8;   // parameters per instance (include/cfnmpc.h: CFNMPC_NP)
+constexpr int NK = 9;     // device rows per instance: g0, KT, KA, KB, KC, KWX, KWY, KWZ | hover speed sqrt(mq g0 / (4 Ct))
+struct NomK {
+    __host__ __device__ static constexpr double g0() { return G0; }
+    __host__ __device__ static constexpr double kt() { return KT; }
+    __host__ __device__ static constexpr double ka() { return KA; }
+    __host__ __device__ static constexpr double kb() { return KB; }
+    __host__ __device__ static constexpr double kc() { return KC; }
+    __host__ __device__ static constexpr double kwx() { return KWX; }
+    __host__ __device__ static constexpr double kwy() { return KWY; }
+    __host__ __device__ static constexpr double kwz() { return KWZ; }
+};
+struct ParK {
+    double c[8];   // g0, KT, KA, KB, KC, KWX, KWY, KWZ
+    __device__ double g0() const { return c[0]; }
+    __device__ double kt() const { return c[1]; }
+    __device__ double ka() const { return c[2]; }
+    __device__ double kb() const { return c[3]; }
+    __device__ double kc() const { return c[4]; }
+    __device__ double kwx() const { return c[5]; }
+    __device__ double kwy() const { return c[6]; }
+    __device__ double kwz() const { return c[7]; }
+};
+// the nominal parameter row (export_ode_model.py:34-42; l = 0.0325 is ARM exactly)
+constexpr double NOM_P[NPAR] = {G0, MQ, IXX, IYY, IZZ, CD, CT, 0.0325};
+static_assert(NOM_P[7] == ARM, "nominal arm length");
+// every entry finite and > 0 (cfnmpc_set_model_params, cfnmpc_sim_params)
+inline bool model_params_ok(const double* p, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (!(p[i] > 0.0 && p[i] <= 1.7976931348623157e308)) return false;   // (NaN fails both)
+    return true;
+}
+// p[NPAR] -> k[NK] (the expressions of the constants above, term for term)
+__host__ __device__ inline void derive_k(const double* p, double* k) {
+    const double g0 = p[0], mq = p[1], ixx = p[2], iyy = p[3], izz = p[4], cd = p[5], ct = p[6], arm = p[7];
+    k[0] = g0;
+    k[1] = ct / mq; k[2] = -ct * arm / ixx; k[3] = -ct * arm / iyy; k[4] = -cd / izz;
+    k[5] = -(izz - iyy) / ixx; k[6] = -(ixx - izz) / iyy; k[7] = -(iyy - ixx) / izz;
+    k[8] = sqrt((mq * g0) / (4 * ct));
+}
+
 // ---- compact pattern of A = d Phi / d x -------------------------------------------------
 __host__ __device__ constexpr int blk(int i) { return i < 3 ? 0 : (i < 7 ? 1 : (i < 10 ? 2 : 3)); }
 // 0: structural zero, 1: unit entry (p-block diagonal), 2: stored
@@ -62,8 +108,9 @@ __host__ __device__ constexpr int s4(int i, int j) {
 }
 
 // ---- continuous dynamics ----------------------------------------------------------------
+template <class K = NomK>
 __device__ __forceinline__ void f_expl(const double* __restrict__ x, const double* __restrict__ u,
-                                       double* __restrict__ dx) {
+                                       double* __restrict__ dx, const K& mk = K()) {
     const double q1 = x[3], q2 = x[4], q3 = x[5], q4 = x[6];
     const double vbx = x[7], vby = x[8], vbz = x[9];
     const double wx = x[10], wy = x[11], wz = x[12];
@@ -75,16 +122,16 @@ __device__ __forceinline__ void f_expl(const double* __restrict__ x, const doubl
     dx[4] = (q1 * wx) / 2 - (q4 * wy) / 2 + (q3 * wz) / 2;
     dx[5] = (q4 * wx) / 2 + (q1 * wy) / 2 - (q2 * wz) / 2;
     dx[6] = (q2 * wy) / 2 - (q3 * wx) / 2 + (q1 * wz) / 2;
-    dx[7] = vby * wz - vbz * wy + G0 * (2 * q1 * q3 - 2 * q2 * q4);
-    dx[8] = vbz * wx - vbx * wz - G0 * (2 * q1 * q2 + 2 * q3 * q4);
+    dx[7] = vby * wz - vbz * wy + mk.g0() * (2 * q1 * q3 - 2 * q2 * q4);
+    dx[8] = vbz * wx - vbx * wz - mk.g0() * (2 * q1 * q2 + 2 * q3 * q4);
     // (rotor terms and gyroscopic couplings with the constants folded at compile time -- KT = Ct / mq, KA = -Ct l / Ixx, ...,
     //  KWX = -(Izz - Iyy) / Ixx, ...: the same products jvp() differentiates; a division by mq / Ixx / Iyy / Izz per
     //  evaluation cost k_linearise 16 FP64 divisions per shooting interval)
     const double s1 = w1 * w1, s2 = w2 * w2, s3 = w3 * w3, s4 = w4 * w4;
-    dx[9] = vbx * wy - vby * wx - G0 * (2 * q1 * q1 + 2 * q4 * q4 - 1) + KT * (s1 + s2 + s3 + s4);
-    dx[10] = KA * (s1 + s2 - s3 - s4) + KWX * (wy * wz);
-    dx[11] = KB * (s1 - s2 - s3 + s4) + KWY * (wx * wz);
-    dx[12] = KC * (s1 - s2 + s3 - s4) + KWZ * (wx * wy);
+    dx[9] = vbx * wy - vby * wx - mk.g0() * (2 * q1 * q1 + 2 * q4 * q4 - 1) + mk.kt() * (s1 + s2 + s3 + s4);
+    dx[10] = mk.ka() * (s1 + s2 - s3 - s4) + mk.kwx() * (wy * wz);
+    dx[11] = mk.kb() * (s1 - s2 - s3 + s4) + mk.kwy() * (wx * wz);
+    dx[12] = mk.kc() * (s1 - s2 + s3 - s4) + mk.kwz() * (wx * wy);
 }
 
 // Point data of df/dx at one RK stage point that is shared by all sensitivity columns:
@@ -114,8 +161,8 @@ __device__ __forceinline__ void jac_point(const double* __restrict__ x, JacPoint
 
 // out = (df/dx)(point) * s  for a direction s whose q-part / w-part may be structurally zero.
 // s, out: 13 entries (s[0..2] is never read: nothing depends on position).
-template <bool HQ, bool HW>
-__device__ __forceinline__ void jvp(const JacPoint& J, const double* __restrict__ s, double* __restrict__ o) {
+template <bool HQ, bool HW, class K = NomK>
+__device__ __forceinline__ void jvp(const JacPoint& J, const double* __restrict__ s, double* __restrict__ o, const K& mk = K()) {
     const double q1 = J.q[0], q2 = J.q[1], q3 = J.q[2], q4 = J.q[3];
     const double vx = J.v[0], vy = J.v[1], vz = J.v[2];
     const double wx = J.w[0], wy = J.w[1], wz = J.w[2];
@@ -137,9 +184,9 @@ __device__ __forceinline__ void jvp(const JacPoint& J, const double* __restrict_
         o4 += 0.5 * (wx * a + wz * c - wy * d);
         o5 += 0.5 * (wy * a - wz * b + wx * d);
         o6 += 0.5 * (wz * a + wy * b - wx * c);
-        o7 += 2 * G0 * (q3 * a - q4 * b + q1 * c - q2 * d);
-        o8 += -2 * G0 * (q2 * a + q1 * b + q4 * c + q3 * d);
-        o9 += -4 * G0 * (q1 * a + q4 * d);
+        o7 += 2 * mk.g0() * (q3 * a - q4 * b + q1 * c - q2 * d);
+        o8 += -2 * mk.g0() * (q2 * a + q1 * b + q4 * c + q3 * d);
+        o9 += -4 * mk.g0() * (q1 * a + q4 * d);
     }
     if (HW) {
         const double a = s[10], b = s[11], c = s[12];
@@ -150,9 +197,9 @@ __device__ __forceinline__ void jvp(const JacPoint& J, const double* __restrict_
         o7 += -vz * b + vy * c;
         o8 += vz * a - vx * c;
         o9 += -vy * a + vx * b;
-        o10 = KWX * (wz * b + wy * c);
-        o11 = KWY * (wz * a + wx * c);
-        o12 = KWZ * (wy * a + wx * b);
+        o10 = mk.kwx() * (wz * b + wy * c);
+        o11 = mk.kwy() * (wz * a + wx * c);
+        o12 = mk.kwz() * (wy * a + wx * b);
     }
     o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3; o[4] = o4; o[5] = o5; o[6] = o6;
     o[7] = o7; o[8] = o8; o[9] = o9; o[10] = o10; o[11] = o11; o[12] = o12;
@@ -176,8 +223,9 @@ __device__ __forceinline__ void ju_col(int c, const double* __restrict__ u, doub
 //   xq[10] = q | v | w of the point, sq[10] = the direction's q | v | w parts (nothing depends on position);
 //   rot[4] = the rotor terms of v_z', w' (functions of u only: constant over the interval), ju[4] = (df/du) du rows 9..12;
 //   kk[13], dk[13]: slopes in EXTERNAL order.  With r = R(q) / 2:  p' = R v,  dp' = R dv + dR v.
+template <class K = NomK>
 __device__ __forceinline__ void lf_point(const double (&xq)[10], const double (&sq)[10], const double (&rot)[4],
-                                         const double (&ju)[4], double (&kk)[13], double (&dk)[13]) {
+                                         const double (&ju)[4], double (&kk)[13], double (&dk)[13], const K& mk = K()) {
     const double q1 = xq[0], q2 = xq[1], q3 = xq[2], q4 = xq[3], vx = xq[4], vy = xq[5], vz = xq[6];
     const double wx = xq[7], wy = xq[8], wz = xq[9];
     const double a = sq[0], b = sq[1], c = sq[2], d = sq[3], sx = sq[4], sy = sq[5], sz = sq[6];
@@ -218,19 +266,19 @@ __device__ __forceinline__ void lf_point(const double (&xq)[10], const double (&
     dk[5] = d * hx + a * hy - b * hz + q4 * gx + q1 * gy - q2 * gz;
     dk[6] = b * hy - c * hx + a * hz + q2 * gy - q3 * gx + q1 * gz;
     // body velocity rows: v' = v x w - g0 R' e_z (+ thrust);  -G0 R[6..8] = -2 G0 r[6..8]
-    kk[7] = vy * wz - vz * wy - (2.0 * G0) * r6;
-    kk[8] = vz * wx - vx * wz - (2.0 * G0) * r7;
-    kk[9] = vx * wy - vy * wx - (2.0 * G0) * r8 + rot[0];
-    dk[7] = sy * wz + vy * oz - sz * wy - vz * oy - (2.0 * G0) * dr6;
-    dk[8] = sz * wx + vz * ox - sx * wz - vx * oz - (2.0 * G0) * dr7;
-    dk[9] = sx * wy + vx * oy - sy * wx - vy * ox - (4.0 * G0) * h8 + ju[0];
+    kk[7] = vy * wz - vz * wy - (2.0 * mk.g0()) * r6;
+    kk[8] = vz * wx - vx * wz - (2.0 * mk.g0()) * r7;
+    kk[9] = vx * wy - vy * wx - (2.0 * mk.g0()) * r8 + rot[0];
+    dk[7] = sy * wz + vy * oz - sz * wy - vz * oy - (2.0 * mk.g0()) * dr6;
+    dk[8] = sz * wx + vz * ox - sx * wz - vx * oz - (2.0 * mk.g0()) * dr7;
+    dk[9] = sx * wy + vx * oy - sy * wx - vy * ox - (4.0 * mk.g0()) * h8 + ju[0];
     // body rate rows
-    kk[10] = KWX * (wy * wz) + rot[1];
-    kk[11] = KWY * (wx * wz) + rot[2];
-    kk[12] = KWZ * (wx * wy) + rot[3];
-    dk[10] = KWX * (oy * wz + wy * oz) + ju[1];
-    dk[11] = KWY * (ox * wz + wx * oz) + ju[2];
-    dk[12] = KWZ * (ox * wy + wx * oy) + ju[3];
+    kk[10] = mk.kwx() * (wy * wz) + rot[1];
+    kk[11] = mk.kwy() * (wx * wz) + rot[2];
+    kk[12] = mk.kwz() * (wx * wy) + rot[3];
+    dk[10] = mk.kwx() * (oy * wz + wy * oz) + ju[1];
+    dk[11] = mk.kwy() * (ox * wz + wx * oz) + ju[2];
+    dk[12] = mk.kwz() * (ox * wy + wx * oy) + ju[3];
 }
 
 }  // namespace cfn

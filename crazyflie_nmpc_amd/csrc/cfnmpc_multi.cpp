@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/cfnmpc.h"
+#include "cfnmpc_model.hpp"
 
 namespace {
 struct Shard {
@@ -271,6 +272,16 @@ int cfnmpc_multi_set_cost_scaling(cfnmpc_multi* m, double stage_scale, double te
     if (!m) return CFNMPC_EINVAL;
     for (Shard& s : m->sh)
         RC_TRY(m->mixed ? cfnmpc_fleet_set_cost_scaling(s.f, stage_scale, terminal_scale) : cfnmpc_set_cost_scaling(s.s, stage_scale, terminal_scale));
+    return CFNMPC_OK;
+}
+
+int cfnmpc_multi_set_model_params(cfnmpc_multi* m, const double* p) {
+    if (!m) return CFNMPC_EINVAL;
+    if (p && !cfn::model_params_ok(p, (size_t)m->B * CFNMPC_NP)) return CFNMPC_EINVAL;   // (as a whole: no shard changes)
+    for (Shard& s : m->sh) {
+        if (m->mixed) RC_TRY(cfnmpc_fleet_set_model_params(s.f, p ? to_shard(s, p, CFNMPC_NP, CFNMPC_NP) : nullptr));
+        else RC_TRY(cfnmpc_set_model_params(s.s, p ? p + (size_t)s.lo * CFNMPC_NP : nullptr, CFNMPC_ON_HOST, s.st));
+    }
     return CFNMPC_OK;
 }
 

@@ -181,6 +181,8 @@ struct Params {
     double *cb;                  // condensed blocks, [instance][block][cb_size(w_max)] (layout: cfnmpc_pcond.hip)
     int erk_steps;               // M: classic RK4 steps of dt / M per shooting interval (cfnmpc_set_erk_steps; 1 = k_linearise / k_forward,
                                  // M > 1 = their _erk variants; k_sqp_check reads it either way)
+    double* mpar;                // per-instance model constants (cfnmpc_set_model_params), [NK][(NW + 1) * 4] structure-of-arrays
+                                 // (cfnmpc_model.hpp: derive_k; the spare block's rows nominal); NULL = the folded constants
 };
 
 // The linearisation (AR, BR, b) of the HOME blocks: [group of 16 blocks][stage][block of the group][sz] -- a lane-per-instance wave
@@ -232,6 +234,8 @@ void launch_qp_cond(const Params& P, hipStream_t st);    // = the four above
 void launch_estimate(int B, const double* meas, double* filt, const double* u, double dt, int use_lpf, double delay,
                      int steps, double* x_est, double* x_pred, hipStream_t st);
 void launch_sim(int B, const double* x, const double* u, double T, int steps, double* xn, hipStream_t st);
+// the same with per-instance parameters p [B][NPAR] (instance-major, cfnmpc_sim_params)
+void launch_sim_par(int B, const double* x, const double* u, const double* p, double T, int steps, double* xn, hipStream_t st);
 // AoS [B][S][E] (external order) <-> wave-blocked vectors; perm13: first 13 entries of each
 // row are states and are permuted to the internal order.
 void launch_put(int B, int S, int E, int perm13, const double* aos, double* blk, hipStream_t st, int v4b = 0);   // v4b: E = 4 fields in the wave-blocked layout (Params.v4b)

@@ -104,6 +104,16 @@ class MixedHorizonFleet:
     def set_cost_scaling(self, stage=1.0, terminal=1.0):
         _check(self._L.cfnmpc_fleet_set_cost_scaling(self._h, float(stage), float(terminal)), "cfnmpc_fleet_set_cost_scaling")
 
+    def set_model_params(self, p=None):
+        """per-vehicle model parameters, host array [B][NP] in the fleet's vehicle order; None: nominal"""
+        if p is None:
+            _check(self._L.cfnmpc_fleet_set_model_params(self._h, None), "cfnmpc_fleet_set_model_params")
+            return
+        pa = np.ascontiguousarray(p, dtype=np.float64)
+        if pa.shape != (self.B, 8):
+            raise ValueError(f"expected shape {(self.B, 8)}, got {pa.shape}")
+        _check(self._L.cfnmpc_fleet_set_model_params(self._h, pa.ctypes.data_as(C.c_void_p)), "cfnmpc_fleet_set_model_params")
+
     def set_box_stages(self, lb=None, ub=None):
         """per-stage / per-input boxes, host arrays [B][Nmax][4] (vehicle i uses rows 0..N_i-1); None, None: scalar box"""
         if lb is None and ub is None:

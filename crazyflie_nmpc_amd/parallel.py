@@ -132,6 +132,19 @@ class MultiGpuFleet:
         if rc != 0:
             raise ValueError(f"cfnmpc_multi_set_erk_steps failed with code {rc}")
 
+    def set_model_params(self, p=None):
+        """per-vehicle model parameters, host array [B][8] of the whole fleet; None: nominal"""
+        import ctypes as C
+        if p is None:
+            rc = self._L.cfnmpc_multi_set_model_params(self._h, None)
+        else:
+            pa = np.ascontiguousarray(p, dtype=np.float64)
+            if pa.shape != (self.B, 8):
+                raise ValueError(f"expected shape {(self.B, 8)}, got {pa.shape}")
+            rc = self._L.cfnmpc_multi_set_model_params(self._h, pa.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise ValueError(f"cfnmpc_multi_set_model_params failed with code {rc}")
+
     def set_cost_scaling(self, stage=1.0, terminal=1.0):
         rc = self._L.cfnmpc_multi_set_cost_scaling(self._h, float(stage), float(terminal))
         if rc != 0:

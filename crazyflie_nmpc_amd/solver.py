@@ -19,6 +19,17 @@ from ._lib import NU, NX, NY, Opts
 
 INIT_ACADOS, INIT_HOVER = 0, 1
 
+# per-instance model parameters (include/cfnmpc.h: cfnmpc_set_model_params), export_ode_model.py:33-42 order, l = arm length
+NP = 8
+PARAM_NAMES = ("g0", "mq", "Ixx", "Iyy", "Izz", "Cd", "Ct", "l")
+NOMINAL_PARAMS = np.array([9.8066, 33e-3, 1.395e-5, 1.395e-5, 2.173e-5, 7.9379e-06, 3.25e-4, 0.0325])
+
+
+def hover_speed(params):
+    """Per-row hover speed sqrt(mq g0 / (4 Ct)) in kRPM of parameter rows [..., NP] (the input part of yref)."""
+    p = np.asarray(params, dtype=np.float64)
+    return np.sqrt((p[..., 1] * p[..., 0]) / (4 * p[..., 6]))
+
 
 class CfnmpcError(RuntimeError):
     pass
@@ -169,6 +180,21 @@ class BatchSolver:
     def set_cost_scaling(self, stage=1.0, terminal=1.0):
         """Effective weights stage * W (stages 0..N-1) and terminal * WN; newer acados uses (dt, 1)."""
         _check(self._L.cfnmpc_set_cost_scaling(self._h, float(stage), float(terminal)), "cfnmpc_set_cost_scaling")
+
+    def set_model_params(self, p=None):
+        """Per-instance model parameters [B][NP] (PARAM_NAMES order; numpy or a device tensor); None: back to the
+        nominal model folded into the default kernels.  Every entry finite and > 0."""
+        if p is None:
+            _check(self._L.cfnmpc_set_model_params(self._h, None, 0, _launch_stream(None, self._device)), "cfnmpc_set_model_params")
+            return
+        pp, dev, st, _k = _arg(p, (self.B, NP), device=self._device)
+        _check(self._L.cfnmpc_set_model_params(self._h, pp, dev, st), "cfnmpc_set_model_params")
+
+    def model_params(self):
+        """-> [B][NP] rows in force (the nominal row everywhere while none are set)"""
+        out = np.empty((self.B, NP))
+        _check(self._L.cfnmpc_get_model_params(self._h, out.ctypes.data_as(C.c_void_p), 0, None), "cfnmpc_get_model_params")
+        return out
 
     def set_box_stages(self, lb=None, ub=None):
         """Per-stage, per-input box [B][N][4] (acados' "lbu" / "ubu" on individual stages); None, None: back to
@@ -344,8 +370,9 @@ class BatchSolver:
         return h
 
 
-def sim(x, u, T=0.06, steps=4, out=None):
-    """Batched predictor / plant step (crazyflie_acados_sim_solve, acados_estimator.cpp:589)."""
+def sim(x, u, T=0.06, steps=4, out=None, params=None):
+    """Batched predictor / plant step (crazyflie_acados_sim_solve, acados_estimator.cpp:589).  params [B][NP]: each
+    row's own model (cfnmpc_sim_params), e.g. a plant that differs from the controller's model."""
     L = _lib.lib()
     B = x.shape[0]
     if _is_torch(x):
@@ -353,11 +380,24 @@ def sim(x, u, T=0.06, steps=4, out=None):
         if out is None:
             out = torch.empty_like(x)
         px, _d, st, _k = _arg(x, (B, NX), device=_torch_device()); pu, _d2, _s, _k2 = _arg(u, (B, NU), device=_torch_device()); po, _d3, _s3, _k3 = _arg(out, (B, NX), device=_torch_device())
+        if params is not None:
+            if not _is_torch(params):   # (host rows: uploaded beside x, the kernel reads device memory only)
+                params = torch.as_tensor(np.ascontiguousarray(params, dtype=np.float64), device=x.device)
+            pp, _d4, _s4, _k4 = _arg(params, (B, NP), device=_torch_device())
+            _check(L.cfnmpc_sim_params(B, px, pu, pp, float(T), int(steps), po, 1, st), "cfnmpc_sim_params")
+            return out
         _check(L.cfnmpc_sim(B, px, pu, float(T), int(steps), po, 1, st), "cfnmpc_sim")
         return out
     xa = np.ascontiguousarray(x, dtype=np.float64); ua = np.ascontiguousarray(u, dtype=np.float64)
     if out is None:
         out = np.empty_like(xa)
+    if params is not None:
+        pa = np.ascontiguousarray(params, dtype=np.float64)
+        if pa.shape != (B, NP):
+            raise ValueError(f"expected shape {(B, NP)}, got {pa.shape}")
+        _check(L.cfnmpc_sim_params(B, xa.ctypes.data_as(C.c_void_p), ua.ctypes.data_as(C.c_void_p), pa.ctypes.data_as(C.c_void_p),
+                                   float(T), int(steps), out.ctypes.data_as(C.c_void_p), 0, None), "cfnmpc_sim_params")
+        return out
     _check(L.cfnmpc_sim(B, xa.ctypes.data_as(C.c_void_p), ua.ctypes.data_as(C.c_void_p), float(T), int(steps),
                         out.ctypes.data_as(C.c_void_p), 0, None), "cfnmpc_sim")
     return out

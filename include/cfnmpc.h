@@ -258,6 +258,20 @@ int cfnmpc_set_box(cfnmpc_solver *s, double u_min, double u_max);
 int cfnmpc_set_erk_steps(cfnmpc_solver *s, int num_steps);
 int cfnmpc_erk_steps(const cfnmpc_solver *s);
 int cfnmpc_set_cost_scaling(cfnmpc_solver *s, double stage_scale, double terminal_scale);
+/* Per-instance model parameters: p [B][CFNMPC_NP], one row per instance in the order of
+ * export_ode_model.py:33-42, [g0, mq, Ixx, Iyy, Izz, Cd, Ct, l] (l = arm length, in place of dq).  The nominal row is
+ *   [9.8066, 33e-3, 1.395e-5, 1.395e-5, 2.173e-5, 7.9379e-06, 3.25e-4, 0.0325]
+ * and gives bit for bit the constants the default kernels fold in.  The linearisation, the matrix-free forward sweeps, the
+ * SQP residual (res_eq), cfnmpc_init_iterate's hover mode (sqrt(mq g0 / (4 Ct)) per instance) use each instance's row.
+ *   cfnmpc_set_model_params: every entry finite and > 0, else CFNMPC_EINVAL and nothing changes (device arrays are copied
+ *     to the host once to be checked).  p = NULL returns the solver to the folded constants.  Refused (CFNMPC_EINVAL) beside
+ *     start_solve 2 or 3 (the fused start solve integrates with the folded constants).  Switching between NULL and
+ *     parameters invalidates captured step graphs; new values over old ones are copied in place on `stream` and complete
+ *     before the call returns, so the next solve or graph replay reads them.
+ *   cfnmpc_get_model_params: the rows in force (the nominal row for every instance while none are set). */
+#define CFNMPC_NP 8
+int cfnmpc_set_model_params(cfnmpc_solver *s, const double *p /*[B][CFNMPC_NP] or NULL*/, int on_device, void *stream);
+int cfnmpc_get_model_params(cfnmpc_solver *s, double *p /*[B][CFNMPC_NP]*/, int on_device, void *stream);
 /* Per-stage, per-input box: lb, ub [B][N][4] (what "lbu" / "ubu" on INDIVIDUAL stages set in acados -- the reference's
  * FIXED_U0 variant pins stage 0 to the input in flight, lbu = ubu = u1, acados_mpc.cpp:605-608).  lb[i] = ub[i] makes
  * that input an equality (the active-set solves keep it fixed whatever its multiplier's sign; the interior-point
@@ -358,6 +372,10 @@ int cfnmpc_get_profile_steps(cfnmpc_solver *s, double *ms_steps, int max_steps, 
 /* crazyflie_acados_sim_solve() equivalent, batched (acados_estimator.cpp:573-593):
  * xn = RK4(x, u) over T seconds in `steps` sub-steps.  Stateless. */
 int cfnmpc_sim(int batch, const double *x, const double *u, double T, int steps, double *xn, int on_device, void *stream);
+/* The same with per-instance model parameters p [batch][CFNMPC_NP] (as cfnmpc_set_model_params): a plant or predictor that
+ * differs from the controller's model.  Host arrays are validated (finite, > 0); device arrays are taken as they are. */
+int cfnmpc_sim_params(int batch, const double *x, const double *u, const double *p, double T, int steps, double *xn,
+                      int on_device, void *stream);
 
 /* ESTIMATOR::predictor() for a fleet (acados_estimator.cpp:521-634), DEVICE pointers only:
  * assembles the 13-state from mocap position, onboard Euler angles [deg, as published by the
@@ -422,6 +440,8 @@ int cfnmpc_fleet_set_box(cfnmpc_fleet *f, double u_min, double u_max);
 /* cfnmpc_set_erk_steps / cfnmpc_set_cost_scaling for every bucket */
 int cfnmpc_fleet_set_erk_steps(cfnmpc_fleet *f, int num_steps);
 int cfnmpc_fleet_set_cost_scaling(cfnmpc_fleet *f, double stage_scale, double terminal_scale);
+/* cfnmpc_set_model_params for a fleet: HOST array [B][CFNMPC_NP] in the fleet's vehicle order (NULL: nominal) */
+int cfnmpc_fleet_set_model_params(cfnmpc_fleet *f, const double *p);
 /* cfnmpc_set_box_stages for a fleet: HOST arrays [B][Nmax][4] in the fleet's vehicle order (rows behind a vehicle's own
  * horizon are ignored); NULL, NULL: back to the scalar box */
 int cfnmpc_fleet_set_box_stages(cfnmpc_fleet *f, const double *lb, const double *ub);
@@ -483,6 +503,8 @@ int cfnmpc_multi_set_box_stages(cfnmpc_multi *m, const double *lb, const double 
 /* cfnmpc_set_erk_steps / cfnmpc_set_cost_scaling for every shard */
 int cfnmpc_multi_set_erk_steps(cfnmpc_multi *m, int num_steps);
 int cfnmpc_multi_set_cost_scaling(cfnmpc_multi *m, double stage_scale, double terminal_scale);
+/* cfnmpc_set_model_params for every shard: HOST array [B][CFNMPC_NP] of the whole fleet (NULL: nominal) */
+int cfnmpc_multi_set_model_params(cfnmpc_multi *m, const double *p);
 
 const char *cfnmpc_version(void);
 
