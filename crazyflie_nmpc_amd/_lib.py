@@ -28,6 +28,8 @@ SYMBOLS = [
     "cfnmpc_fleet_set_cost_scaling", "cfnmpc_multi_set_erk_steps", "cfnmpc_multi_set_cost_scaling",
     "cfnmpc_set_model_params", "cfnmpc_get_model_params", "cfnmpc_fleet_set_model_params", "cfnmpc_multi_set_model_params",
     "cfnmpc_sim_params",
+    "cfnmpc_eval_sens_x0", "cfnmpc_get_sens_x0", "cfnmpc_get_sens_active", "cfnmpc_fleet_eval_sens_x0", "cfnmpc_fleet_get_sens_x0",
+    "cfnmpc_multi_eval_sens_x0", "cfnmpc_multi_get_sens_x0",
 ]
 ABI_VERSION = 9   # CFNMPC_ABI_VERSION of the include/cfnmpc.h this binding was written against
 
@@ -95,6 +97,13 @@ def lib():
     L.cfnmpc_get_u.argtypes = [vp, i32, vp, i32, vp]
     L.cfnmpc_get_x.argtypes = [vp, i32, vp, i32, vp]
     L.cfnmpc_get_stats.argtypes = [vp, vp, vp, vp, i32, vp]
+    L.cfnmpc_eval_sens_x0.argtypes = [vp, dbl, vp]
+    L.cfnmpc_get_sens_x0.argtypes = [vp, i32, i32, vp, vp, i32, vp]
+    L.cfnmpc_get_sens_active.argtypes = [vp, vp, i32, vp]
+    L.cfnmpc_fleet_eval_sens_x0.argtypes = [vp, dbl, vp]
+    L.cfnmpc_fleet_get_sens_x0.argtypes = [vp, i32, i32, vp, vp, i32, vp]
+    L.cfnmpc_multi_eval_sens_x0.argtypes = [vp, dbl]
+    L.cfnmpc_multi_get_sens_x0.argtypes = [vp, i32, i32, vp, vp]
     L.cfnmpc_sim.argtypes = [i32, vp, vp, dbl, i32, vp, i32, vp]
     L.cfnmpc_estimate.argtypes = [i32, vp, vp, vp, dbl, i32, dbl, i32, vp, vp, vp]
     L.cfnmpc_debug_get_linearisation.argtypes = [vp, vp, vp, vp]

@@ -13,6 +13,8 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <new>
+#include <set>
 
 #include "../../include/acados_sim_solver_crazyflie.h"
 #include "../../include/acados_solver_crazyflie.h"
@@ -32,6 +34,10 @@ struct Shim {
     double scaling[N + 1];              // per-stage cost scaling as set through "scaling" (default 1)
     int erk_steps = 1;                  // "sim_method_num_steps" as set through ocp_nlp_solver_opts_set
     bool weights_dirty = false, box_dirty = false, disc_dirty = false;
+    // solution sensitivities w.r.t. x0 of the last acados_solve() (ocp_nlp_eval_param_sens): evaluated at the first request
+    // after a solve, all stages at once (0: not yet, 1: held, -1: the engine refused)
+    int sens_state = 0;
+    double sdu[N][NU][NX], sdx[N + 1][NX][NX];
     ocp_nlp_in in;
     ocp_nlp_out out;
     ocp_nlp_solver solver;
@@ -41,6 +47,16 @@ struct Shim {
     external_function_param_casadi vde;
 };
 Shim* g = nullptr;
+// outs made by ocp_nlp_out_create: column `index` of dx_k/dx0 and du_k/dx0 as the last ocp_nlp_eval_param_sens left them
+struct SensOut {
+    ocp_nlp_out out;
+    double x[N + 1][NX], u[N][NU];
+};
+std::set<ocp_nlp_out*> g_sens_outs;
+void sens_fill_nan(SensOut* o) {
+    for (auto& r : o->x) for (double& v : r) v = std::nan("");
+    for (auto& r : o->u) for (double& v : r) v = std::nan("");
+}
 
 sim_config g_sim_config;
 sim_in g_sim_in;
@@ -222,6 +238,7 @@ int acados_solve(void) {
     int status = 1, iters = 0;
     double res = 0.0;
     // inputs in, one RTI step, iterate and statistics out: one transfer each way, one synchronisation
+    g->sens_state = 0;
     if (cfnmpc_step_host(g->s, g->lbx, g->yref, g->yref_e, g->u, g->x, &status, &iters, &res, nullptr) != CFNMPC_OK) return 1;
     g->out.inf_norm_res = res;
     g->out.qp_iter = iters;
@@ -229,11 +246,53 @@ int acados_solve(void) {
     return status;
 }
 
-void ocp_nlp_out_get(ocp_nlp_config*, ocp_nlp_dims*, ocp_nlp_out*, int stage, const char* field, void* value) {
-    if (!g || !field || !value) return;
+void ocp_nlp_out_get(ocp_nlp_config*, ocp_nlp_dims*, ocp_nlp_out* out, int stage, const char* field, void* value) {
+    if (!field || !value) return;
     double* v = static_cast<double*>(value);
+    if (out && g_sens_outs.count(out)) {   // a sensitivity out (ocp_nlp_out_create)
+        const SensOut* o = reinterpret_cast<const SensOut*>(out);
+        if (!std::strcmp(field, "x") && stage >= 0 && stage <= N) std::memcpy(v, o->x[stage], sizeof(double) * NX);
+        else if (!std::strcmp(field, "u") && stage >= 0 && stage < N) std::memcpy(v, o->u[stage], sizeof(double) * NU);
+        return;
+    }
+    if (!g) return;
     if (!std::strcmp(field, "x") && stage >= 0 && stage <= N) std::memcpy(v, g->x + stage * NX, sizeof(double) * NX);
     else if (!std::strcmp(field, "u") && stage >= 0 && stage < N) std::memcpy(v, g->u + stage * NU, sizeof(double) * NU);
+}
+
+ocp_nlp_out* ocp_nlp_out_create(ocp_nlp_config*, ocp_nlp_dims*) {
+    SensOut* o = new (std::nothrow) SensOut();
+    if (!o) return nullptr;
+    o->out = ocp_nlp_out{0.0, 0.0, 1, 0, o};
+    sens_fill_nan(o);
+    g_sens_outs.insert(&o->out);
+    return &o->out;
+}
+
+void ocp_nlp_out_destroy(void* out) {
+    ocp_nlp_out* p = static_cast<ocp_nlp_out*>(out);
+    if (!p || !g_sens_outs.erase(p)) return;   // (only what ocp_nlp_out_create made)
+    delete reinterpret_cast<SensOut*>(p);
+}
+
+// field "ex", stage 0, 0 <= index < 13: sens_out gets column `index` of dx_k/dx0 (k = 0..N) and du_k/dx0 (k < N) of the last
+// acados_solve()'s QP (cfnmpc_eval_sens_x0, act_tol 1e-6).  Anything invalid leaves NaN in sens_out; never aborts.
+void ocp_nlp_eval_param_sens(ocp_nlp_solver*, char* field, int stage, int index, ocp_nlp_out* sens_out) {
+    if (!sens_out || !g_sens_outs.count(sens_out)) return;
+    SensOut* o = reinterpret_cast<SensOut*>(sens_out);
+    sens_fill_nan(o);
+    if (!g || !field || std::strcmp(field, "ex") != 0 || stage != 0 || index < 0 || index >= NX) return;
+    if (g->sens_state == 0) {
+        const bool ok = cfnmpc_eval_sens_x0(g->s, 1e-6, nullptr) == CFNMPC_OK &&
+                        cfnmpc_get_sens_x0(g->s, 0, N, &g->sdu[0][0][0], nullptr, CFNMPC_ON_HOST, nullptr) == CFNMPC_OK &&
+                        cfnmpc_get_sens_x0(g->s, 0, N + 1, nullptr, &g->sdx[0][0][0], CFNMPC_ON_HOST, nullptr) == CFNMPC_OK;
+        g->sens_state = ok ? 1 : -1;
+    }
+    if (g->sens_state != 1) return;
+    for (int k = 0; k <= N; k++)
+        for (int i = 0; i < NX; i++) o->x[k][i] = g->sdx[k][i][index];
+    for (int k = 0; k < N; k++)
+        for (int a = 0; a < NU; a++) o->u[k][a] = g->sdu[k][a][index];
 }
 
 // ---------------------------------------------------------------- predictor (sim solver)

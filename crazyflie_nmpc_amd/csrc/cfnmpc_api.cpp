@@ -3,6 +3,7 @@
 // There is no CPU fallback: without a usable HIP device cfnmpc_create() fails.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -67,6 +68,14 @@ struct cfnmpc_solver {
     // device block of derived constants P.mpar points to while set (allocated at the first call, kept for later ones)
     std::vector<double> mp_rows;
     double* mpar_buf;
+    // solution sensitivities (cfnmpc_eval_sens_x0): what the last QP was (0: none, or its data changed since; 1: an RTI step;
+    // 2: an SQP iteration, whose status is sqp.status), whether an evaluation belongs to it, the buffers (allocated at the
+    // first evaluation) and the staging buffer of host reads
+    int sens_src;
+    bool sens_valid;
+    cfn::SensArgs sens;
+    double* sens_stage;
+    size_t sens_stage_doubles;
 };
 
 namespace {
@@ -557,6 +566,8 @@ int cfnmpc_set_yref_windows(cfnmpc_solver* s, const double* traj, int n_rows, in
 
 // kernel arguments changed (weights, box): the captured steps hold the old ones
 static void invalidate_graphs(cfnmpc_solver* s) { s->gvalid[0] = s->gvalid[1] = false; }
+// the QP's data changed since the last solve: no sensitivities until the next one
+static void invalidate_sens(cfnmpc_solver* s) { s->sens_src = 0; s->sens_valid = false; }
 
 int cfnmpc_set_weights(cfnmpc_solver* s, const double* W, const double* WN) {
     if (!s || (!W && !WN)) return CFNMPC_EINVAL;
@@ -564,6 +575,7 @@ int cfnmpc_set_weights(cfnmpc_solver* s, const double* W, const double* WN) {
     if (W) for (int i = 0; i < 17; i++) s->P.W[i] = s->stage_scale * (s->W_set[i] = W[i]);
     if (WN) for (int i = 0; i < 13; i++) s->P.WN[i] = s->terminal_scale * (s->WN_set[i] = WN[i]);
     invalidate_graphs(s);
+    invalidate_sens(s);
     return CFNMPC_OK;  // kernel arguments: take effect at the next cfnmpc_solve
 }
 
@@ -571,6 +583,7 @@ int cfnmpc_set_cost_scaling(cfnmpc_solver* s, double stage_scale, double termina
     if (!s || !(std::isfinite(stage_scale) && stage_scale > 0) || !(std::isfinite(terminal_scale) && terminal_scale > 0))
         return CFNMPC_EINVAL;
     s->stage_scale = stage_scale;
+    invalidate_sens(s);
     s->terminal_scale = terminal_scale;
     for (int i = 0; i < 17; i++) s->P.W[i] = stage_scale * s->W_set[i];
     for (int i = 0; i < 13; i++) s->P.WN[i] = terminal_scale * s->WN_set[i];
@@ -584,6 +597,7 @@ int cfnmpc_set_erk_steps(cfnmpc_solver* s, int num_steps) {
     // overlapped preparation (k_linearise_list) likewise
     if (num_steps > 1 && (s->P.fused || s->overlap)) return CFNMPC_EINVAL;
     s->P.erk_steps = num_steps;
+    invalidate_sens(s);
     s->lin_valid = false;
     invalidate_graphs(s);
     return CFNMPC_OK;
@@ -599,6 +613,7 @@ int cfnmpc_set_model_params(cfnmpc_solver* s, const double* p, int on_device, vo
     if (!p) {   // back to the folded constants (the default kernels)
         if (P.mpar) { P.mpar = nullptr; s->lin_valid = false; invalidate_graphs(s); }
         s->mp_rows.clear();
+        invalidate_sens(s);
         return CFNMPC_OK;
     }
     // the fused start solve (k_linfactor, k_linearise_clist) and the development build's overlapped preparation
@@ -632,6 +647,7 @@ int cfnmpc_set_model_params(cfnmpc_solver* s, const double* p, int on_device, vo
     if (!P.mpar) { P.mpar = s->mpar_buf; invalidate_graphs(s); }   // other kernels from here on
     s->lin_valid = false;
     s->mp_rows = std::move(rows);
+    invalidate_sens(s);
     return CFNMPC_OK;
 }
 
@@ -657,6 +673,7 @@ int cfnmpc_set_box(cfnmpc_solver* s, double u_min, double u_max) {
     if (!s || !(u_max > u_min)) return CFNMPC_EINVAL;
     s->P.u_min = u_min;   // kernel arguments: take effect at the next cfnmpc_solve
     s->P.u_max = u_max;
+    invalidate_sens(s);
     invalidate_graphs(s);
     return CFNMPC_OK;
 }
@@ -669,6 +686,7 @@ int cfnmpc_set_box_stages(cfnmpc_solver* s, const double* lb, const double* ub, 
         if (P.lbs) { s->lbs_keep = P.lbs; s->ubs_keep = P.ubs; }
         P.lbs = P.ubs = nullptr;
         invalidate_graphs(s);
+        invalidate_sens(s);
         return CFNMPC_OK;
     }
     if (P.cond_N2) return CFNMPC_EINVAL;   // the condensed path has no per-stage boxes
@@ -677,6 +695,7 @@ int cfnmpc_set_box_stages(cfnmpc_solver* s, const double* lb, const double* ub, 
     // that hands over device pointers is responsible for lb <= ub (an inverted box ends in status 4 for that vehicle)
     if (is_host(on_device))
         for (size_t i = 0; i < n; i++) if (!(lb[i] <= ub[i])) return CFNMPC_EINVAL;
+    invalidate_sens(s);
     if (!s->lbs_keep || !P.clbs || !P.cubs) {
         // allocated and initialised as a whole before any pointer is committed: a failure half-way (ENOMEM, a failed copy)
         // leaves the solver on the scalar box with nothing dangling (the blocks stay owned by s->allocs until cfnmpc_free)
@@ -738,6 +757,7 @@ int cfnmpc_init_iterate(cfnmpc_solver* s, int mode, void* stream) {
     HIP_TRY(hipGetLastError());
     if (s->P.as_warm) HIP_TRY(hipMemsetAsync(s->P.wvalid, 0, sizeof(int) * (size_t)s->P.B, (hipStream_t)stream));   // a new iterate: no set to start from
     s->lin_valid = false;
+    invalidate_sens(s);
     return CFNMPC_OK;
 }
 
@@ -745,6 +765,7 @@ int cfnmpc_set_iterate(cfnmpc_solver* s, const double* x, const double* u, int o
     if (!s || !x || !u) return CFNMPC_EINVAL;
     DeviceGuard dg(s);
     s->lin_valid = false;
+    invalidate_sens(s);
     if (s->P.as_warm) HIP_TRY(hipMemsetAsync(s->P.wvalid, 0, sizeof(int) * (size_t)s->P.B, (hipStream_t)stream));
     int rc = put_field(s, x, on_device, s->P.N + 1, 13, 1, s->P.xit, (hipStream_t)stream);
     if (rc != CFNMPC_OK) return rc;
@@ -768,6 +789,7 @@ namespace {
 // chk (may be NULL): the SQP solve's convergence check, launched behind the step's kernels and BEFORE the host swaps the
 // iterate buffers (it reads both); the launches of the step itself are the same with or without it.
 int rti_step(cfnmpc_solver* s, hipStream_t st, bool reinit, const cfn::SqpArgs* chk) {
+    invalidate_sens(s);   // (until the step is through)
     hipEvent_t* e = nullptr;
     if (s->profiling && s->ev_used < EV_PER_STEP * MAX_PROFILED_STEPS) {   // bounded: later steps go untimed
         while (s->ev.size() < s->ev_used + EV_PER_STEP) {
@@ -822,6 +844,7 @@ int rti_step(cfnmpc_solver* s, hipStream_t st, bool reinit, const cfn::SqpArgs* 
             std::swap(s->P.uit, s->P.uitn);
             s->parity ^= 1;
             s->lin_valid = false;
+            s->sens_src = chk ? 2 : 1;
             return CFNMPC_OK;
         }
     }
@@ -842,6 +865,7 @@ int rti_step(cfnmpc_solver* s, hipStream_t st, bool reinit, const cfn::SqpArgs* 
         std::swap(s->P.uit, s->P.uitn);
         s->parity ^= 1;
         s->lin_valid = false;   // the iterate moved
+        s->sens_src = chk ? 2 : 1;   // (cfnmpc_eval_sens_x0: the QP of this step)
         return CFNMPC_OK;
     }
 #ifdef CFN_DEV   // overlapped preparation: development builds only (CFNMPC_OVERLAP=1); s->overlap is 0 in the product
@@ -1036,6 +1060,85 @@ int cfnmpc_get_stats(cfnmpc_solver* s, int* status, int* qp_iter, double* res, i
     if (status) HIP_TRY(hipMemcpyAsync(status, s->P.status, B * sizeof(int), kind, st));
     if (qp_iter) HIP_TRY(hipMemcpyAsync(qp_iter, s->P.iters, B * sizeof(int), kind, st));
     if (res) HIP_TRY(hipMemcpyAsync(res, s->P.res, B * sizeof(double), kind, st));
+    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
+
+// ---- solution sensitivities with respect to x0 ---------------------------------------------------
+int cfnmpc_eval_sens_x0(cfnmpc_solver* s, double act_tol, void* stream) {
+    if (!s || !std::isfinite(act_tol) || !(act_tol > 0.0)) return CFNMPC_EINVAL;
+    // partial condensing and the fused start solve (start_solve = 2) write no home blocks / gains / checkpoints
+    if (s->P.cond_N2 || s->P.fused == 1 || s->sens_src == 0) return CFNMPC_EINVAL;
+    DeviceGuard dg(s);
+    cfn::SensArgs& A = s->sens;
+    const size_t NW = (size_t)s->P.NW + 1, N = s->P.N, B = s->P.B;
+    if (!A.K) {
+        cfn::SensArgs a{};
+        int rc = dev_alloc(s, &a.mask, B * N * 4);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &a.list, B);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &a.cnt, 1);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &a.kst, B);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &a.K, NW * N * cfn::SZ_K);
+        if (rc != CFNMPC_OK) return rc;   // (what was allocated stays with the solver; the next call allocates again)
+        A = a;
+    }
+    s->sens_valid = false;
+    A.tol = act_tol;
+    cfn::launch_sens_eval(s->P, A, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    s->sens_valid = true;
+    return CFNMPC_OK;
+}
+
+int cfnmpc_get_sens_x0(cfnmpc_solver* s, int stage, int n_stages, double* du, double* dx, int on_device, void* stream) {
+    if (!s || !s->sens_valid) return CFNMPC_EINVAL;
+    const int N = s->P.N;
+    if (stage < 0 || n_stages < 1 || (long)stage + n_stages > N + 1 || (!du && !dx) || (du && stage + n_stages > N))
+        return CFNMPC_EINVAL;
+    DeviceGuard dg(s);
+    hipStream_t st = (hipStream_t)stream;
+    cfn::SensArgs A = s->sens;
+    A.status = s->sens_src == 2 ? s->sqp.status : s->P.status;
+    A.s0 = stage;
+    A.ns = n_stages;
+    const size_t B = s->P.B, nu = du ? (size_t)n_stages * 52 : 0, nx = dx ? (size_t)n_stages * 169 : 0;
+    if (!is_host(on_device)) {
+        A.du = du; A.dx = dx; A.b0 = 0; A.nb = (int)B;
+        cfn::launch_sens_fwd(s->P, A, st);
+        HIP_TRY(hipGetLastError());
+        return CFNMPC_OK;
+    }
+    // host arrays: rows in chunks of whole wavefronts through a staging buffer of at most 32 Mi doubles
+    const size_t per = nu + nx, cap_max = (size_t)1 << 25;
+    if (!s->sens_stage) {
+        const size_t want = std::min(B * (size_t)(N + 1) * 221, cap_max);
+        const int rc = dev_alloc(s, &s->sens_stage, want);
+        if (rc != CFNMPC_OK) return rc;
+        s->sens_stage_doubles = want;
+    }
+    size_t chunk = s->sens_stage_doubles / per;
+    chunk = chunk >= B ? B : (chunk & ~(size_t)3);   // (fewer than four rows: the buffer holds them all)
+    if (chunk == 0) return CFNMPC_ENOMEM;   // (unreachable: the buffer holds four rows of the longest range)
+    for (size_t b0 = 0; b0 < B; b0 += chunk) {
+        const size_t nb = std::min(chunk, B - b0);
+        A.b0 = (int)b0; A.nb = (int)nb;
+        A.du = du ? s->sens_stage : nullptr;
+        A.dx = dx ? s->sens_stage + nb * nu : nullptr;
+        cfn::launch_sens_fwd(s->P, A, st);
+        HIP_TRY(hipGetLastError());
+        if (du) HIP_TRY(hipMemcpyAsync(du + b0 * nu, A.du, nb * nu * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (dx) HIP_TRY(hipMemcpyAsync(dx + b0 * nx, A.dx, nb * nx * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
+
+int cfnmpc_get_sens_active(cfnmpc_solver* s, signed char* act, int on_device, void* stream) {
+    if (!s || !act || !s->sens_valid) return CFNMPC_EINVAL;
+    DeviceGuard dg(s);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)s->P.B * s->P.N * 4;
+    HIP_TRY(hipMemcpyAsync(act, s->sens.mask, n, is_host(on_device) ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
     if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
     return CFNMPC_OK;
 }
@@ -1247,6 +1350,7 @@ int cfnmpc_debug_start_factor(cfnmpc_solver* s, int mode, int reps, double* ms, 
     if (s->P.cond_N2 || !s->P.v4b) return CFNMPC_EINVAL;
     if (mode == 2 && s->P.mpar) return CFNMPC_EINVAL;   // (k_linfactor integrates with the folded model constants)
     DeviceGuard dg(s);
+    invalidate_sens(s);   // (rewrites KR / Pchk: they no longer belong to the last QP)
     hipStream_t st = (hipStream_t)stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (hipEventCreate(&e0) != hipSuccess) return CFNMPC_EHIP;
@@ -1339,6 +1443,7 @@ int cfnmpc_debug_solve_part(cfnmpc_solver* s, int part, int flags, void* stream)
 int cfnmpc_debug_linearise(cfnmpc_solver* s, void* stream) {
     if (!s) return CFNMPC_EINVAL;
     DeviceGuard dg(s);
+    invalidate_sens(s);   // (rewrites AR / BR / b: they no longer belong to the last QP)
     cfn::launch_linearise(s->P, s->chunks_all, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     s->lin_valid = true;

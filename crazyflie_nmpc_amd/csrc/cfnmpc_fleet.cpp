@@ -53,6 +53,8 @@ struct Bucket {
     int* d_idx = nullptr;
     double* d_rows = nullptr;   // [count][N*17] staging in bucket order (device-pointer calls)
     int* d_ints = nullptr;      // [2][count]
+    double* d_sens = nullptr;   // [count][rows of cfnmpc_get_sens_x0] staging of device-pointer sensitivity reads (grown on demand)
+    size_t n_sens = 0;
     hipStream_t st = nullptr;
     hipEvent_t done = nullptr;
 };
@@ -176,6 +178,7 @@ int cfnmpc_fleet_free(cfnmpc_fleet* f) {
         if (b.d_idx) (void)hipFree(b.d_idx);
         if (b.d_rows) (void)hipFree(b.d_rows);
         if (b.d_ints) (void)hipFree(b.d_ints);
+        if (b.d_sens) (void)hipFree(b.d_sens);
         if (b.st) (void)hipStreamDestroy(b.st);
         if (b.done) (void)hipEventDestroy(b.done);
     }
@@ -464,6 +467,53 @@ int cfnmpc_fleet_get_sqp_stats(cfnmpc_fleet* f, int* status, int* sqp_iter, doub
         if (status) rows<int, false>(b.d_ints, status, b.d_idx, b.count, 1, 1, st);
         if (sqp_iter) rows<int, false>(b.d_ints + b.count, sqp_iter, b.d_idx, b.count, 1, 1, st);
         if (res) rows<double, false>(b.d_rows, res, b.d_idx, b.count, 3, 3, st);
+        return (int)CFNMPC_OK;
+    });
+}
+
+// ---- solution sensitivities with respect to x0 (include/cfnmpc.h: cfnmpc_eval_sens_x0) --------------
+int cfnmpc_fleet_eval_sens_x0(cfnmpc_fleet* f, double act_tol, void* stream) {
+    if (!f) return CFNMPC_EINVAL;
+    FleetDevice fd(f);
+    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) { return cfnmpc_eval_sens_x0(b.s, act_tol, st); });
+}
+
+// rows in the fleet's vehicle order: du [B][n_stages][4][13], dx [B][n_stages][13][13]; the range is limited by the shortest
+// horizon (dx up to stage Nmin, du below it)
+int cfnmpc_fleet_get_sens_x0(cfnmpc_fleet* f, int stage, int n_stages, double* du, double* dx, int on_device, void* stream) {
+    if (!f || stage < 0 || n_stages < 1 || (!du && !dx) || (long)stage + n_stages > f->Nmin + 1 ||
+        (du && stage + n_stages > f->Nmin))
+        return CFNMPC_EINVAL;
+    FleetDevice fd(f);
+    const size_t wu = du ? (size_t)n_stages * 52 : 0, wx = dx ? (size_t)n_stages * 169 : 0;
+    if (on_device == CFNMPC_ON_HOST || on_device == CFNMPC_ON_HOST_ASYNC) {   // (host arrays: synchronous)
+        for (Bucket& b : f->bk) {
+            f->h_rows.resize((size_t)b.count * (wu + wx));
+            double* hu = du ? f->h_rows.data() : nullptr;
+            double* hx = dx ? f->h_rows.data() + (size_t)b.count * wu : nullptr;
+            RC_TRY(cfnmpc_get_sens_x0(b.s, stage, n_stages, hu, hx, CFNMPC_ON_HOST, stream));
+            for (int r = 0; r < b.count; r++) {
+                if (du) std::copy_n(hu + (size_t)r * wu, wu, du + (size_t)b.idx[r] * wu);
+                if (dx) std::copy_n(hx + (size_t)r * wx, wx, dx + (size_t)b.idx[r] * wx);
+            }
+        }
+        return CFNMPC_OK;
+    }
+    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) {
+        const size_t need = (size_t)b.count * (wu + wx);
+        if (b.n_sens < need) {
+            HIP_TRY(hipStreamSynchronize(st));   // (an earlier read may still use the old buffer)
+            if (b.d_sens) (void)hipFree(b.d_sens);
+            b.d_sens = nullptr;
+            b.n_sens = 0;
+            if (hipMalloc((void**)&b.d_sens, need * sizeof(double)) != hipSuccess) return (int)CFNMPC_ENOMEM;
+            b.n_sens = need;
+        }
+        double* su = du ? b.d_sens : nullptr;
+        double* sx = dx ? b.d_sens + (size_t)b.count * wu : nullptr;
+        RC_TRY(cfnmpc_get_sens_x0(b.s, stage, n_stages, su, sx, 1, st));
+        if (du) rows<double, false>(su, du, b.d_idx, b.count, (int)wu, (long)wu, st);
+        if (dx) rows<double, false>(sx, dx, b.d_idx, b.count, (int)wx, (long)wx, st);
         return (int)CFNMPC_OK;
     });
 }

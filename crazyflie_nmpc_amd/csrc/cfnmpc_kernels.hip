@@ -3684,3 +3684,5 @@ void launch_init_iterate(const Params& P, int mode, hipStream_t st) {
 }
 
 }  // namespace cfn
+
+#include "cfnmpc_sens.hpp"

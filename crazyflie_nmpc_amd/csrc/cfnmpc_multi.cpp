@@ -371,4 +371,34 @@ int cfnmpc_multi_get_stats(cfnmpc_multi* m, int* status, int* qp_iter, double* r
     return sync_all(m);
 }
 
+// ---- solution sensitivities with respect to x0 (host arrays over the whole fleet, caller's order; synchronous) ---------------
+int cfnmpc_multi_eval_sens_x0(cfnmpc_multi* m, double act_tol) {
+    if (!m) return CFNMPC_EINVAL;
+    for (Shard& s : m->sh) RC_TRY_SYNC(m, m->mixed ? cfnmpc_fleet_eval_sens_x0(s.f, act_tol, s.st) : cfnmpc_eval_sens_x0(s.s, act_tol, s.st));
+    return sync_all(m);
+}
+
+int cfnmpc_multi_get_sens_x0(cfnmpc_multi* m, int stage, int n_stages, double* du, double* dx) {
+    const int Nlim = m ? (m->mixed ? m->Nmin : m->N) : 0;
+    if (!m || stage < 0 || n_stages < 1 || (!du && !dx) || (long)stage + n_stages > Nlim + 1 || (du && stage + n_stages > Nlim))
+        return CFNMPC_EINVAL;
+    const size_t wu = du ? (size_t)n_stages * 52 : 0, wx = dx ? (size_t)n_stages * 169 : 0;
+    if (m->mixed) {
+        for (Shard& s : m->sh) {
+            const size_t n = s.idx.size();
+            s.h.resize(n * (wu + wx));
+            double* hu = du ? s.h.data() : nullptr;
+            double* hx = dx ? s.h.data() + n * wu : nullptr;
+            RC_TRY(cfnmpc_fleet_get_sens_x0(s.f, stage, n_stages, hu, hx, CFNMPC_ON_HOST, s.st));
+            if (du) from_shard(s, hu, du, wu);
+            if (dx) from_shard(s, hx, dx, wx);
+        }
+        return CFNMPC_OK;
+    }
+    for (Shard& s : m->sh)
+        RC_TRY_SYNC(m, cfnmpc_get_sens_x0(s.s, stage, n_stages, du ? du + (size_t)s.lo * wu : nullptr, dx ? dx + (size_t)s.lo * wx : nullptr,
+                                          CFNMPC_ON_HOST_ASYNC, s.st));
+    return sync_all(m);
+}
+
 }  // extern "C"

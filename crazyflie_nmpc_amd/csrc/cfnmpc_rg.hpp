@@ -312,6 +312,8 @@ __device__ __forceinline__ void load_stage(const Params& P, const Lane& t, const
 constexpr int WT_ROW = 14, WT_TILE = 204;
 static_assert(WT_TILE >= 13 * WT_ROW && WT_TILE % 2 == 0, "W transpose tile");
 // One stage of the augmented backward recursion.
+// (cfnmpc_sens.hpp: sens_stage repeats steps (1) - (8) without the affine row for the masked sensitivity sweep -- a change to
+// the arithmetic, the LDS transpose or the DPP wait-state discipline here belongs there too.)
 //   Pa[13]: lanes 0..12 row i of P_{k+1}; lane 13 the affine row p_{k+1}' -- on exit the same for
 //           stage k.  ABSOLUTE: start solve with the QP's own affine terms (q_k, b_k, r_k);
 //   otherwise R^ and g come from the interior-point state (homogeneous Newton system).

@@ -255,6 +255,24 @@ struct SqpArgs {
 };
 // after the step of iteration A.j, BEFORE the host swaps the iterate buffers (reads P.xit / P.uit and P.xitn / P.uitn)
 void launch_sqp_check(const Params& P, const SqpArgs& A, hipStream_t st);
+// solution sensitivities with respect to x0 (cfnmpc_eval_sens_x0 / cfnmpc_get_sens_x0; kernels: cfnmpc_sens.hpp, DESIGN.md
+// section 5.14): buffers owned by the solver, allocated at its first evaluation (not part of Params: no RTI kernel sees them)
+struct SensArgs {
+    signed char* mask;   // [B][N][4] active set (0 free, -1 lower, +1 upper); a stage's four bytes are one aligned word
+    int* list;           // [B] rows with at least one active input (first *cnt entries, any order)
+    int* cnt;            // [1] length of the list
+    int* kst;            // [B] stages [0, kst) of the row use the masked gains K (0: the home gains throughout)
+    double* K;           // masked gains, KR's layout (N x SZ_K per block); written for the stages [0, kst) of listed rows
+    double tol;          // activity tolerance
+    // forward propagation (k_sens_fwd): rows [b0, b0 + nb), stages [s0, s0 + ns) of the outputs
+    const int* status;   // [B] status of the last solve (4: NaN outputs)
+    double *du, *dx;     // [nb][ns][4][13], [nb][ns][13][13] (either may be NULL)
+    int s0, ns, b0, nb;
+};
+// active set, work list and masked backward sweep of the listed rows (clears *cnt first)
+void launch_sens_eval(const Params& P, const SensArgs& A, hipStream_t st);
+// forward propagation for the rows [A.b0, A.b0 + A.nb) into A.du / A.dx
+void launch_sens_fwd(const Params& P, const SensArgs& A, hipStream_t st);
 // output stage of the reference node for the fleet (cmd_vel [B][4] doubles, motvel [B][4] int32 or NULL)
 void launch_postproc(const Params& P, double* cmd_vel, int* motvel, hipStream_t st);
 

@@ -168,6 +168,18 @@ class MixedHorizonFleet:
         _check(self._L.cfnmpc_fleet_get_u(self._h, int(stage), p, dev, st), "cfnmpc_fleet_get_u")
         return out
 
+    def eval_sens_x0(self, act_tol=1e-6, stream=None):
+        """cfnmpc_fleet_eval_sens_x0: sensitivities w.r.t. x0 of every bucket's last QP (BatchSolver.eval_sens_x0)"""
+        _check(self._L.cfnmpc_fleet_eval_sens_x0(self._h, float(act_tol), _launch_stream(stream, self._device)),
+               "cfnmpc_fleet_eval_sens_x0")
+
+    def sens_x0(self, stage=0, n_stages=None, out_u=None, out_x=None):
+        """-> (du, dx) in the fleet's vehicle order, shapes as BatchSolver.sens_x0; stages up to the shortest horizon Nmin
+        (du is None if the range includes stage Nmin)"""
+        from .solver import sens_x0_call
+        return sens_x0_call(self, self.Nmin, self._L.cfnmpc_fleet_get_sens_x0, "cfnmpc_fleet_get_sens_x0", stage, n_stages,
+                            out_u, out_x)
+
     def get_x(self, stage, out=None):
         if out is None:
             out = np.empty((self.B, NX))

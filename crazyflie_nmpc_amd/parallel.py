@@ -167,6 +167,23 @@ class MultiGpuFleet:
     def sync(self):
         self._check(self._L.cfnmpc_multi_sync(self._h), "cfnmpc_multi_sync")
 
+    def eval_sens_x0(self, act_tol=1e-6):
+        """cfnmpc_multi_eval_sens_x0: sensitivities w.r.t. x0 of every shard's last QP (synchronous)"""
+        self._check(self._L.cfnmpc_multi_eval_sens_x0(self._h, float(act_tol)), "cfnmpc_multi_eval_sens_x0")
+
+    def sens_x0(self, stage=0, n_stages=None):
+        """-> (du, dx) host arrays over the whole fleet in the caller's order, shapes as BatchSolver.sens_x0 (mixed horizons:
+        stages up to the shortest horizon; du is None if the range includes the last stage)"""
+        C = self._C
+        Nlim = int(self.horizons.min()) if self.mixed else self.N
+        ns = 1 if n_stages is None else int(n_stages)
+        want_u = int(stage) + ns <= Nlim
+        dx = np.empty((self.B, 13, 13) if n_stages is None else (self.B, ns, 13, 13))
+        du = (np.empty((self.B, 4, 13) if n_stages is None else (self.B, ns, 4, 13))) if want_u else None
+        self._check(self._L.cfnmpc_multi_get_sens_x0(self._h, int(stage), ns, None if du is None else du.ctypes.data_as(C.c_void_p),
+                                                     dx.ctypes.data_as(C.c_void_p)), "cfnmpc_multi_get_sens_x0")
+        return du, dx
+
     def get_u(self, stage):
         u = np.empty((self.B, 4))
         self._check(self._L.cfnmpc_multi_get_u(self._h, int(stage), u.ctypes.data_as(self._C.c_void_p)), "cfnmpc_multi_get_u")

@@ -91,6 +91,11 @@ def _launch_stream(stream, device=None):
     return C.c_void_p(0)
 
 
+def _torch_like(a, shape):
+    import torch
+    return torch.empty(shape, dtype=a.dtype, device=a.device)
+
+
 def _arg(a, shape, dtype=np.float64, device=None):
     """-> (pointer, on_device, stream, keepalive).  Host arrays travel on the stream the launch calls use (torch's CURRENT
     stream on the solver's device, _launch_stream): inside `with torch.cuda.stream(s):` a numpy getter then waits for the
@@ -106,6 +111,29 @@ def _arg(a, shape, dtype=np.float64, device=None):
         raise ValueError(f"expected shape {shape}, got {arr.shape}")
     return arr.ctypes.data_as(C.c_void_p), 0, _launch_stream(None, device), arr
 
+
+
+def sens_x0_call(obj, N, fn, what, stage, n_stages, out_u, out_x):
+    """shared body of BatchSolver.sens_x0 / MixedHorizonFleet.sens_x0 (fn: the C getter; N: the last stage of the range)"""
+    ns = 1 if n_stages is None else int(n_stages)
+    stage = int(stage)
+    want_u = stage + ns <= N
+    su = (obj.B, 4, NX) if n_stages is None else (obj.B, ns, 4, NX)
+    sx = (obj.B, NX, NX) if n_stages is None else (obj.B, ns, NX, NX)
+    if out_x is None:
+        out_x = _torch_like(out_u, sx) if (out_u is not None and _is_torch(out_u)) else np.empty(sx)
+    if want_u and out_u is None:
+        out_u = _torch_like(out_x, su) if _is_torch(out_x) else np.empty(su)
+    px, dev, st, _kx = _arg(out_x, sx, device=obj._device)
+    pu = C.c_void_p(0)
+    if want_u:
+        pu, devu, _s, _ku = _arg(out_u, su, device=obj._device)
+        if devu != dev:
+            raise ValueError("out_u and out_x must both be host arrays or both device tensors")
+    else:
+        out_u = None
+    _check(fn(obj._h, stage, ns, pu, px, dev, st), what)
+    return out_u, out_x
 
 class BatchSolver:
     def __init__(self, batch: int, opts: Opts | None = None, **kw):
@@ -238,6 +266,25 @@ class BatchSolver:
         _check(self._L.cfnmpc_get_sqp_stats(self._h, st.ctypes.data_as(C.c_void_p), it.ctypes.data_as(C.c_void_p),
                                             rs.ctypes.data_as(C.c_void_p), 0, _launch_stream(None, self._device)), "cfnmpc_get_sqp_stats")
         return st, it, rs
+
+    def eval_sens_x0(self, act_tol=1e-6, stream=None):
+        """Sensitivities of the last QP's solution with respect to x0 (include/cfnmpc.h: cfnmpc_eval_sens_x0): the active set
+        of the current iterate (inputs within act_tol of a bound) and the masked Riccati gains.  Read with sens_x0()."""
+        _check(self._L.cfnmpc_eval_sens_x0(self._h, float(act_tol), _launch_stream(stream, self._device)), "cfnmpc_eval_sens_x0")
+
+    def sens_x0(self, stage=0, n_stages=None, out_u=None, out_x=None):
+        """-> (du, dx): du_k/dx0 and dx_k/dx0 in the public state order, after eval_sens_x0.  n_stages = None: stage `stage`
+        alone, du [B, 4, 13] and dx [B, 13, 13]; else stages [stage, stage + n_stages), du [B, n_stages, 4, 13] and
+        dx [B, n_stages, 13, 13].  du is None if the range includes stage N.  out_u / out_x: numpy arrays or torch device
+        tensors of those shapes (device tensors are filled on torch's current stream)."""
+        return sens_x0_call(self, self.N, self._L.cfnmpc_get_sens_x0, "cfnmpc_get_sens_x0", stage, n_stages, out_u, out_x)
+
+    def sens_active(self):
+        """-> int8 [B, N, 4]: the active set of the last eval_sens_x0 (0 free, -1 lower bound, +1 upper bound)"""
+        a = np.empty((self.B, self.N, NU), dtype=np.int8)
+        _check(self._L.cfnmpc_get_sens_active(self._h, a.ctypes.data_as(C.c_void_p), 0, _launch_stream(None, self._device)),
+               "cfnmpc_get_sens_active")
+        return a
 
     def step_host(self, x0, yref, yref_e, stream=None):
         """cfnmpc_step_host: host arrays in (x0 [B,13], yref [B,N,17], yref_e [B,13]), one RTI step,

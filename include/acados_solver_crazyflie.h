@@ -80,6 +80,16 @@ void ocp_nlp_solver_opts_set(ocp_nlp_config *config, void *opts_, const char *fi
 void ocp_nlp_out_get(ocp_nlp_config *config, ocp_nlp_dims *dims, ocp_nlp_out *out, int stage,
                      const char *field, void *value);
 
+/* ---- solution sensitivities with respect to x0 (acados' parametric sensitivities; include/cfnmpc.h:
+ *      cfnmpc_eval_sens_x0).  ocp_nlp_out_create makes an out to receive them (free with ocp_nlp_out_destroy);
+ *      ocp_nlp_eval_param_sens(solver, "ex", 0, index, sens_out), 0 <= index < 13, leaves column `index` of dx_k/dx0
+ *      (k = 0..N) and du_k/dx0 (k < N) of the last acados_solve()'s QP in it, read with ocp_nlp_out_get(.., sens_out, k,
+ *      "x" | "u", v).  The first call after a solve evaluates every column (active inputs: within 1e-6 of a bound); the
+ *      others only copy.  Anything invalid fills sens_out with NaN.  nlp_out and other outs read as before. */
+ocp_nlp_out *ocp_nlp_out_create(ocp_nlp_config *config, ocp_nlp_dims *dims);
+void ocp_nlp_out_destroy(void *out);
+void ocp_nlp_eval_param_sens(ocp_nlp_solver *solver, char *field, int stage, int index, ocp_nlp_out *sens_out);
+
 /* ---- extension (not in acados): choose the initial iterate after acados_create():
  *      0 = acados default (x_k = [0,0,0,1,0..], u_k = 0), 1 = x_k = current lbx, u_k = hover. */
 int acados_cfnmpc_init_iterate(int mode);

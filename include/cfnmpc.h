@@ -341,6 +341,29 @@ int cfnmpc_get_x(cfnmpc_solver *s, int stage, double *x /*[B][13]*/, int on_devi
  * NLP results: cfnmpc_get_sqp_stats). */
 int cfnmpc_get_stats(cfnmpc_solver *s, int *status /*[B]*/, int *qp_iter /*[B]*/, double *res /*[B]*/, int on_device, void *stream);
 
+/* Solution sensitivities with respect to the initial state (acados' ocp_nlp_eval_param_sens with field "ex", stage 0; DESIGN.md
+ * section 5.14): the Jacobians du_k/dx0 [4][13] and dx_k/dx0 [13][13] of the last QP's solution -- the QP of the latest
+ * cfnmpc_solve step or of the last iteration of cfnmpc_solve_sqp -- with its active set held fixed.  An input of the current
+ * iterate within act_tol of its lower or upper bound is active (lb == ub: always); an active input has a zero derivative row.
+ * A weakly active input (at its bound with a zero multiplier) has no derivative: the result is the one for the set detected.
+ * Both axes are in the public state order (xq yq zq qw qx qy qz vbx vby vbz wx wy wz).  A row whose status is 4
+ * (cfnmpc_get_stats after a solve, cfnmpc_get_sqp_stats after cfnmpc_solve_sqp) gets NaN in every entry.
+ *   cfnmpc_eval_sens_x0: the active set and the gains of the masked Riccati recursion, on `stream`.  Writes nothing that a
+ *     solve, getter or option reads; its buffers are allocated at the first call (cfnmpc_workspace_bytes counts them from
+ *     then on).  CFNMPC_EINVAL: act_tol not finite or <= 0; no solve yet, or set_weights / set_cost_scaling / set_box /
+ *     set_box_stages / set_model_params / set_erk_steps / set_iterate / init_iterate since the last one; cond_N2 > 0 or
+ *     start_solve = 2 (no stored blocks).
+ *   cfnmpc_get_sens_x0: stages [stage, stage + n_stages) of one forward sweep from stage 0, du [B][n_stages][4][13] and dx
+ *     [B][n_stages][13][13] (either may be NULL, not both; du must be NULL if the range includes stage N;
+ *     stage + n_stages <= N + 1).  (0, 1) is the feedback gain; (0, N + 1) the whole trajectory.  CFNMPC_EINVAL without an
+ *     evaluation since the last solve or data change.  Host arrays go through one staging buffer per solver: with
+ *     CFNMPC_ON_HOST_ASYNC, calls that overlap must be made on the same stream.
+ *   cfnmpc_get_sens_active: the active set the evaluation used, act [B][N][4]: 0 free, -1 lower, +1 upper. */
+int cfnmpc_eval_sens_x0(cfnmpc_solver *s, double act_tol, void *stream);
+int cfnmpc_get_sens_x0(cfnmpc_solver *s, int stage, int n_stages, double *du /*[B][n_stages][4][13] or NULL*/,
+                       double *dx /*[B][n_stages][13][13] or NULL*/, int on_device, void *stream);
+int cfnmpc_get_sens_active(cfnmpc_solver *s, signed char *act /*[B][N][4]*/, int on_device, void *stream);
+
 /* Output stage of the reference node for the whole fleet, on the device (NMPC::iteration,
  * acados_mpc.cpp:619-670): from the current iterate (u0 = inputs of stage 0, u1 = stage 1, x4 =
  * state of stage 4) it forms what the node publishes per vehicle,
@@ -458,6 +481,12 @@ int cfnmpc_fleet_solve_sqp(cfnmpc_fleet *f, int max_iter, double tol_step, doubl
                            void *stream);
 /* cfnmpc_get_sqp_stats in the fleet's vehicle order: status [B], sqp_iter [B], res [B][3] */
 int cfnmpc_fleet_get_sqp_stats(cfnmpc_fleet *f, int *status, int *sqp_iter, double *res, int on_device, void *stream);
+/* Solution sensitivities w.r.t. x0 of every bucket's last QP (cfnmpc_eval_sens_x0), rows in the fleet's vehicle order.  The range
+ * is limited by the shortest horizon: dx up to stage Nmin, du below it.  Host arrays (on_device 0 or 2) are filled
+ * synchronously. */
+int cfnmpc_fleet_eval_sens_x0(cfnmpc_fleet *f, double act_tol, void *stream);
+int cfnmpc_fleet_get_sens_x0(cfnmpc_fleet *f, int stage, int n_stages, double *du /*[B][n_stages][4][13] or NULL*/,
+                             double *dx /*[B][n_stages][13][13] or NULL*/, int on_device, void *stream);
 
 /* ---- one fleet across several GPUs of a node, from ONE process --------------------------------
  * The reference owns one vehicle per process (acados_mpc.cpp:76-82); instances are independent, so a
@@ -505,6 +534,10 @@ int cfnmpc_multi_set_erk_steps(cfnmpc_multi *m, int num_steps);
 int cfnmpc_multi_set_cost_scaling(cfnmpc_multi *m, double stage_scale, double terminal_scale);
 /* cfnmpc_set_model_params for every shard: HOST array [B][CFNMPC_NP] of the whole fleet (NULL: nominal) */
 int cfnmpc_multi_set_model_params(cfnmpc_multi *m, const double *p);
+/* Solution sensitivities w.r.t. x0 over the whole fleet (cfnmpc_eval_sens_x0 per shard): host arrays in the caller's order,
+ * synchronous; for cfnmpc_multi_create_horizons the range is limited by the shortest horizon, as for a fleet. */
+int cfnmpc_multi_eval_sens_x0(cfnmpc_multi *m, double act_tol);
+int cfnmpc_multi_get_sens_x0(cfnmpc_multi *m, int stage, int n_stages, double *du /*host or NULL*/, double *dx /*host or NULL*/);
 
 const char *cfnmpc_version(void);
 
