@@ -68,6 +68,10 @@ struct cfnmpc_solver {
     // device block of derived constants P.mpar points to while set (allocated at the first call, kept for later ones)
     std::vector<double> mp_rows;
     double* mpar_buf;
+    // per-instance cost weights (cfnmpc_set_weights_batch): the caller's unscaled rows [B][17] / [B][13] while set (empty: the
+    // uniform W_set / WN_set) and the device table P.wtab points to while set (allocated at the first call, kept for later ones)
+    std::vector<double> w_rows, wn_rows;
+    double* wtab_buf;
     // solution sensitivities (cfnmpc_eval_sens_x0): what the last QP was (0: none, or its data changed since; 1: an RTI step;
     // 2: an SQP iteration, whose status is sqp.status), whether an evaluation belongs to it, the buffers (allocated at the
     // first evaluation) and the staging buffer of host reads
@@ -569,14 +573,112 @@ static void invalidate_graphs(cfnmpc_solver* s) { s->gvalid[0] = s->gvalid[1] = 
 // the QP's data changed since the last solve: no sensitivities until the next one
 static void invalidate_sens(cfnmpc_solver* s) { s->sens_src = 0; s->sens_valid = false; }
 
+// Per-instance weight table (Params.wtab, layout: cfnmpc_ws.hpp) from the rows in force, scaling applied: uploaded in place on
+// `st` and complete on return, so that a captured step graph (which holds the pointer) replays with the new values.
+static int upload_weight_rows(cfnmpc_solver* s, hipStream_t st) {
+    const cfn::Params& P = s->P;
+    const size_t B = P.B, S = ((size_t)P.NW + 1) * 4;
+    std::vector<double> tab(S * 32, 0.0);
+    for (size_t i = 0; i < S; i++) {   // (padding rows and the spare block: the uniform weights)
+        const double* w = i < B ? s->w_rows.data() + i * 17 : s->W_set;
+        const double* wn = i < B ? s->wn_rows.data() + i * 13 : s->WN_set;
+        double* r = tab.data() + i * 32;
+        for (int j = 0; j < 13; j++) r[j] = s->stage_scale * w[cfn::ext_of(j)];
+        for (int c = 0; c < 4; c++) r[13 + c] = s->stage_scale * w[13 + c];
+        for (int j = 0; j < 13; j++) r[17 + j] = s->terminal_scale * wn[cfn::ext_of(j)];
+    }
+    HIP_TRY(hipMemcpyAsync(s->wtab_buf, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
+
 int cfnmpc_set_weights(cfnmpc_solver* s, const double* W, const double* WN) {
     if (!s || (!W && !WN)) return CFNMPC_EINVAL;
     if (!weights_ok(W, WN)) return CFNMPC_EINVAL;   // validated as a whole before anything is copied
+    // rows in force: what goes into every row obeys the rows' own rule (finite; weights_ok lets +inf through)
+    if (s->P.wtab && !cfn::weight_rows_ok(W, WN, 1)) return CFNMPC_EINVAL;
     if (W) for (int i = 0; i < 17; i++) s->P.W[i] = s->stage_scale * (s->W_set[i] = W[i]);
     if (WN) for (int i = 0; i < 13; i++) s->P.WN[i] = s->terminal_scale * (s->WN_set[i] = WN[i]);
     invalidate_graphs(s);
     invalidate_sens(s);
+    if (s->P.wtab) {   // "for all instances": each part given replaces that part in every row
+        DeviceGuard dg(s);
+        for (size_t i = 0; i < (size_t)s->P.B; i++) {
+            if (W) std::copy_n(W, 17, s->w_rows.data() + i * 17);
+            if (WN) std::copy_n(WN, 13, s->wn_rows.data() + i * 13);
+        }
+        return upload_weight_rows(s, nullptr);
+    }
     return CFNMPC_OK;  // kernel arguments: take effect at the next cfnmpc_solve
+}
+
+int cfnmpc_set_weights_batch(cfnmpc_solver* s, const double* W, const double* WN, int on_device, void* stream) {
+    if (!s) return CFNMPC_EINVAL;
+    DeviceGuard dg(s);
+    cfn::Params& P = s->P;
+    // not covered: the fused start solve (k_linfactor's weight table is shared by the four rows of a wavefront), partial
+    // condensing (one weight vector per workgroup), the development build's overlapped preparation
+    if (P.fused || P.cond_N2 || s->overlap) return CFNMPC_EINVAL;
+    if (!W && !WN) {   // back to the uniform weights (the kernel arguments)
+        if (P.wtab) { P.wtab = nullptr; invalidate_graphs(s); }
+        s->w_rows.clear(); s->wn_rows.clear();
+        invalidate_sens(s);
+        return CFNMPC_OK;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const size_t B = P.B;
+    std::vector<double> w, wn;
+    if (W) w.resize(B * 17);
+    if (WN) wn.resize(B * 13);
+    if (is_host(on_device)) {
+        if (W) std::copy_n(W, w.size(), w.data());
+        if (WN) std::copy_n(WN, wn.size(), wn.data());
+    } else {   // device rows: one copy to the host to validate them
+        if (W) HIP_TRY(hipMemcpyAsync(w.data(), W, w.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (WN) HIP_TRY(hipMemcpyAsync(wn.data(), WN, wn.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (!cfn::weight_rows_ok(W ? w.data() : nullptr, WN ? wn.data() : nullptr, B)) return CFNMPC_EINVAL;
+    if (!s->wtab_buf) {
+        const int rc = dev_alloc(s, &s->wtab_buf, ((size_t)P.NW + 1) * 4 * 32);
+        if (rc != CFNMPC_OK) return rc;
+    }
+    // a part not given keeps what every row has (the uniform values if no rows were set)
+    const bool had = !s->w_rows.empty();
+    std::vector<double> w_old = s->w_rows, wn_old = s->wn_rows;
+    if (!W && !had) { w.resize(B * 17); for (size_t i = 0; i < B; i++) std::copy_n(s->W_set, 17, w.data() + i * 17); }
+    if (!WN && !had) { wn.resize(B * 13); for (size_t i = 0; i < B; i++) std::copy_n(s->WN_set, 13, wn.data() + i * 13); }
+    if (W || !had) s->w_rows = std::move(w);
+    if (WN || !had) s->wn_rows = std::move(wn);
+    const int rc = upload_weight_rows(s, st);
+    if (rc != CFNMPC_OK) {   // (nothing in force changes: the kernels keep reading what they read before)
+        s->w_rows = std::move(w_old); s->wn_rows = std::move(wn_old);
+        return rc;
+    }
+    if (!P.wtab) { P.wtab = s->wtab_buf; invalidate_graphs(s); }   // other kernels from here on
+    invalidate_sens(s);
+    return CFNMPC_OK;
+}
+
+int cfnmpc_get_weights_batch(cfnmpc_solver* s, double* W, double* WN, int on_device, void* stream) {
+    if (!s || (!W && !WN)) return CFNMPC_EINVAL;
+    DeviceGuard dg(s);
+    const size_t B = s->P.B;
+    std::vector<double> w = s->w_rows, wn = s->wn_rows;
+    if (w.empty()) {
+        w.resize(B * 17); wn.resize(B * 13);
+        for (size_t i = 0; i < B; i++) { std::copy_n(s->W_set, 17, w.data() + i * 17); std::copy_n(s->WN_set, 13, wn.data() + i * 13); }
+    }
+    if (is_host(on_device)) {
+        if (W) std::copy_n(w.data(), w.size(), W);
+        if (WN) std::copy_n(wn.data(), wn.size(), WN);
+        return CFNMPC_OK;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (W) HIP_TRY(hipMemcpyAsync(W, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    if (WN) HIP_TRY(hipMemcpyAsync(WN, wn.data(), wn.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (the sources are host temporaries)
+    return CFNMPC_OK;
 }
 
 int cfnmpc_set_cost_scaling(cfnmpc_solver* s, double stage_scale, double terminal_scale) {
@@ -588,6 +690,10 @@ int cfnmpc_set_cost_scaling(cfnmpc_solver* s, double stage_scale, double termina
     for (int i = 0; i < 17; i++) s->P.W[i] = stage_scale * s->W_set[i];
     for (int i = 0; i < 13; i++) s->P.WN[i] = terminal_scale * s->WN_set[i];
     invalidate_graphs(s);
+    if (s->P.wtab) {   // rescales the rows in force
+        DeviceGuard dg(s);
+        return upload_weight_rows(s, nullptr);
+    }
     return CFNMPC_OK;
 }
 
@@ -1348,7 +1454,7 @@ int cfnmpc_debug_start_factor(cfnmpc_solver* s, int mode, int reps, double* ms, 
     // k_factor / k_linfactor address the home 4-vectors in the wave-blocked layout (Params.v4b): a partial-condensing solver
     // keeps them instance-major and never runs these kernels -- refuse instead of reading and writing in the wrong layout
     if (s->P.cond_N2 || !s->P.v4b) return CFNMPC_EINVAL;
-    if (mode == 2 && s->P.mpar) return CFNMPC_EINVAL;   // (k_linfactor integrates with the folded model constants)
+    if (mode == 2 && (s->P.mpar || s->P.wtab)) return CFNMPC_EINVAL;   // (k_linfactor: folded model constants, uniform weights)
     DeviceGuard dg(s);
     invalidate_sens(s);   // (rewrites KR / Pchk: they no longer belong to the last QP)
     hipStream_t st = (hipStream_t)stream;

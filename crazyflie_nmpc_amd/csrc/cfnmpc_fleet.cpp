@@ -286,6 +286,28 @@ int cfnmpc_fleet_set_model_params(cfnmpc_fleet* f, const double* p) {
     return CFNMPC_OK;
 }
 
+// per-instance cost weights: rows in the fleet's vehicle order -> each bucket's order.  Validated as a whole first, and a bucket
+// refuses rows only for options every bucket shares (start_solve 2 / 3, cond_N2), so the FIRST bucket refuses and nothing has
+// changed (as cfnmpc_fleet_set_model_params).
+int cfnmpc_fleet_set_weights_batch(cfnmpc_fleet* f, const double* W, const double* WN) {
+    if (!f) return CFNMPC_EINVAL;
+    if (!cfn::weight_rows_ok(W, WN, (size_t)f->B)) return CFNMPC_EINVAL;
+    FleetDevice fd(f);
+    std::vector<double> hw, hn;
+    for (Bucket& b : f->bk) {
+        if (W) {
+            hw.resize((size_t)b.count * 17);
+            for (int r = 0; r < b.count; r++) std::copy_n(W + (size_t)b.idx[r] * 17, 17, hw.data() + (size_t)r * 17);
+        }
+        if (WN) {
+            hn.resize((size_t)b.count * 13);
+            for (int r = 0; r < b.count; r++) std::copy_n(WN + (size_t)b.idx[r] * 13, 13, hn.data() + (size_t)r * 13);
+        }
+        RC_TRY(cfnmpc_set_weights_batch(b.s, W ? hw.data() : nullptr, WN ? hn.data() : nullptr, CFNMPC_ON_HOST, b.st));
+    }
+    return CFNMPC_OK;
+}
+
 int cfnmpc_fleet_set_box(cfnmpc_fleet* f, double u_min, double u_max) {
     if (!f || !(u_max > u_min)) return CFNMPC_EINVAL;
     for (Bucket& b : f->bk) RC_TRY(cfnmpc_set_box(b.s, u_min, u_max));

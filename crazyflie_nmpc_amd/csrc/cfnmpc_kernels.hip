@@ -515,10 +515,15 @@ __global__ __launch_bounds__(64) void k_linearise_clist(Params P, int which) {
 // row zero), else from the terminal cost.
 // klo / park / from_park: only the stages [klo, head) of the sweep, cost-to-go taken from / left in `park`
 // ([wave][13][64 lanes]) -- the stage-chunked hand-over experiment (k_factor_chunk); the defaults fold away.
+// WR_TABLE (the _w twins of the compacted kernels): `qtab` is the row's weight-table entry staged in LDS by qp_wave.
 // QTAB: diagonal weights through the LDS table of factor_stage (frees the ~34 registers of their hoisted selects);
 // DEEP: three rotating stage buffers -- the loads of stage k - 2 are issued before the arithmetic of stage k (the start
 // solve streams 1.75 KB per stage and wave from HBM; with two buffers its waves wait a quarter of their time).
-template <bool ABSOLUTE, bool QTAB = false, bool DEEP = false>
+__device__ __forceinline__ double lds_w(const double* wl, const Lane& t, const int off) {   // entry off + L of the staged row, 0 in lanes 13..15
+    const double v = wl[off + imin(t.L, 12)];
+    return t.L < 13 ? v : 0.0;
+}
+template <bool ABSOLUTE, bool QTAB = false, bool DEEP = false, bool WROW = false, int WR = WR_TEST>
 __device__ __forceinline__ bool sweep_factor(const Params& P, const Lane& t, const int head, const int chk,
                                              double* wt, double* sb, const int klo = 0, gdouble* park = nullptr,
                                              const bool from_park = false, const double* qtab = nullptr) {
@@ -528,12 +533,21 @@ __device__ __forceinline__ bool sweep_factor(const Params& P, const Lane& t, con
     } else if (ABSOLUTE || chk < 0) {
         const double xN = ABSOLUTE ? ld13(blk(P.xit, t, P.N + 1, P.N, SZ_V13), t) : 0.0;
         const double yN = ABSOLUTE ? ld13(blk(P.yref_e, t, 1, 0, SZ_V13), t) : 0.0;
-        double qv = 0.0;
-        SFOR(j, 0, 13, { if (t.L == j) qv = P.WN[ext_of(j)] * (xN - yN); });
-        SFOR(j, 0, 13, {
-            const double qj = bc<j>(qv);
-            Pa[j] = (t.L == j) ? P.WN[ext_of(j)] : ((ABSOLUTE && t.L == 13) ? qj : 0.0);
-        });
+        if constexpr (WR == WR_ARGS) {
+            double qv = 0.0;
+            SFOR(j, 0, 13, { if (t.L == j) qv = P.WN[ext_of(j)] * (xN - yN); });
+            SFOR(j, 0, 13, {
+                const double qj = bc<j>(qv);
+                Pa[j] = (t.L == j) ? P.WN[ext_of(j)] : ((ABSOLUTE && t.L == 13) ? qj : 0.0);
+            });
+        } else {
+            const double wn = WR == WR_TABLE ? lds_w(qtab, t, WT_QN) : lane_wn<WR>(P, t);   // terminal weight of this lane's row (0 in lanes 13..15)
+            const double qv = wn * (xN - yN);
+            SFOR(j, 0, 13, {
+                const double qj = bc<j>(qv);
+                Pa[j] = (t.L == j) ? wn : ((ABSOLUTE && t.L == 13) ? qj : 0.0);
+            });
+        }
     } else {
         const gdouble* pc = gm(P.Pchk) + ((size_t)t.wave * N_CHK + chk) * SZ_P;
         SFOR(j, 0, 13, {
@@ -543,8 +557,7 @@ __device__ __forceinline__ bool sweep_factor(const Params& P, const Lane& t, con
     }
     bool ok = true;
     // per-lane constants: state weight of this lane's row, indicator of the affine row
-    double wq = 0.0;
-    SFOR(j, 0, 13, { if (t.L == j) wq = P.W[ext_of(j)]; });
+    const double wq = WR == WR_TABLE ? lds_w(qtab, t, 0) : lane_wq<WR>(P, t);
     const double is13 = t.L == 13 ? 1.0 : 0.0;
     auto after = [&](int k) {
         if (ABSOLUTE) {
@@ -565,15 +578,15 @@ __device__ __forceinline__ bool sweep_factor(const Params& P, const Lane& t, con
         int k = head - 1;
         while (k >= klo) {
             load_stage<ABSOLUTE>(P, t, imax(k - 2, 0), wq, b2);
-            ok = factor_stage<ABSOLUTE, false, false, QTAB>(P, t, k, Pa, b0, wq, is13, wt, sb, true, qtab) && ok;
+            ok = factor_stage<ABSOLUTE, false, false, QTAB, WROW>(P, t, k, Pa, b0, wq, is13, wt, sb, true, qtab) && ok;
             after(k);
             if (--k < klo) break;
             load_stage<ABSOLUTE>(P, t, imax(k - 2, 0), wq, b0);
-            ok = factor_stage<ABSOLUTE, false, false, QTAB>(P, t, k, Pa, b1, wq, is13, wt, sb, true, qtab) && ok;
+            ok = factor_stage<ABSOLUTE, false, false, QTAB, WROW>(P, t, k, Pa, b1, wq, is13, wt, sb, true, qtab) && ok;
             after(k);
             if (--k < klo) break;
             load_stage<ABSOLUTE>(P, t, imax(k - 2, 0), wq, b1);
-            ok = factor_stage<ABSOLUTE, false, false, QTAB>(P, t, k, Pa, b2, wq, is13, wt, sb, true, qtab) && ok;
+            ok = factor_stage<ABSOLUTE, false, false, QTAB, WROW>(P, t, k, Pa, b2, wq, is13, wt, sb, true, qtab) && ok;
             after(k);
             --k;
         }
@@ -585,12 +598,12 @@ __device__ __forceinline__ bool sweep_factor(const Params& P, const Lane& t, con
     int k = head - 1;
     while (k >= klo) {
         load_stage<ABSOLUTE>(P, t, imax(k - 1, 0), wq, bufB);
-        ok = factor_stage<ABSOLUTE, false, false, QTAB>(P, t, k, Pa, bufA, wq, is13, wt, sb, true, qtab) && ok;
+        ok = factor_stage<ABSOLUTE, false, false, QTAB, WROW>(P, t, k, Pa, bufA, wq, is13, wt, sb, true, qtab) && ok;
         after(k);
         k--;
         if (k < klo) break;
         load_stage<ABSOLUTE>(P, t, imax(k - 1, 0), wq, bufA);
-        ok = factor_stage<ABSOLUTE, false, false, QTAB>(P, t, k, Pa, bufB, wq, is13, wt, sb, true, qtab) && ok;
+        ok = factor_stage<ABSOLUTE, false, false, QTAB, WROW>(P, t, k, Pa, bufB, wq, is13, wt, sb, true, qtab) && ok;
         after(k);
         k--;
     }
@@ -803,7 +816,7 @@ __device__ __forceinline__ int as_restart_mono(int jm, int head, int sh) {   // 
     const int jr = (((jm >> sh) + 1) << sh) - 1;
     return (jr + 1 < head && ((jr + 1) >> sh) < AS_PSAVE) ? jr : head - 1;
 }
-template <bool QT = false>
+template <bool QT = false, int WR = WR_TEST>
 __device__ __forceinline__ bool sweep_factor_as(const Params& P, const Lane& t, const int head, const int chk,
                                                 const int kstart, double* wt, double* sb, const double* qtab = nullptr) {
     const int sh = as_pg_shift(head);
@@ -812,7 +825,12 @@ __device__ __forceinline__ bool sweep_factor_as(const Params& P, const Lane& t, 
         const gdouble* ps = blk(P.cPs, t, AS_PSAVE, (kstart + 1) >> sh, SZ_PA) + t.q * 14 + imin(t.L, 13);
         SFOR(j, 0, 13, { Pa[j] = ps[j * 56]; });
     } else if (chk < 0) {
-        SFOR(j, 0, 13, { Pa[j] = (t.L == j) ? P.WN[ext_of(j)] : 0.0; });
+        if constexpr (WR == WR_ARGS) {
+            SFOR(j, 0, 13, { Pa[j] = (t.L == j) ? P.WN[ext_of(j)] : 0.0; });
+        } else {
+            const double wn = WR == WR_TABLE ? lds_w(qtab, t, WT_QN) : lane_wn<WR>(P, t);
+            SFOR(j, 0, 13, { Pa[j] = (t.L == j) ? wn : 0.0; });
+        }
     } else {
         const gdouble* pc = gm(P.Pchk) + ((size_t)t.wave * N_CHK + chk) * SZ_P;
         SFOR(j, 0, 13, {
@@ -821,8 +839,7 @@ __device__ __forceinline__ bool sweep_factor_as(const Params& P, const Lane& t, 
         });
     }
     bool ok = true;
-    double wq = 0.0;
-    SFOR(j, 0, 13, { if (t.L == j) wq = P.W[ext_of(j)]; });
+    const double wq = WR == WR_TABLE ? lds_w(qtab, t, 0) : lane_wq<WR>(P, t);
     const double is13 = t.L == 13 ? 1.0 : 0.0;
     auto keep = [&](int k) {
         if (k > 0 && (k & ((1 << sh) - 1)) == 0 && (k >> sh) < AS_PSAVE && t.L < 14) {
@@ -948,10 +965,22 @@ KALIGN __global__ __launch_bounds__(64, 2) void k_factor(Params P) {
     __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
     __shared__ double btile[4][64];
     __shared__ __attribute__((aligned(16))) double qtab[16 * QT_ROW];
-    const Lane t = lane_id(P);
+    const Lane t = lane_id<WR_ARGS>(P);   // (launched for the uniform weights only: k_factor_w)
     qtab_fill(P, qtab);
     __syncthreads();
-    bool ok = sweep_factor<true, true, CFN_FACTOR_DEEP != 0>(P, t, P.N, -1, wtile[t.row], btile[t.row], 0, nullptr, false, qtab);
+    bool ok = sweep_factor<true, true, CFN_FACTOR_DEEP != 0, false, WR_ARGS>(P, t, P.N, -1, wtile[t.row], btile[t.row], 0, nullptr, false, qtab);
+    ok = row_min(ok ? 1.0 : 0.0) > 0.0;
+    if (t.L == 0 && t.valid) gm(P.status)[t.inst] = ok ? 0 : 4;
+}
+
+// The same sweep for per-instance cost weights (Params.wtab): the LDS weight table of k_factor is shared by the four rows of a
+// wavefront, so this twin takes the diagonal of Q and R from the row's own registers (wq, Lane::wu) instead.
+KALIGN __global__ __launch_bounds__(64, 2) void k_factor_w(Params P) {
+    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
+    __shared__ double btile[4][64];
+    // (launched with the table set only; with WR_TABLE in place of the run-time test the compiler spills 36 B here)
+    const Lane t = lane_id(P);
+    bool ok = sweep_factor<true, false, CFN_FACTOR_DEEP != 0, true>(P, t, P.N, -1, wtile[t.row], btile[t.row]);
     ok = row_min(ok ? 1.0 : 0.0) > 0.0;
     if (t.L == 0 && t.valid) gm(P.status)[t.inst] = ok ? 0 : 4;
 }
@@ -1677,7 +1706,10 @@ __device__ __forceinline__ void elem_pass(const Params& P, size_t base, int n, i
 // backward costate sweep (pi_head = P_head dx_head; g_k = R dv_k + B'pi_{k+1}; pi_k = Q dx_k + A'pi_{k+1}, the costate
 // carried replicated as in sweep_resolve).  dv is read from Q.dva, g is left in Q.g.  Rows with dv = 0 get g = 0.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void sweep_clip_gradient(const Params& P, const Params& Q, const Lane& tc, const int head, const int chk) {
+template <int WR = WR_TEST>
+__device__ __forceinline__ void sweep_clip_gradient(const Params& P, const Params& Q, const Lane& tc, const int head, const int chk,
+                                                    const double* wl = nullptr) {
+    // wl (WR_TABLE): the row's weight-table entry staged in LDS -- this sweep needs all 13 state / terminal weights in every lane
     const int N = P.N;
     const int a = tc.L & 3;
     const bool lo4 = tc.L < 4;
@@ -1719,7 +1751,9 @@ __device__ __forceinline__ void sweep_clip_gradient(const Params& P, const Param
         double xh[13];
         SFOR(j, 0, 13, { xh[j] = zx[(size_t)head * 13 + j]; });
         if (chk < 0) {
-            SFOR(j, 0, 13, { p[j] = P.WN[ext_of(j)] * xh[j]; });
+            if (WR == WR_TABLE) SFOR(j, 0, 13, { p[j] = wl[WT_QN + j] * xh[j]; });
+            else if (wrows<WR>(P)) { const double wn = lane_wn<WR_TABLE>(P, tc); SFOR(j, 0, 13, { p[j] = bc<j>(wn) * xh[j]; }); }
+            else SFOR(j, 0, 13, { p[j] = P.WN[ext_of(j)] * xh[j]; });
         } else {   // pi = P_head dx_head, P_head row-distributed (lane i holds row i)
             const gdouble* pc = gm(Q.Pchk) + ((size_t)tc.wave * N_CHK + chk) * SZ_P;
             double pd = 0.0;
@@ -1737,7 +1771,9 @@ __device__ __forceinline__ void sweep_clip_gradient(const Params& P, const Param
     auto bodyb = [&](const Bk& cur, int k) {
         const double(&ar)[10] = cur.ar;
         const double(&br)[4] = cur.br;
-        double glane = lo4 ? tc.wu * cur.dv : 0.0;
+        double wua = tc.wu;
+        if constexpr (WR == WR_TABLE) { const double* w8 = wl; asm volatile("" : "+v"(w8)); wua = w8[WT_R + a]; }
+        double glane = lo4 ? wua * cur.dv : 0.0;
         double rr[4];
         SFOR(c, 0, 4, { rr[c] = bc<c>(glane); });
         dot2bc<13, 0>(rr[0], rr[1], p, br[0], br[1]);
@@ -1753,7 +1789,18 @@ __device__ __forceinline__ void sweep_clip_gradient(const Params& P, const Param
         dot2bc<10, 0>(pn[8], pn[9], p, ar[5], ar[6]);
         dot2bc<13, 0>(pn[10], pn[11], p, ar[7], ar[8]);
         dotbc<13, 0>(pn[12], p, ar[9]);
-        SFOR(j, 0, 13, { p[j] = pn[j] + P.W[ext_of(j)] * cur.xk[j]; });
+        if (WR == WR_TABLE) {
+            const double* w = wl;   // (re-read per stage: 13 hoisted copies would stay live over the sweep)
+            asm volatile("" : "+v"(w));
+            SFOR(j, 0, 13, { p[j] = pn[j] + w[j] * cur.xk[j]; });
+        } else if (wrows<WR>(P)) {   // (the row's weights re-read and broadcast per stage: nothing of them stays live over the sweep)
+            int h = tc.home;
+            asm volatile("" : "+v"(h));
+            const double w = wrow(P, h)[imin(tc.L, 12)];
+            SFOR(j, 0, 13, { p[j] = pn[j] + bc<j>(w) * cur.xk[j]; });
+        } else {
+            SFOR(j, 0, 13, { p[j] = pn[j] + P.W[ext_of(j)] * cur.xk[j]; });
+        }
     };
     Bk c0, c1;
     loadb(head - 1, c0);
@@ -1803,7 +1850,7 @@ __device__ unsigned long long g_prof[32];   // [0..7] phases of the longest wave
 #ifndef CFN_REST_FULL_HEAD
 #define CFN_REST_FULL_HEAD 1
 #endif
-template <int MODE, bool SBOX = false, bool CST = false, bool QT = false>
+template <int MODE, bool SBOX = false, bool CST = false, bool QT = false, int WR = WR_TEST>
 __device__ __forceinline__ void qp_wave(const Params& P, double (*wtile)[WT_TILE], double (*btile)[64], const int vb,
                                         const double* qtab = nullptr) {
 #ifdef CFN_PROF
@@ -1837,7 +1884,33 @@ __device__ __forceinline__ void qp_wave(const Params& P, double (*wtile)[WT_TILE
         has = has && gm(P.done)[inst0] == (MODE == 2 ? 0 : 2);   // commit kernel sent back for a longer head (done = 2)
         if (!__any(has)) return;
     }
-    const Lane t = lane_indirect(P, inst0, has);
+    Lane t = lane_indirect<WR == WR_TABLE ? WR_ARGS : WR>(P, inst0, has);   // (WR_TABLE: the input weight follows from the staged row)
+    // WR_TABLE: `qtab` is [4][WT_STRIDE] of LDS for the rows' table entries -- the sweeps take their weights from there (no global
+    // address to form or keep), the clipped start of the interior point all 26 of them per stage
+    const double* wl = nullptr;
+    if constexpr (WR == WR_TABLE) {
+        double* wd = const_cast<double*>(qtab) + t.row * WT_STRIDE;
+        __syncthreads();   // (k_ipm_rest_w: the previous round's readers)
+        wd[t.L] = wrow(P, t.home)[t.L];
+        wd[t.L + 16] = wrow(P, t.home)[t.L + 16];
+        __syncthreads();
+        wl = wd;
+        if constexpr (AS_ONLY) {
+            t.wu = wd[WT_R + (t.L & 3)];
+            asm volatile("" : "+v"(t.wu));
+        } else {
+            t.wu = 0.0;   // (the interior-point twins re-read it where they use it, wu_now: two registers less over the whole kernel)
+        }
+    }
+    auto wu_now = [&]() {   // input weight of this lane's input slot
+        if constexpr (WR == WR_TABLE && !AS_ONLY) {
+            const double* w = wl;
+            asm volatile("" : "+v"(w));
+            return w[WT_R + (t.L & 3)];
+        } else {
+            return t.wu;
+        }
+    };
     double* wt = wtile[t.row];
     double* sb = btile[t.row];
     const int N = P.N;
@@ -1934,7 +2007,9 @@ __device__ __forceinline__ void qp_wave(const Params& P, double (*wtile)[WT_TILE
         // ---- primal-dual active-set solves (exact when the classification becomes stationary)
         bool as_done = false;
         int as_iters = 0;
-        if (MODE != 2 && P.active_set) {
+        // (the interior-point twins keep no Lane::wu -- wu_now -- while the active-set sweeps read it: the block is not compiled
+        //  into them.  The host launches a MODE 0 kernel only with active_set = 0, launch_qp_ipm.)
+        if (MODE != 2 && !(WR == WR_TABLE && !AS_ONLY) && P.active_set) {
             // initial classification from the unconstrained minimiser; WARM (cfnmpc_opts.as_warm): a row whose previous RTI step
             // ended in a settled active-set solve starts from the union of that solve's final set and today's violations (the
             // reference never shifts its iterate, acados_mpc.cpp:581-611, so the classes are taken stage for stage).  Any start
@@ -1975,7 +2050,7 @@ __device__ __forceinline__ void qp_wave(const Params& P, double (*wtile)[WT_TILE
             const bool any_try = __any(try_as);
             for (int it = 1; any_try && it <= AS_MAX_SOLVES; it++) {
                 PROF_T(1)
-                as_ok = sweep_factor_as<QT>(Q, lane_opaque(tc), head, chk, kstart, wt, sb, qtab) && as_ok;
+                as_ok = sweep_factor_as<QT, WR>(Q, lane_opaque(tc), head, chk, kstart, wt, sb, WR == WR_TABLE ? wl : qtab) && as_ok;
                 PROF_T(2)
                 PROF_SOLVE(kstart + 1)
                 int jw = sweep_forward_as<SBOX, NO_ROLL>(Q, lane_opaque(tc), head);
@@ -2056,7 +2131,7 @@ __device__ __forceinline__ void qp_wave(const Params& P, double (*wtile)[WT_TILE
                     }
                 });
             }
-            sweep_clip_gradient(P, Q, tc, head, chk);
+            sweep_clip_gradient<WR>(P, Q, tc, head, chk, wl);
             double acc = 0.0;
             for (int e0 = t.L; e0 < head * 4; e0 += 64) {
                 double uk[4], vv[4], gg[4], blo[4], bhi[4];
@@ -2103,7 +2178,7 @@ __device__ __forceinline__ void qp_wave(const Params& P, double (*wtile)[WT_TILE
                         gm(Q.tl)[idx] = tl; gm(Q.tu)[idx] = tu; gm(Q.ll)[idx] = ll; gm(Q.lu)[idx] = lu; gm(Q.rg)[idx] = rg;
                         const double rl = v - lb - tl, ru = ub - v - tu;
                         const double Dl = ll * itl, Du = lu * itu;
-                        gm(Q.Rh)[idx] = t.wu + Dl + Du;
+                        gm(Q.Rh)[idx] = wu_now() + Dl + Du;
                         gm(Q.g)[idx] = rg + ll + Dl * rl - lu - Du * ru;
                         mu += ll * tl + lu * tu;
                         res = fmax(res, fmax(fmax(ll * tl, lu * tu), fmax(fabs(rg), fmax(fabs(rl), fabs(ru)))));
@@ -2129,7 +2204,7 @@ __device__ __forceinline__ void qp_wave(const Params& P, double (*wtile)[WT_TILE
             // predictor: factorise (R^, g from the element-wise pass), forward
             PROF_T(1)
             PROF_SOLVE(head)   // (profiling builds: interior-point iterations count like active-set solves)
-            const bool fok = sweep_factor<false>(Q, lane_opaque(tc), head, chk, wt, sb);
+            const bool fok = sweep_factor<false, false, false, false, WR>(Q, lane_opaque(tc), head, chk, wt, sb, 0, nullptr, false, wl);
             PROF_T(2)
             sweep_forward_delta(Q, lane_opaque(tc), head, gm(Q.dva));
             PROF_T(3)
@@ -2217,7 +2292,7 @@ __device__ __forceinline__ void qp_wave(const Params& P, double (*wtile)[WT_TILE
                     const double Dl = ll * rcp_nr(tl), Du = lu * rcp_nr(tu);
                     if (R.act) {
                         gm(Q.v)[idx] = v; gm(Q.tl)[idx] = tl; gm(Q.tu)[idx] = tu; gm(Q.ll)[idx] = ll; gm(Q.lu)[idx] = lu; gm(Q.rg)[idx] = rg;
-                        gm(Q.Rh)[idx] = t.wu + Dl + Du;
+                        gm(Q.Rh)[idx] = wu_now() + Dl + Du;
                         gm(Q.g)[idx] = rg + ll + Dl * rln - lu - Du * run;
                     }
                     mu += ll * tl + lu * tu;
@@ -2430,7 +2505,7 @@ __device__ __forceinline__ int ipm_rest_rows(const Params& P) {
 __global__ __launch_bounds__(64) void k_ipm(Params P) {       // MODE 0: used when active_set = 0
     __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
     __shared__ double btile[4][64];
-    qp_wave<0>(P, wtile, btile, blockIdx.x);
+    qp_wave<0, false, false, false, WR_ARGS>(P, wtile, btile, blockIdx.x);
 }
 KALIGN __global__ __launch_bounds__(64) void k_as(Params P) {        // active-set solves
     __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
@@ -2438,44 +2513,44 @@ KALIGN __global__ __launch_bounds__(64) void k_as(Params P) {        // active-s
     __shared__ __attribute__((aligned(16))) double qtab[16 * QT_ROW];
     qtab_fill(P, qtab);
     __syncthreads();
-    qp_wave<1, false, false, true>(P, wtile, btile, blockIdx.x, qtab);
+    qp_wave<1, false, false, true, WR_ARGS>(P, wtile, btile, blockIdx.x, qtab);
 }
 __global__ __launch_bounds__(64) void k_ipm_rest(Params P) {  // interior point for what k_as left
     __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
     __shared__ double btile[4][64];
-    for (int vb = blockIdx.x; vb * 4 < ipm_rest_rows(P); vb += gridDim.x) qp_wave<2>(P, wtile, btile, vb);
+    for (int vb = blockIdx.x; vb * 4 < ipm_rest_rows(P); vb += gridDim.x) qp_wave<2, false, false, false, WR_ARGS>(P, wtile, btile, vb);
 }
 // the same three for per-stage input boxes (cfnmpc_set_box_stages)
 __global__ __launch_bounds__(64) void k_ipm_sbox(Params P) {
     __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
     __shared__ double btile[4][64];
-    qp_wave<0, true>(P, wtile, btile, blockIdx.x);
+    qp_wave<0, true, false, false, WR_ARGS>(P, wtile, btile, blockIdx.x);
 }
 __global__ __launch_bounds__(64) void k_as_sbox(Params P) {
     __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
     __shared__ double btile[4][64];
-    qp_wave<1, true>(P, wtile, btile, blockIdx.x);
+    qp_wave<1, true, false, false, WR_ARGS>(P, wtile, btile, blockIdx.x);
 }
 __global__ __launch_bounds__(64) void k_ipm_rest_sbox(Params P) {
     __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
     __shared__ double btile[4][64];
-    for (int vb = blockIdx.x; vb * 4 < ipm_rest_rows(P); vb += gridDim.x) qp_wave<2, true>(P, wtile, btile, vb);
+    for (int vb = blockIdx.x; vb * 4 < ipm_rest_rows(P); vb += gridDim.x) qp_wave<2, true, false, false, WR_ARGS>(P, wtile, btile, vb);
 }
 // the three for the fused start solve (Params.fused = 1: stage blocks only in the compact store)
 __global__ __launch_bounds__(64) void k_ipm_cst(Params P) {
     __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
     __shared__ double btile[4][64];
-    qp_wave<0, false, true>(P, wtile, btile, blockIdx.x);
+    qp_wave<0, false, true, false, WR_ARGS>(P, wtile, btile, blockIdx.x);
 }
 KALIGN __global__ __launch_bounds__(64) void k_as_cst(Params P) {
     __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
     __shared__ double btile[4][64];
-    qp_wave<1, false, true>(P, wtile, btile, blockIdx.x);
+    qp_wave<1, false, true, false, WR_ARGS>(P, wtile, btile, blockIdx.x);
 }
 __global__ __launch_bounds__(64) void k_ipm_rest_cst(Params P) {
     __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
     __shared__ double btile[4][64];
-    for (int vb = blockIdx.x; vb * 4 < ipm_rest_rows(P); vb += gridDim.x) qp_wave<2, false, true>(P, wtile, btile, vb);
+    for (int vb = blockIdx.x; vb * 4 < ipm_rest_rows(P); vb += gridDim.x) qp_wave<2, false, true, false, WR_ARGS>(P, wtile, btile, vb);
 }
 __global__ __launch_bounds__(64) void k_as_solves(Params P) {  // MODE 4: active-set solves, no roll-out
     __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
@@ -2483,12 +2558,63 @@ __global__ __launch_bounds__(64) void k_as_solves(Params P) {  // MODE 4: active
     __shared__ __attribute__((aligned(16))) double qtab[16 * QT_ROW];
     qtab_fill(P, qtab);
     __syncthreads();
-    qp_wave<4, false, false, true>(P, wtile, btile, blockIdx.x, qtab);
+    qp_wave<4, false, false, true, WR_ARGS>(P, wtile, btile, blockIdx.x, qtab);
+}
+// The twins for per-instance cost weights (Params.wtab).  k_as / k_as_solves: without the LDS weight
+// table, which the four rows of a wavefront share.  The interior-point kernels: with the run-time test of P.wtab inside they
+// exceed their scratch ceilings (tests/test_resource_budget.py), so the kernels above read the kernel arguments and these the table.
+KALIGN __global__ __launch_bounds__(64) void k_as_w(Params P) {
+    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
+    __shared__ double btile[4][64];
+    __shared__ double wrows_lds[4][WT_STRIDE];
+    qp_wave<1, false, false, false, WR_TABLE>(P, wtile, btile, blockIdx.x, &wrows_lds[0][0]);
+}
+__global__ __launch_bounds__(64) void k_as_solves_w(Params P) {
+    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
+    __shared__ double btile[4][64];
+    __shared__ double wrows_lds[4][WT_STRIDE];
+    qp_wave<4, false, false, false, WR_TABLE>(P, wtile, btile, blockIdx.x, &wrows_lds[0][0]);
+}
+__global__ __launch_bounds__(64) void k_as_sbox_w(Params P) {
+    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
+    __shared__ double btile[4][64];
+    __shared__ double wrows_lds[4][WT_STRIDE];
+    qp_wave<1, true, false, false, WR_TABLE>(P, wtile, btile, blockIdx.x, &wrows_lds[0][0]);
+}
+__global__ __launch_bounds__(64) void k_as_retry_w(Params P) {
+    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
+    __shared__ double btile[4][64];
+    __shared__ double wrows_lds[4][WT_STRIDE];
+    qp_wave<3, false, false, false, WR_TABLE>(P, wtile, btile, blockIdx.x, &wrows_lds[0][0]);
+}
+__global__ __launch_bounds__(64) void k_ipm_w(Params P) {
+    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
+    __shared__ double btile[4][64];
+    __shared__ double wrows_lds[4][WT_STRIDE];
+    qp_wave<0, false, false, false, WR_TABLE>(P, wtile, btile, blockIdx.x, &wrows_lds[0][0]);
+}
+__global__ __launch_bounds__(64) void k_ipm_rest_w(Params P) {
+    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
+    __shared__ double btile[4][64];
+    __shared__ double wrows_lds[4][WT_STRIDE];
+    for (int vb = blockIdx.x; vb * 4 < ipm_rest_rows(P); vb += gridDim.x) qp_wave<2, false, false, false, WR_TABLE>(P, wtile, btile, vb, &wrows_lds[0][0]);
+}
+__global__ __launch_bounds__(64) void k_ipm_sbox_w(Params P) {
+    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
+    __shared__ double btile[4][64];
+    __shared__ double wrows_lds[4][WT_STRIDE];
+    qp_wave<0, true, false, false, WR_TABLE>(P, wtile, btile, blockIdx.x, &wrows_lds[0][0]);
+}
+__global__ __launch_bounds__(64) void k_ipm_rest_sbox_w(Params P) {
+    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
+    __shared__ double btile[4][64];
+    __shared__ double wrows_lds[4][WT_STRIDE];
+    for (int vb = blockIdx.x; vb * 4 < ipm_rest_rows(P); vb += gridDim.x) qp_wave<2, true, false, false, WR_TABLE>(P, wtile, btile, vb, &wrows_lds[0][0]);
 }
 __global__ __launch_bounds__(64) void k_as_retry(Params P) {  // MODE 3: rows the commit kernel sent back
     __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
     __shared__ double btile[4][64];
-    qp_wave<3>(P, wtile, btile, blockIdx.x);
+    qp_wave<3, false, false, false, WR_ARGS>(P, wtile, btile, blockIdx.x);
 }
 #ifdef CFN_DEV   // round 3's scheduling experiments (as_passes -2 / 1..12): development builds only since round 6 (measured slower at every fleet size)
 // =============================================================================================
@@ -2581,8 +2707,7 @@ __device__ __forceinline__ bool zsweep_factor(const Params& P, const Params& Q, 
                                               double* wt, double* sb) {
     double Pa[13];
     SFOR(j, 0, 13, { Pa[j] = 0.0; });
-    double wq = 0.0;
-    SFOR(j, 0, 13, { if (tc.L == j) wq = P.W[ext_of(j)]; });
+    const double wq = lane_wq(P, tc);
     const double is13 = tc.L == 13 ? 1.0 : 0.0;
     auto start_row = [&](int k) {   // rows with join == k: cost-to-go of stage k + 1
         if (k != join) return;
@@ -2590,7 +2715,8 @@ __device__ __forceinline__ bool zsweep_factor(const Params& P, const Params& Q, 
             const gdouble* ps = gm(Q.cPs) + ((size_t)tc.inst * AS_PSAVE + (k + 1) / AS_PGRAN) * 182 + imin(tc.L, 13);
             SFOR(j, 0, 13, { Pa[j] = ps[j * 14]; });
         } else if (chk < 0) {
-            SFOR(j, 0, 13, { Pa[j] = (tc.L == j) ? P.WN[ext_of(j)] : 0.0; });
+            const double wn = lane_wn(P, tc);
+            SFOR(j, 0, 13, { Pa[j] = (tc.L == j) ? wn : 0.0; });
         } else {                    // checkpoint of the unconstrained tail (home block)
             const gdouble* pc = gm(P.Pchk) + ((size_t)th.wave * N_CHK + chk) * SZ_PP;
             SFOR(j, 0, 13, {
@@ -2896,7 +3022,7 @@ __global__ __launch_bounds__(64) void k_asp_all(Params P) {
 #ifndef CFN_COMMIT_DEPTH
 #define CFN_COMMIT_DEPTH 3
 #endif
-template <bool DEEP>
+template <bool DEEP, int WR>
 __device__ __forceinline__ void ascommit_body(const Params& P) {
     const int nipm = gm(P.nipm)[0];
     const int N = P.N;
@@ -2912,7 +3038,7 @@ __device__ __forceinline__ void ascommit_body(const Params& P) {
             if (has && (threadIdx.x & 15) == 0) gm(P.done)[inst] = untried ? 2 : 0;
             continue;
         }
-        const Lane t = lane_indirect(P, inst, go);
+        const Lane t = lane_indirect<WR>(P, inst, go);
         const int head = go ? gm(P.head)[inst] : N;
         const int a = t.L & 3;
         const bool lo4 = t.L < 4;
@@ -3025,8 +3151,11 @@ __device__ __forceinline__ void ascommit_body(const Params& P) {
         }
     }
 }
-__global__ __launch_bounds__(64, 2) void k_ascommit(Params P) { ascommit_body<false>(P); }
-__global__ __launch_bounds__(64) void k_ascommit1(Params P) { ascommit_body<true>(P); }
+__global__ __launch_bounds__(64, 2) void k_ascommit(Params P) { ascommit_body<false, WR_ARGS>(P); }
+__global__ __launch_bounds__(64) void k_ascommit1(Params P) { ascommit_body<true, WR_ARGS>(P); }
+// the twins for per-instance cost weights (Params.wtab): the input weight of the home row from the table
+__global__ __launch_bounds__(64, 2) void k_ascommit_w(Params P) { ascommit_body<false, WR_TABLE>(P); }
+__global__ __launch_bounds__(64) void k_ascommit1_w(Params P) { ascommit_body<true, WR_TABLE>(P); }
 #ifdef CFN_PROF
 // isolated sweeps on one wave per SIMD (development aid): every wave repeats the sweep `reps` times
 __global__ __launch_bounds__(64) void k_bench_sweep(Params P, int head, int reps, int which) {
@@ -3517,7 +3646,7 @@ void launch_factor_only(const Params& P, hipStream_t st) {
     // the start-solve kernels index the home 4-vectors in the wave-blocked layout unconditionally (cfnmpc_rg.hpp: load_stage,
     // factor_stage); solvers without it (partial condensing) have no path that leads here -- refuse rather than corrupt
     if (!P.v4b) { std::fprintf(stderr, "cfnmpc: k_factor needs the wave-blocked 4-vector layout (not a cond_N2 solver)\n"); return; }
-    hipLaunchKernelGGL(k_factor, dim3(P.NW), dim3(64), 0, st, P);
+    hipLaunchKernelGGL(P.wtab ? k_factor_w : k_factor, dim3(P.NW), dim3(64), 0, st, P);
 }
 void launch_cforward(const Params& P, hipStream_t st) {
     if (P.mpar) { if (P.erk_steps > 1) hipLaunchKernelGGL(k_cforward_erk_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_cforward_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
@@ -3548,12 +3677,12 @@ void launch_qp_ipm(const Params& P, hipStream_t st, hipEvent_t* ev) {
     }
     if (P.lbs) {   // per-stage boxes: monolithic kernels instantiated for them
         if (P.active_set) {
-            hipLaunchKernelGGL(k_as_sbox, dim3(P.NW), dim3(64), 0, st, P);   // (lists its fall-back rows itself)
+            hipLaunchKernelGGL(P.wtab ? k_as_sbox_w : k_as_sbox, dim3(P.NW), dim3(64), 0, st, P);   // (lists its fall-back rows itself)
             if (ev) (void)hipEventRecord(ev[0], st);
-            hipLaunchKernelGGL(k_ipm_rest_sbox, dim3(imax_h(1, imin_h(P.NW, P.as_grid / 2))), dim3(64), 0, st, P);
+            hipLaunchKernelGGL(P.wtab ? k_ipm_rest_sbox_w : k_ipm_rest_sbox, dim3(imax_h(1, imin_h(P.NW, P.as_grid / 2))), dim3(64), 0, st, P);
         } else {
             if (ev) (void)hipEventRecord(ev[0], st);
-            hipLaunchKernelGGL(k_ipm_sbox, dim3(P.NW), dim3(64), 0, st, P);
+            hipLaunchKernelGGL(P.wtab ? k_ipm_sbox_w : k_ipm_sbox, dim3(P.NW), dim3(64), 0, st, P);
         }
     } else if (P.active_set && P.as_passes != 0) {
         // as_passes > 0: level-synchronous active-set passes -- pairs (factor, forward) of one solve each, one
@@ -3584,26 +3713,26 @@ void launch_qp_ipm(const Params& P, hipStream_t st, hipEvent_t* ev) {
                 //  part two, which is the longest chain of this group, cost 5 + 8 us per step whether it had work or not)
                 (void)hipEventRecord((hipEvent_t)P.as_join2, side2);
                 (void)hipStreamWaitEvent(side, (hipEvent_t)P.as_fork, 0);
-                hipLaunchKernelGGL(k_as_solves, dim3(P.NW), dim3(64), 0, side, PA);
+                hipLaunchKernelGGL(P.wtab ? k_as_solves_w : k_as_solves, dim3(P.NW), dim3(64), 0, side, PA);
                 (void)hipEventRecord((hipEvent_t)P.as_join, side);
             } else {
                 if (p1_ran) launch_forward_p2(P, st);   // no side streams: in order
                 if (side && !p1_ran) {
                     (void)hipStreamWaitEvent(side, (hipEvent_t)P.as_fork, 0);
-                    hipLaunchKernelGGL(k_as_solves, dim3(P.NW), dim3(64), 0, side, P);
+                    hipLaunchKernelGGL(P.wtab ? k_as_solves_w : k_as_solves, dim3(P.NW), dim3(64), 0, side, P);
                     (void)hipEventRecord((hipEvent_t)P.as_join, side);
                 } else {
                     side = nullptr;
                     Params PA = P;
                     PA.as_range = p1_ran ? 1 : 0;   // (behind a split sweep the same rows as with the side streams: bit-identical steps)
-                    hipLaunchKernelGGL(k_as_solves, dim3(P.NW), dim3(64), 0, st, PA);
+                    hipLaunchKernelGGL(P.wtab ? k_as_solves_w : k_as_solves, dim3(P.NW), dim3(64), 0, st, PA);
                 }
             }
             launch_as_dense(P, imax_h(1, imin_h(P.as_grid / 2, P.NW * 4)), st);
             if (side) (void)hipStreamWaitEvent(st, (hipEvent_t)P.as_join, 0);
             if (split) (void)hipStreamWaitEvent(st, (hipEvent_t)P.as_join2, 0);
         } else if (P.as_passes == -2) {
-            hipLaunchKernelGGL(k_as_solves, dim3(P.NW), dim3(64), 0, st, P);
+            hipLaunchKernelGGL(P.wtab ? k_as_solves_w : k_as_solves, dim3(P.NW), dim3(64), 0, st, P);
         }
 #ifdef CFN_DEV
         else if (P.as_passes < 0) {
@@ -3619,22 +3748,22 @@ void launch_qp_ipm(const Params& P, hipStream_t st, hipEvent_t* ev) {
                 hipLaunchKernelGGL(k_asp, dim3(imax_h(1, G / 2)), dim3(64), 0, st, P, P.as_passes, AS_MAX_SOLVES - P.as_passes);
         }
 #endif
-        if (P.NW <= 2 * P.as_grid) hipLaunchKernelGGL(k_ascommit1, dim3(imax_h(1, imin_h(P.as_grid / 2, P.NW))), dim3(64), 0, st, P);
-        else hipLaunchKernelGGL(k_ascommit, dim3(G), dim3(64), 0, st, P);
+        if (P.NW <= 2 * P.as_grid) hipLaunchKernelGGL(P.wtab ? k_ascommit1_w : k_ascommit1, dim3(imax_h(1, imin_h(P.as_grid / 2, P.NW))), dim3(64), 0, st, P);
+        else hipLaunchKernelGGL(P.wtab ? k_ascommit_w : k_ascommit, dim3(G), dim3(64), 0, st, P);
         // (late rows of a split forward sweep: k_as_retry and k_ipm_rest count them in, P.nipm[0] + P.nipm[NI_LATE].  Tried: both modes in
         //  ONE launch for small fleets, where each normally finds nothing to do and an empty launch costs 5 - 7 us -- either half
         //  alone runs, the combined kernel aborts on the device; not pursued)
-        hipLaunchKernelGGL(k_as_retry, dim3(P.NW), dim3(64), 0, st, P);
+        hipLaunchKernelGGL(P.wtab ? k_as_retry_w : k_as_retry, dim3(P.NW), dim3(64), 0, st, P);
         if (ev) (void)hipEventRecord(ev[0], st);
         if (P.ipm_listed) hipLaunchKernelGGL(k_ipm_list, dim3(1), dim3(1024), 0, st, P);
-        hipLaunchKernelGGL(k_ipm_rest, dim3(imax_h(1, imin_h(P.NW, P.as_grid / 2))), dim3(64), 0, st, P);
+        hipLaunchKernelGGL(P.wtab ? k_ipm_rest_w : k_ipm_rest, dim3(imax_h(1, imin_h(P.NW, P.as_grid / 2))), dim3(64), 0, st, P);
     } else if (P.active_set) {
-        hipLaunchKernelGGL(k_as, dim3(P.NW), dim3(64), 0, st, P);   // (lists its fall-back rows itself)
+        hipLaunchKernelGGL(P.wtab ? k_as_w : k_as, dim3(P.NW), dim3(64), 0, st, P);   // (lists its fall-back rows itself)
         if (ev) (void)hipEventRecord(ev[0], st);
-        hipLaunchKernelGGL(k_ipm_rest, dim3(imax_h(1, imin_h(P.NW, P.as_grid / 2))), dim3(64), 0, st, P);
+        hipLaunchKernelGGL(P.wtab ? k_ipm_rest_w : k_ipm_rest, dim3(imax_h(1, imin_h(P.NW, P.as_grid / 2))), dim3(64), 0, st, P);
     } else {
         if (ev) (void)hipEventRecord(ev[0], st);
-        hipLaunchKernelGGL(k_ipm, dim3(P.NW), dim3(64), 0, st, P);
+        hipLaunchKernelGGL(P.wtab ? k_ipm_w : k_ipm, dim3(P.NW), dim3(64), 0, st, P);
     }
 }
 void launch_qp(const Params& P, hipStream_t st, hipEvent_t* ev) {

@@ -185,7 +185,7 @@ KALIGN __global__ __launch_bounds__(64, 2) void k_linfactor(Params P) {
     __shared__ double btile[4][64];
     __shared__ double park[13 * 64];
     __shared__ __attribute__((aligned(16))) double qtab[16 * QT_ROW];
-    const Lane t = lane_id(P);
+    const Lane t = lane_id<WR_ARGS>(P);   // (uniform weights only: cfnmpc_set_weights_batch refuses the fused start solve)
     qtab_fill(P, qtab);
     __syncthreads();
     bool ok = sweep_linfactor(P, t, wtile[t.row], btile[t.row], park, qtab);

@@ -64,6 +64,14 @@ inline bool model_params_ok(const double* p, size_t n) {
         if (!(p[i] > 0.0 && p[i] <= 1.7976931348623157e308)) return false;   // (NaN fails both)
     return true;
 }
+// rows of cfnmpc_set_weights_batch, W [B][17] and / or WN [B][13]: every entry finite, state and terminal weights >= 0, input
+// weights > 0 (NaN fails the comparisons)
+inline bool weight_rows_ok(const double* W, const double* WN, size_t B) {
+    const double big = 1.7976931348623157e308;
+    if (W) for (size_t i = 0; i < B * 17; i++) if (!(W[i] >= 0.0 && W[i] <= big) || (i % 17 >= 13 && !(W[i] > 0.0))) return false;
+    if (WN) for (size_t i = 0; i < B * 13; i++) if (!(WN[i] >= 0.0 && WN[i] <= big)) return false;
+    return true;
+}
 // p[NPAR] -> k[NK] (the expressions of the constants above, term for term)
 __host__ __device__ inline void derive_k(const double* p, double* k) {
     const double g0 = p[0], mq = p[1], ixx = p[2], iyy = p[3], izz = p[4], cd = p[5], ct = p[6], arm = p[7];

@@ -285,6 +285,25 @@ int cfnmpc_multi_set_model_params(cfnmpc_multi* m, const double* p) {
     return CFNMPC_OK;
 }
 
+int cfnmpc_multi_set_weights_batch(cfnmpc_multi* m, const double* W, const double* WN) {
+    if (!m) return CFNMPC_EINVAL;
+    if (!cfn::weight_rows_ok(W, WN, (size_t)m->B)) return CFNMPC_EINVAL;   // (as a whole: no shard changes)
+    std::vector<double> hn;
+    for (Shard& s : m->sh) {
+        if (m->mixed) {
+            if (WN) {   // (to_shard's staging buffer holds W)
+                hn.resize(s.idx.size() * 13);
+                for (size_t r = 0; r < s.idx.size(); r++) std::copy_n(WN + (size_t)s.idx[r] * 13, 13, hn.data() + r * 13);
+            }
+            RC_TRY(cfnmpc_fleet_set_weights_batch(s.f, W ? to_shard(s, W, 17, 17) : nullptr, WN ? hn.data() : nullptr));
+        } else {
+            RC_TRY(cfnmpc_set_weights_batch(s.s, W ? W + (size_t)s.lo * 17 : nullptr, WN ? WN + (size_t)s.lo * 13 : nullptr,
+                                            CFNMPC_ON_HOST, s.st));
+        }
+    }
+    return CFNMPC_OK;
+}
+
 int cfnmpc_multi_init_iterate(cfnmpc_multi* m, int mode) {
     if (!m) return CFNMPC_EINVAL;
     for (Shard& s : m->sh) RC_TRY(m->mixed ? cfnmpc_fleet_init_iterate(s.f, mode, s.st) : cfnmpc_init_iterate(s.s, mode, s.st));

@@ -58,8 +58,27 @@ __device__ __forceinline__ double row_max(double x) {
     return s;
 }
 
-__device__ __forceinline__ double lane_wu(const Params& P, int a) {
-    double w = a == 0 ? P.W[13] : (a == 1 ? P.W[14] : (a == 2 ? P.W[15] : P.W[16]));
+// Cost weights of a row: the uniform kernel arguments P.W / P.WN, or -- cfnmpc_set_weights_batch -- the row of the HOME
+// instance in the per-instance table P.wtab, 32 doubles per workspace row: [0, 13) state weights in the INTERNAL order,
+// [13, 17) input weights, [17, 30) terminal weights in the internal order, two pad entries (effective values: the scaling
+// factors are applied on the host; padding rows and the spare block hold the uniform weights).  The test of P.wtab is
+// wave-uniform and every read sits in front of a sweep's stage loop.
+// WR: where a kernel's weights come from -- WR_ARGS: the kernel arguments, whatever P.wtab says (the kernels that keep their
+// register budget only without the test; their _w twins are WR_TABLE: the table, untested); WR_TEST: the run-time test.
+constexpr int WR_ARGS = 0, WR_TABLE = 1, WR_TEST = 2;
+template <int WR>
+__device__ __forceinline__ bool wrows(const Params& P) { return WR == WR_TEST ? P.wtab != nullptr : WR == WR_TABLE; }
+constexpr int WT_STRIDE = 32, WT_R = 13, WT_QN = 17;
+typedef __attribute__((address_space(1))) double gwdouble;
+__device__ __forceinline__ const gwdouble* wrow(const Params& P, int home) {
+    return (const gwdouble*)(unsigned long long)P.wtab + (size_t)home * WT_STRIDE;
+}
+__device__ __forceinline__ int imin_w(int a, int b) { return a < b ? a : b; }
+template <int WR = WR_TEST>
+__device__ __forceinline__ double lane_wu(const Params& P, int home, int a) {
+    double w;
+    if (wrows<WR>(P)) w = wrow(P, home)[WT_R + a];
+    else w = a == 0 ? P.W[13] : (a == 1 ? P.W[14] : (a == 2 ? P.W[15] : P.W[16]));
     asm volatile("" : "+v"(w));
     return w;
 }
@@ -69,6 +88,7 @@ struct Lane {
     int q;      // position of the instance inside its workspace block, 0..3
     int wave;   // workspace block (= "home" wave) of the instance
     int inst;   // global instance
+    int home;   // instance whose cost weights the row uses (= inst, except in the compact copies of a lane: their inst is a compact slot)
     bool valid;
     double wu;  // input weight R_a of this lane's input slot a = L & 3 (kept in a register: a select
                 // chain at the point of use gets turned into a lookup table in scratch, whose load
@@ -81,6 +101,7 @@ __device__ __forceinline__ Lane lane_opaque(const Lane& t) {
     asm volatile("" : "+v"(o.L), "+v"(o.q), "+v"(o.wave), "+v"(o.inst));
     return o;
 }
+template <int WR = WR_TEST>
 __device__ __forceinline__ Lane lane_id(const Params& P) {
     Lane t;
     t.L = threadIdx.x & 15;
@@ -88,12 +109,14 @@ __device__ __forceinline__ Lane lane_id(const Params& P) {
     t.q = t.row;
     t.wave = blockIdx.x;
     t.inst = t.wave * 4 + t.q;
+    t.home = t.inst;
     t.valid = t.inst < P.B;
-    t.wu = lane_wu(P, t.L & 3);
+    t.wu = lane_wu<WR>(P, t.home, t.L & 3);
     return t;
 }
 // Row r of this wavefront works on an arbitrary instance (compacted interior-point waves);
 // rows without work are parked on the spare workspace block NW (never read by anyone else).
+template <int WR = WR_TEST>
 __device__ __forceinline__ Lane lane_indirect(const Params& P, int inst, bool valid) {
     Lane t;
     t.L = threadIdx.x & 15;
@@ -101,9 +124,31 @@ __device__ __forceinline__ Lane lane_indirect(const Params& P, int inst, bool va
     t.inst = valid ? inst : P.NW * 4 + t.row;
     t.wave = t.inst >> 2;
     t.q = t.inst & 3;
+    t.home = t.inst;
     t.valid = valid;
-    t.wu = lane_wu(P, t.L & 3);
+    t.wu = lane_wu<WR>(P, t.home, t.L & 3);
     return t;
+}
+// state weight Q_i of this lane's row (lane i < 13, 0 elsewhere) and its terminal weight, once per sweep
+template <int WR = WR_TEST>
+__device__ __forceinline__ double lane_wq(const Params& P, const Lane& t) {
+    double wq = 0.0;
+    if (wrows<WR>(P)) { const double v = wrow(P, t.home)[imin_w(t.L, 12)]; wq = t.L < 13 ? v : 0.0; }
+    else SFOR(j, 0, 13, { if (t.L == j) wq = P.W[ext_of(j)]; });
+    return wq;
+}
+template <int WR = WR_TEST>
+__device__ __forceinline__ double lane_wn(const Params& P, const Lane& t) {
+    double wn = 0.0;
+    if (wrows<WR>(P)) { const double v = wrow(P, t.home)[WT_QN + imin_w(t.L, 12)]; wn = t.L < 13 ? v : 0.0; }
+    else SFOR(j, 0, 13, { if (t.L == j) wn = P.WN[ext_of(j)]; });
+    return wn;
+}
+// a value that is the same in every lane of the wavefront, moved to scalar registers
+__device__ __forceinline__ double wave_uniform(double v) {
+    const unsigned long long x = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)x), hi = __builtin_amdgcn_readfirstlane((unsigned)(x >> 32));
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 // Workspace pointers live inside the by-value Params struct, where clang cannot infer the
 // address space: gm() re-types them as global (address_space(1)) so that loads / stores are
@@ -333,7 +378,10 @@ __device__ __forceinline__ void qtab_fill(const Params& P, double* qtab) {   // 
         qtab[L * QT_ROW + 17] = 0.0;
     }
 }
-template <bool ABSOLUTE, bool AS = false, bool ZL = false, bool QTAB = false>
+//   WROW (k_factor_w: per-instance weights, where that table cannot serve -- it is shared by the wave's four rows): the diagonals are
+//   selected from the lane's own wq / R against a zero the compiler cannot see through, so that the 17 selects are formed per stage
+//   and not hoisted either.
+template <bool ABSOLUTE, bool AS = false, bool ZL = false, bool QTAB = false, bool WROW = false>
 __device__ __forceinline__ bool factor_stage(const Params& P, const Lane& t, const int k, double (&Pa)[13],
                                              const StageIn<ABSOLUTE>& in, const double wq, const double is13,
                                              double* wt, double* sb, const bool act = true, const double* qtab = nullptr) {
@@ -374,7 +422,10 @@ __device__ __forceinline__ bool factor_stage(const Params& P, const Lane& t, con
     // (4) S = R^ + B'V in lanes a < 4, replicated; every lane inverts it redundantly (4x4 Cholesky),
     //     one pivot at a time BETWEEN the blocks of (5) and (6), which hide the pivots' latency
     double Srow[4];
-    if (QTAB && ABSOLUTE && !AS) SFOR(c, 0, 4, { Srow[c] = qtab[t.L * QT_ROW + 13 + c]; });   // (R constant: start solve only)
+    double zero = 0.0;
+    if (WROW) opaque(zero);
+    if (WROW) SFOR(c, 0, 4, { Srow[c] = (t.L == c) ? in.Rh : zero; });
+    else if (QTAB && ABSOLUTE && !AS) SFOR(c, 0, 4, { Srow[c] = qtab[t.L * QT_ROW + 13 + c]; });   // (R constant: start solve only)
     else SFOR(c, 0, 4, { Srow[c] = (t.L == c) ? in.Rh : 0.0; });
     dot4bc<13>(Srow[0], Srow[1], Srow[2], Srow[3], bcl, V[0], V[1], V[2], V[3]);
     SFOR(c, 0, 4, { settle(Srow[c]); });
@@ -390,7 +441,8 @@ __device__ __forceinline__ bool factor_stage(const Params& P, const Lane& t, con
     chol4_pivot<0>(S, ch);
     // (5) M = Q + Wt A  (lane 13: q_k' + hb'A)
     double M[13];
-    if (QTAB) SFOR(j, 0, 13, { M[j] = qtab[t.L * QT_ROW + j]; });
+    if (WROW) SFOR(j, 0, 13, { M[j] = (t.L == j) ? wq : zero; });
+    else if (QTAB) SFOR(j, 0, 13, { M[j] = qtab[t.L * QT_ROW + j]; });
     else SFOR(j, 0, 13, { M[j] = (t.L == j) ? wq : 0.0; });
     if (ABSOLUTE) rank1bc<13>(M, is13, in.qv);   // lane 13: += q_k[j]
     SFOR(j, 0, 3, { M[j] += Wt[j]; });

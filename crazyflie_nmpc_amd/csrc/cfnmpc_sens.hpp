@@ -156,8 +156,9 @@ __global__ __launch_bounds__(64, 2) void k_sens_factor(Params P, SensArgs A) {
     t.inst = A.list[valid ? w * 4 + row : w * 4];
     t.wave = t.inst >> 2;
     t.q = t.inst & 3;
+    t.home = t.inst;
     t.valid = valid;
-    t.wu = lane_wu(P, t.L & 3);
+    t.wu = lane_wu(P, t.home, t.L & 3);
     const int kst = valid ? A.kst[t.inst] : 0;
     int kmax = 0;
     for (int r = 0; r < 4; r++)
@@ -171,10 +172,10 @@ __global__ __launch_bounds__(64, 2) void k_sens_factor(Params P, SensArgs A) {
             Pa[j] = t.L < 13 ? v : 0.0;
         });
     } else {
-        SFOR(j, 0, 13, { Pa[j] = (t.L == j) ? P.WN[ext_of(j)] : 0.0; });
+        const double wn = lane_wn(P, t);
+        SFOR(j, 0, 13, { Pa[j] = (t.L == j) ? wn : 0.0; });
     }
-    double wq = 0.0;
-    SFOR(j, 0, 13, { if (t.L == j) wq = P.W[ext_of(j)]; });
+    const double wq = lane_wq(P, t);
     const double rh = t.wu;
     for (int k = kmax - 1; k >= 0; k--) {
         double ar[10], br[4];
@@ -203,6 +204,7 @@ __global__ __launch_bounds__(64, 2) void k_sens_fwd(Params P, SensArgs A) {
     t.q = t.row;
     t.wave = A.b0 / 4 + blockIdx.x;
     t.inst = t.wave * 4 + t.q;
+    t.home = t.inst;
     t.valid = t.inst < P.B && t.inst < A.b0 + A.nb;
     t.wu = 0.0;
     const int kst = t.valid ? A.kst[t.inst] : 0;

@@ -183,6 +183,9 @@ struct Params {
                                  // M > 1 = their _erk variants; k_sqp_check reads it either way)
     double* mpar;                // per-instance model constants (cfnmpc_set_model_params), [NK][(NW + 1) * 4] structure-of-arrays
                                  // (cfnmpc_model.hpp: derive_k; the spare block's rows nominal); NULL = the folded constants
+    double* wtab;                // per-instance cost weights (cfnmpc_set_weights_batch), [(NW + 1) * 4][32]: state weights in the internal
+                                 // order at [0, 13), input weights at [13, 17), terminal weights (internal order) at [17, 30); effective
+                                 // values (scaling applied); padding rows and the spare block uniform; NULL = the uniform W / WN above
 };
 
 // The linearisation (AR, BR, b) of the HOME blocks: [group of 16 blocks][stage][block of the group][sz] -- a lane-per-instance wave

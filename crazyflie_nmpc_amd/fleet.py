@@ -17,6 +17,20 @@ from .solver import _arg, _check, default_opts, _launch_stream, _torch_device
 from .synthetic import regulation_row
 
 
+def _weight_rows(B, W, WN):
+    """host rows of set_weights_batch -> ((pointer or None, keepalive), (pointer or None, keepalive))"""
+    out = []
+    for a, n in ((W, 17), (WN, 13)):
+        if a is None:
+            out.append((None, None))
+            continue
+        arr = np.ascontiguousarray(a, dtype=np.float64)
+        if arr.shape != (B, n):
+            raise ValueError(f"expected shape {(B, n)}, got {arr.shape}")
+        out.append((arr.ctypes.data_as(C.c_void_p), arr))
+    return out
+
+
 class MixedHorizonFleet:
     def __init__(self, horizons, **opt_kw):
         self._L = _lib.lib()
@@ -113,6 +127,11 @@ class MixedHorizonFleet:
         if pa.shape != (self.B, 8):
             raise ValueError(f"expected shape {(self.B, 8)}, got {pa.shape}")
         _check(self._L.cfnmpc_fleet_set_model_params(self._h, pa.ctypes.data_as(C.c_void_p)), "cfnmpc_fleet_set_model_params")
+
+    def set_weights_batch(self, W=None, WN=None):
+        """per-vehicle cost weights, host arrays W [B][17] / WN [B][13] in the fleet's vehicle order; None, None: uniform"""
+        pw, pn = _weight_rows(self.B, W, WN)
+        _check(self._L.cfnmpc_fleet_set_weights_batch(self._h, pw[0], pn[0]), "cfnmpc_fleet_set_weights_batch")
 
     def set_box_stages(self, lb=None, ub=None):
         """per-stage / per-input boxes, host arrays [B][Nmax][4] (vehicle i uses rows 0..N_i-1); None, None: scalar box"""

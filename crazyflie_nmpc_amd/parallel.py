@@ -145,6 +145,15 @@ class MultiGpuFleet:
         if rc != 0:
             raise ValueError(f"cfnmpc_multi_set_model_params failed with code {rc}")
 
+    def set_weights_batch(self, W=None, WN=None):
+        """per-vehicle cost weights, host arrays W [B][17] / WN [B][13] of the whole fleet; None, None: uniform"""
+        from .fleet import _weight_rows
+        from .solver import CfnmpcError
+        pw, pn = _weight_rows(self.B, W, WN)
+        rc = self._L.cfnmpc_multi_set_weights_batch(self._h, pw[0], pn[0])
+        if rc != 0:
+            raise CfnmpcError(f"cfnmpc_multi_set_weights_batch failed with code {rc}")
+
     def set_cost_scaling(self, stage=1.0, terminal=1.0):
         rc = self._L.cfnmpc_multi_set_cost_scaling(self._h, float(stage), float(terminal))
         if rc != 0:

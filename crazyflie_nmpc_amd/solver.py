@@ -224,6 +224,29 @@ class BatchSolver:
         _check(self._L.cfnmpc_get_model_params(self._h, out.ctypes.data_as(C.c_void_p), 0, None), "cfnmpc_get_model_params")
         return out
 
+    def set_weights_batch(self, W=None, WN=None):
+        """Per-instance cost weights: W [B][17], WN [B][13] (numpy or device tensors; external order, unscaled -- the effective
+        weights are the cost scaling's factors times the rows).  None, None: back to the uniform weights; one None: that
+        part keeps what every row has.  Every entry finite, state / terminal weights >= 0, input weights > 0."""
+        if W is None and WN is None:
+            _check(self._L.cfnmpc_set_weights_batch(self._h, None, None, 0, _launch_stream(None, self._device)), "cfnmpc_set_weights_batch")
+            return
+        if W is not None and WN is not None and _is_torch(W) != _is_torch(WN):
+            raise ValueError("W and WN must both be host arrays or both device tensors")
+        pw, pn, dev, st, keep = None, None, 0, None, []
+        if W is not None:
+            pw, dev, st, k = _arg(W, (self.B, NY), device=self._device); keep.append(k)
+        if WN is not None:
+            pn, dev, st, k = _arg(WN, (self.B, NX), device=self._device); keep.append(k)
+        _check(self._L.cfnmpc_set_weights_batch(self._h, pw, pn, dev, st), "cfnmpc_set_weights_batch")
+
+    def weights_batch(self):
+        """-> (W [B][17], WN [B][13]): the unscaled rows in force (the uniform weights everywhere while none are set)"""
+        W, WN = np.empty((self.B, NY)), np.empty((self.B, NX))
+        _check(self._L.cfnmpc_get_weights_batch(self._h, W.ctypes.data_as(C.c_void_p), WN.ctypes.data_as(C.c_void_p), 0, None),
+               "cfnmpc_get_weights_batch")
+        return W, WN
+
     def set_box_stages(self, lb=None, ub=None):
         """Per-stage, per-input box [B][N][4] (acados' "lbu" / "ubu" on individual stages); None, None: back to
         the scalar box."""

@@ -272,6 +272,30 @@ int cfnmpc_set_cost_scaling(cfnmpc_solver *s, double stage_scale, double termina
 #define CFNMPC_NP 8
 int cfnmpc_set_model_params(cfnmpc_solver *s, const double *p /*[B][CFNMPC_NP] or NULL*/, int on_device, void *stream);
 int cfnmpc_get_model_params(cfnmpc_solver *s, double *p /*[B][CFNMPC_NP]*/, int on_device, void *stream);
+/* Per-instance cost weights: W [B][17] and WN [B][13], one row per instance in the external order of
+ * cfnmpc_opts.W / .WN, unscaled -- the effective weights of row i are stage_scale * W[i] and terminal_scale * WN[i], and a later
+ * cfnmpc_set_cost_scaling rescales the rows in force.  The reference tunes the 17 Wdiag_* values per vehicle through each node's
+ * dynamic_reconfigure server (acados_mpc.cpp:199-203, 274-290, 334-350).
+ *   cfnmpc_set_weights_batch: every entry finite, state and terminal weights >= 0, input weights > 0; the arrays are validated as
+ *     a whole before anything changes (CFNMPC_EINVAL, the previous weights stay in force; device arrays are copied to the host once
+ *     to be checked).  W = NULL and WN = NULL returns to the uniform weights, i.e. the values of cfnmpc_opts or of the last
+ *     cfnmpc_set_weights.  One NULL part: that part keeps what every row has (the uniform values if no rows were set).  While rows
+ *     are in force, each part cfnmpc_set_weights is given replaces that part in every row.  Refused (CFNMPC_EINVAL) beside
+ *     start_solve 2 or 3 and cond_N2 > 0 (their kernels stage one weight vector per wavefront / workgroup); with rows in force
+ *     cfnmpc_debug_start_factor refuses mode 2.  Switching between uniform weights and rows invalidates captured step graphs; new
+ *     rows over old ones are copied in place on `stream` and complete before the call returns, so the next solve or graph replay
+ *     reads them.  Every change of weights invalidates a sensitivity evaluation; cfnmpc_eval_sens_x0 uses the rows.
+ *     cfnmpc_workspace_bytes counts the table (256 bytes per instance, allocated at the first call).
+ *     While rows are in force, cfnmpc_set_weights (finite entries only, then) and cfnmpc_set_cost_scaling rewrite the table in
+ *     place on the null stream, block until that is done and may return CFNMPC_EHIP; like cfnmpc_set_weights_batch on a stream
+ *     other than the solves' own, they must not overlap a solve in flight, which reads the table (without rows both calls only
+ *     change the arguments of the next launch, as before).
+ *   cfnmpc_get_weights_batch: the unscaled rows in force (the uniform values for every instance while none are set); either
+ *     pointer may be NULL. */
+int cfnmpc_set_weights_batch(cfnmpc_solver *s, const double *W /*[B][17] or NULL*/, const double *WN /*[B][13] or NULL*/,
+                             int on_device, void *stream);
+int cfnmpc_get_weights_batch(cfnmpc_solver *s, double *W /*[B][17] or NULL*/, double *WN /*[B][13] or NULL*/,
+                             int on_device, void *stream);
 /* Per-stage, per-input box: lb, ub [B][N][4] (what "lbu" / "ubu" on INDIVIDUAL stages set in acados -- the reference's
  * FIXED_U0 variant pins stage 0 to the input in flight, lbu = ubu = u1, acados_mpc.cpp:605-608).  lb[i] = ub[i] makes
  * that input an equality (the active-set solves keep it fixed whatever its multiplier's sign; the interior-point
@@ -465,6 +489,10 @@ int cfnmpc_fleet_set_erk_steps(cfnmpc_fleet *f, int num_steps);
 int cfnmpc_fleet_set_cost_scaling(cfnmpc_fleet *f, double stage_scale, double terminal_scale);
 /* cfnmpc_set_model_params for a fleet: HOST array [B][CFNMPC_NP] in the fleet's vehicle order (NULL: nominal) */
 int cfnmpc_fleet_set_model_params(cfnmpc_fleet *f, const double *p);
+/* cfnmpc_set_weights_batch for a fleet: HOST arrays [B][17] / [B][13] in the fleet's vehicle order, scattered to the buckets;
+ * validated as a whole first (a bad row, or an option that refuses rows, leaves every bucket unchanged; an allocation or copy
+ * failure in a later bucket does not undo the earlier ones, as with cfnmpc_fleet_set_model_params) */
+int cfnmpc_fleet_set_weights_batch(cfnmpc_fleet *f, const double *W, const double *WN);
 /* cfnmpc_set_box_stages for a fleet: HOST arrays [B][Nmax][4] in the fleet's vehicle order (rows behind a vehicle's own
  * horizon are ignored); NULL, NULL: back to the scalar box */
 int cfnmpc_fleet_set_box_stages(cfnmpc_fleet *f, const double *lb, const double *ub);
@@ -534,6 +562,10 @@ int cfnmpc_multi_set_erk_steps(cfnmpc_multi *m, int num_steps);
 int cfnmpc_multi_set_cost_scaling(cfnmpc_multi *m, double stage_scale, double terminal_scale);
 /* cfnmpc_set_model_params for every shard: HOST array [B][CFNMPC_NP] of the whole fleet (NULL: nominal) */
 int cfnmpc_multi_set_model_params(cfnmpc_multi *m, const double *p);
+/* cfnmpc_set_weights_batch for every shard (both create variants): HOST arrays [B][17] / [B][13] of the whole fleet; validated
+ * as a whole first (a bad row leaves every shard unchanged; an allocation or copy failure in a later shard does not undo the
+ * earlier ones) */
+int cfnmpc_multi_set_weights_batch(cfnmpc_multi *m, const double *W, const double *WN);
 /* Solution sensitivities w.r.t. x0 over the whole fleet (cfnmpc_eval_sens_x0 per shard): host arrays in the caller's order,
  * synchronous; for cfnmpc_multi_create_horizons the range is limited by the shortest horizon, as for a fleet. */
 int cfnmpc_multi_eval_sens_x0(cfnmpc_multi *m, double act_tol);
