@@ -31,6 +31,8 @@ SYMBOLS = [
     "cfnmpc_set_weights_batch", "cfnmpc_get_weights_batch", "cfnmpc_fleet_set_weights_batch", "cfnmpc_multi_set_weights_batch",
     "cfnmpc_eval_sens_x0", "cfnmpc_get_sens_x0", "cfnmpc_get_sens_active", "cfnmpc_fleet_eval_sens_x0", "cfnmpc_fleet_get_sens_x0",
     "cfnmpc_multi_eval_sens_x0", "cfnmpc_multi_get_sens_x0",
+    "cfnmpc_eval_nlp", "cfnmpc_get_nlp_stats", "cfnmpc_get_nlp_multipliers", "cfnmpc_fleet_eval_nlp", "cfnmpc_fleet_get_nlp_stats",
+    "cfnmpc_multi_eval_nlp", "cfnmpc_multi_get_nlp_stats",
 ]
 ABI_VERSION = 9   # CFNMPC_ABI_VERSION of the include/cfnmpc.h this binding was written against
 
@@ -105,6 +107,13 @@ def lib():
     L.cfnmpc_fleet_get_sens_x0.argtypes = [vp, i32, i32, vp, vp, i32, vp]
     L.cfnmpc_multi_eval_sens_x0.argtypes = [vp, dbl]
     L.cfnmpc_multi_get_sens_x0.argtypes = [vp, i32, i32, vp, vp]
+    L.cfnmpc_eval_nlp.argtypes = [vp, i32, vp]
+    L.cfnmpc_get_nlp_stats.argtypes = [vp, vp, vp, i32, vp]
+    L.cfnmpc_get_nlp_multipliers.argtypes = [vp, vp, vp, i32, vp]
+    L.cfnmpc_fleet_eval_nlp.argtypes = [vp, vp]
+    L.cfnmpc_fleet_get_nlp_stats.argtypes = [vp, vp, vp, i32, vp]
+    L.cfnmpc_multi_eval_nlp.argtypes = [vp]
+    L.cfnmpc_multi_get_nlp_stats.argtypes = [vp, vp, vp]
     L.cfnmpc_sim.argtypes = [i32, vp, vp, dbl, i32, vp, i32, vp]
     L.cfnmpc_estimate.argtypes = [i32, vp, vp, vp, dbl, i32, dbl, i32, vp, vp, vp]
     L.cfnmpc_debug_get_linearisation.argtypes = [vp, vp, vp, vp]

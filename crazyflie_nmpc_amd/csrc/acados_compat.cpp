@@ -38,6 +38,10 @@ struct Shim {
     // after a solve, all stages at once (0: not yet, 1: held, -1: the engine refused)
     int sens_state = 0;
     double sdu[N][NU][NX], sdx[N + 1][NX][NX];
+    // NLP cost and KKT residuals at the iterate of the last acados_solve() (ocp_nlp_eval_cost / ocp_nlp_eval_residuals /
+    // ocp_nlp_get): evaluated at the first request after a solve (0: not yet, 1: held, -1: the engine refused)
+    int nlp_state = 0;
+    double nlp_cost = 0.0, nlp_res[3] = {0.0, 0.0, 0.0};
     ocp_nlp_in in;
     ocp_nlp_out out;
     ocp_nlp_solver solver;
@@ -136,6 +140,7 @@ int acados_cfnmpc_init_iterate(int mode) {
     if (!g) return 1;
     if (cfnmpc_set_x0(g->s, g->lbx, 0, nullptr) != CFNMPC_OK) return 1;
     if (cfnmpc_init_iterate(g->s, mode, nullptr) != CFNMPC_OK) return 1;
+    g->nlp_state = 0;   // another iterate: what ocp_nlp_get held belongs to the old one
     // ocp_nlp_out_get reads the host copy of the iterate: refresh it
     return cfnmpc_get_iterate(g->s, g->x, g->u, 0, nullptr) == CFNMPC_OK ? 0 : 1;
 }
@@ -239,6 +244,7 @@ int acados_solve(void) {
     double res = 0.0;
     // inputs in, one RTI step, iterate and statistics out: one transfer each way, one synchronisation
     g->sens_state = 0;
+    g->nlp_state = 0;
     if (cfnmpc_step_host(g->s, g->lbx, g->yref, g->yref_e, g->u, g->x, &status, &iters, &res, nullptr) != CFNMPC_OK) return 1;
     g->out.inf_norm_res = res;
     g->out.qp_iter = iters;
@@ -293,6 +299,28 @@ void ocp_nlp_eval_param_sens(ocp_nlp_solver*, char* field, int stage, int index,
         for (int i = 0; i < NX; i++) o->x[k][i] = g->sdx[k][i][index];
     for (int k = 0; k < N; k++)
         for (int a = 0; a < NU; a++) o->u[k][a] = g->sdu[k][a][index];
+}
+
+// NLP cost and KKT residuals (cfnmpc_eval_nlp) at the engine's current iterate, with the data the last acados_solve() put in force
+// (before any solve: what acados_create() left).  One evaluation serves both calls and the getter until the next solve.
+static bool nlp_ensure() {
+    if (!g) return false;
+    if (g->nlp_state == 0) {
+        const bool ok = cfnmpc_eval_nlp(g->s, 0, nullptr) == CFNMPC_OK &&
+                        cfnmpc_get_nlp_stats(g->s, &g->nlp_cost, g->nlp_res, CFNMPC_ON_HOST, nullptr) == CFNMPC_OK;
+        g->nlp_state = ok ? 1 : -1;
+    }
+    return g->nlp_state == 1;
+}
+void ocp_nlp_eval_cost(ocp_nlp_solver*, ocp_nlp_in*, ocp_nlp_out*) { (void)nlp_ensure(); }
+void ocp_nlp_eval_residuals(ocp_nlp_solver*, ocp_nlp_in*, ocp_nlp_out*) { (void)nlp_ensure(); }
+// "cost_value", "res_stat", "res_eq", "res_ineq": one double; any other field (and a refused evaluation) leaves *value untouched
+void ocp_nlp_get(ocp_nlp_config*, ocp_nlp_solver*, const char* field, void* value) {
+    if (!field || !value) return;
+    const int which = !std::strcmp(field, "cost_value") ? 0 : (!std::strcmp(field, "res_stat") ? 1 : (!std::strcmp(field, "res_eq") ? 2 :
+                      (!std::strcmp(field, "res_ineq") ? 3 : -1)));
+    if (which < 0 || !nlp_ensure()) return;
+    *static_cast<double*>(value) = which == 0 ? g->nlp_cost : g->nlp_res[which - 1];
 }
 
 // ---------------------------------------------------------------- predictor (sim solver)

@@ -80,6 +80,11 @@ struct cfnmpc_solver {
     cfn::SensArgs sens;
     double* sens_stage;
     size_t sens_stage_doubles;
+    // NLP evaluation (cfnmpc_eval_nlp): cost [B] and residuals [B][3] (allocated with the solver), costates and reduced gradient
+    // (allocated at the first evaluation that keeps them), and what the last evaluation left (0: none yet, 1: cost and residuals,
+    // 2: the multipliers too)
+    cfn::NlpArgs nlp;
+    int nlp_state;
 };
 
 namespace {
@@ -310,6 +315,8 @@ int cfnmpc_create(cfnmpc_solver** out, int batch, const cfnmpc_opts* opts) {
     std::memset(&s->sqp, 0, sizeof s->sqp);
     s->h_sqp_cnt = nullptr;
     s->sqp_ev = nullptr;
+    std::memset(&s->nlp, 0, sizeof s->nlp);
+    s->nlp_state = 0;
     int simds = 1024;   // SIMDs of the device the solver is created on
     {
         hipDeviceProp_t prop;
@@ -486,6 +493,9 @@ int cfnmpc_create(cfnmpc_solver** out, int batch, const cfnmpc_opts* opts) {
     if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->sqp.iter, (size_t)batch);
     if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->sqp.done, (size_t)batch);
     if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->sqp.cnt, 2);
+    // NLP evaluation (cfnmpc_eval_nlp): cost and the three residuals
+    if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->nlp.cost, (size_t)batch);
+    if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->nlp.res, (size_t)batch * 3);
     if (s->overlap) {
         if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->AR2, NW16 * N * cfn::SZ_A);
         if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->BR2, NW16 * N * cfn::SZ_B);
@@ -1167,6 +1177,51 @@ int cfnmpc_get_stats(cfnmpc_solver* s, int* status, int* qp_iter, double* res, i
     if (qp_iter) HIP_TRY(hipMemcpyAsync(qp_iter, s->P.iters, B * sizeof(int), kind, st));
     if (res) HIP_TRY(hipMemcpyAsync(res, s->P.res, B * sizeof(double), kind, st));
     if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
+
+// ---- NLP evaluation at the current iterate --------------------------------------------------------
+int cfnmpc_eval_nlp(cfnmpc_solver* s, int keep_multipliers, void* stream) {
+    if (!s || (keep_multipliers != 0 && keep_multipliers != 1)) return CFNMPC_EINVAL;
+    DeviceGuard dg(s);
+    cfn::NlpArgs& A = s->nlp;
+    if (keep_multipliers && !A.gu) {   // costates in the x-iterate's layout, reduced gradient in the u-iterate's (spare block included)
+        const size_t NW = (size_t)s->P.NW + 1, N = s->P.N;
+        double *pi = nullptr, *gu = nullptr;
+        int rc = dev_alloc(s, &pi, NW * (N + 1) * cfn::SZ_V13);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &gu, NW * 4 * N * 4);
+        if (rc != CFNMPC_OK) return rc;   // (what was allocated stays with the solver; the next call allocates again)
+        A.pi = pi; A.gu = gu;
+    }
+    cfn::NlpArgs a = A;
+    if (!keep_multipliers) a.pi = a.gu = nullptr;
+    cfn::launch_nlp_eval(s->P, a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    s->nlp_state = keep_multipliers ? 2 : 1;
+    return CFNMPC_OK;
+}
+
+int cfnmpc_get_nlp_stats(cfnmpc_solver* s, double* cost, double* res, int on_device, void* stream) {
+    if (!s || s->nlp_state == 0 || (!cost && !res)) return CFNMPC_EINVAL;
+    DeviceGuard dg(s);
+    hipStream_t st = (hipStream_t)stream;
+    const hipMemcpyKind kind = !is_host(on_device) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const size_t B = s->P.B;
+    if (cost) HIP_TRY(hipMemcpyAsync(cost, s->nlp.cost, B * sizeof(double), kind, st));
+    if (res) HIP_TRY(hipMemcpyAsync(res, s->nlp.res, B * 3 * sizeof(double), kind, st));
+    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
+
+int cfnmpc_get_nlp_multipliers(cfnmpc_solver* s, double* pi, double* gu, int on_device, void* stream) {
+    if (!s || s->nlp_state != 2 || (!pi && !gu)) return CFNMPC_EINVAL;
+    DeviceGuard dg(s);
+    const int N = s->P.N;
+    if (pi) {
+        const int rc = get_field(s, pi, on_device, N + 1, 13, 1, 0, N + 1, s->nlp.pi, (hipStream_t)stream);
+        if (rc != CFNMPC_OK) return rc;
+    }
+    if (gu) return get_field(s, gu, on_device, N, 4, 0, 0, N, s->nlp.gu, (hipStream_t)stream);
     return CFNMPC_OK;
 }
 

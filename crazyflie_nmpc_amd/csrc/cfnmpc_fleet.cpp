@@ -493,6 +493,38 @@ int cfnmpc_fleet_get_sqp_stats(cfnmpc_fleet* f, int* status, int* sqp_iter, doub
     });
 }
 
+// ---- NLP evaluation at every bucket's current iterate (include/cfnmpc.h: cfnmpc_eval_nlp) -------------
+int cfnmpc_fleet_eval_nlp(cfnmpc_fleet* f, void* stream) {
+    if (!f) return CFNMPC_EINVAL;
+    FleetDevice fd(f);
+    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) { return cfnmpc_eval_nlp(b.s, 0, st); });
+}
+
+// rows in the fleet's vehicle order: cost [B], res [B][3]
+int cfnmpc_fleet_get_nlp_stats(cfnmpc_fleet* f, double* cost, double* res, int on_device, void* stream) {
+    if (!f || (!cost && !res)) return CFNMPC_EINVAL;
+    FleetDevice fd(f);
+    if (on_device == CFNMPC_ON_HOST || on_device == CFNMPC_ON_HOST_ASYNC) {   // (host arrays: synchronous)
+        for (Bucket& b : f->bk) {
+            f->h_rows.resize((size_t)4 * b.count);
+            double* hc = f->h_rows.data(), *hr = hc + b.count;
+            RC_TRY(cfnmpc_get_nlp_stats(b.s, hc, hr, CFNMPC_ON_HOST, stream));
+            for (int r = 0; r < b.count; r++) {
+                if (cost) cost[b.idx[r]] = hc[r];
+                if (res) std::copy_n(hr + (size_t)r * 3, 3, res + (long)b.idx[r] * 3);
+            }
+        }
+        return CFNMPC_OK;
+    }
+    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) {
+        RC_TRY(staging(b));
+        RC_TRY(cfnmpc_get_nlp_stats(b.s, b.d_rows, b.d_rows + b.count, 1, st));
+        if (cost) rows<double, false>(b.d_rows, cost, b.d_idx, b.count, 1, 1, st);
+        if (res) rows<double, false>(b.d_rows + b.count, res, b.d_idx, b.count, 3, 3, st);
+        return (int)CFNMPC_OK;
+    });
+}
+
 // ---- solution sensitivities with respect to x0 (include/cfnmpc.h: cfnmpc_eval_sens_x0) --------------
 int cfnmpc_fleet_eval_sens_x0(cfnmpc_fleet* f, double act_tol, void* stream) {
     if (!f) return CFNMPC_EINVAL;

@@ -3587,6 +3587,222 @@ __device__ __forceinline__ void sqp_check_body(const Params& P, const SqpArgs& A
 __global__ __launch_bounds__(64) void k_sqp_check(Params P, SqpArgs A) { sqp_check_body<false>(P, A); }
 __global__ __launch_bounds__(64) void k_sqp_check_par(Params P, SqpArgs A) { sqp_check_body<true>(P, A); }
 
+// =============================================================================================
+// NLP evaluation at the current iterate (cfnmpc_eval_nlp)
+// =============================================================================================
+// Cost, KKT residuals, costates and reduced gradient of the NLP at w = (P.xit, P.uit), from the data in force (x0, yref, weights
+// with the cost scaling applied, box, model constants, P.erk_steps); reads nothing a solve wrote but the iterate and writes
+// nothing a solve, getter or option reads.  Lane per instance, 64 per wavefront, 13-vectors and reference rows through LDS tiles
+// as in k_sqp_check (every global access of the wave a contiguous run), the loads of stage k - 1 in flight during stage k.
+// BACKWARD over the stages, the costate lam = pi_{k+1} carried in registers; per stage and RK4 sub-step (last sub-step first):
+//   1. the sub-step's start state (sub-step m of M > 1: m plain RK4 steps from x_k, RECOMPUTED -- at most M (M - 1) / 2 = 28
+//      extra steps at M = 8 beside the 8 of the sweep itself, against 13 (M - 1) doubles per lane of LDS to park them: 46 KB at
+//      M = 8 on top of the 37 KB below, static, i.e. one wavefront per compute unit instead of four for every M, the default 1
+//      included);
+//   2. one RK4 step from there, the stage points X2..X4 (q | v | w: nothing depends on position) parked in a lane-private
+//      LDS slab; behind the interval's last sub-step the defect x_{k+1} - Phi(x_k, u_k);
+//   3. the step in reverse mode: four products (df/dx)' kbar at X4..X1 (cfnmpc_model.hpp: jtvp) pull lam back to the sub-step's
+//      start, the kbar's rows 9..12 summed for (df/du)' -- A_k' lam and B_k' lam without A_k or B_k.
+// Then pi_k = s Q (x_k - yref_k) + A_k' lam, g_k = s R (u_k - yref_k^u) + B_k' lam, the natural residual of the box and the cost.
+// The RK stages and the reverse products are LOOPS (one f_expl, one Jacobian point live at a time): unrolled, the scheduler
+// builds the four independent Jacobian points side by side and the kernel spills past 512 registers.
+// A.pi (x-iterate layout, internal order) / A.gu (u-iterate layout) are written when given; NaN sticks (max_nan).
+static_assert(div_ok(68, 64 * 17), "k_nlp_eval: e / 68 by multiply-shift");
+template <bool PAR>
+__device__ __forceinline__ void nlp_eval_body(const Params& P, const NlpArgs& A) {
+    __shared__ double tx[64 * 13], ty[64 * 17], pts[3 * 10 * 64], xn[13 * 64], ws[17];
+    const int N = P.N;
+    const int tid = threadIdx.x;
+    const int raw = blockIdx.x * 64 + tid;
+    const bool valid = raw < P.B;
+    const int inst = valid ? raw : P.NW * 4 + (tid & 3);   // idle lanes: spare block
+    const size_t w = (size_t)(inst >> 2);
+    const int q = inst & 3;
+    const int w0 = blockIdx.x * 16;
+    const int M = P.erk_steps;
+    const double h = P.dt / M;
+    const ModelK<PAR> mk = model_k<PAR>(P, inst);
+    const size_t i4b = P.v4b ? ((size_t)w * N * 4 + q) * 4 : (size_t)inst * N * 4;   // this lane's 4-vectors (Params.v4b)
+    const size_t i4s = P.v4b ? 16 : 4;
+    const bool keep = A.pi != nullptr;
+    auto el13 = [&](const double* f, int e, int stages, int k) -> gdouble* {   // (k_forward's accessor)
+        const int bk = (int)(__umul24((unsigned)e, div_magic(52)) >> 16), off = e - bk * 52;
+        const unsigned bo = (__umul24((unsigned)imin(bk, P.NW - w0), (unsigned)(stages * SZ_V13)) + (unsigned)off) * 8u;
+        const char* base = (const char*)(gm(f) + ((size_t)w0 * stages + k) * SZ_V13);
+        return (gdouble*)(base + bo);
+    };
+    auto el17 = [&](const double* f, int e, int k) -> gdouble* {   // the same for the reference rows (68 doubles per block and stage)
+        const int bk = (int)(__umul24((unsigned)e, div_magic(68)) >> 16), off = e - bk * 68;
+        const unsigned bo = (__umul24((unsigned)imin(bk, P.NW - w0), (unsigned)(N * SZ_Y)) + (unsigned)off) * 8u;
+        const char* base = (const char*)(gm(f) + ((size_t)w0 * N + k) * SZ_Y);
+        return (gdouble*)(base + bo);
+    };
+    // weights in force (effective values: the cost scaling is applied on the host), states in the EXTERNAL order; read where they are
+    // used, without a branch: the uniform stage weights from a 17-entry LDS table (as kernel arguments they hold 34 scalar
+    // registers over the whole sweep), the per-instance row loaded either way (from x0 while unset)
+    if (tid == 0) SFOR(e, 0, 17, { ws[e] = P.W[e]; });
+    const bool wt = P.wtab != nullptr;
+    // wrow: this lane's row of the weight table; WITHOUT a table it points at P.x0 -- any readable 30 doubles: the loads from it
+    // below ("wl") are then dummies, in bounds ((NW + 1) * 52 doubles, the same address in every lane) and dropped by the select
+    // next to each of them.  Loading only under `wt` makes the compiler branch around every single load (34 per stage).
+    const gdouble* wrow = wt ? gm(P.wtab) + (size_t)inst * WT_STRIDE : gm(P.x0);
+    struct Ld { double x[13], y[17], u[4]; };   // stage k: state and reference row (tile elements), inputs
+    auto issue = [&](int k, Ld& L) {
+        SFOR(j, 0, 13, { L.x[j] = *el13(P.xit, tid + 64 * j, N + 1, k); });
+        SFOR(j, 0, 17, { L.y[j] = *el17(P.yref, tid + 64 * j, k); });
+        SFOR(a, 0, 4, { L.u[a] = gm(P.uit)[i4b + (size_t)k * i4s + a]; });
+    };
+    auto deposit = [&](const Ld& L) {   // hands the tiles to the next stage
+        __syncthreads();
+        SFOR(j, 0, 13, { tx[tid + 64 * j] = L.x[j]; });
+        SFOR(j, 0, 17, { ty[tid + 64 * j] = L.y[j]; });
+        __syncthreads();
+    };
+    // pi_k in the x-iterate's layout through the (then idle) stage-point slab
+    auto store_pi = [&](const double (&lam)[13], int k) {
+        __syncthreads();
+        SFOR(i, 0, 13, { pts[tid * 13 + i] = lam[ext_of(i)]; });
+        __syncthreads();
+        SFOR(j, 0, 13, { *el13(A.pi, tid + 64 * j, N + 1, k) = pts[tid + 64 * j]; });
+        __syncthreads();
+    };
+    Ld ld;
+    double lam[13], u[4];   // pi_{k+1} (model vectors in the EXTERNAL order), u_k
+    double cost = 0.0, r_stat = 0.0, r_eq = 0.0, r_ineq = 0.0;
+    {   // terminal stage: pi_N = s_e W_N (x_N - yref_e)
+        double tn[13], te[13];
+        SFOR(j, 0, 13, { tn[j] = *el13(P.xit, tid + 64 * j, N + 1, N); te[j] = *el13(P.yref_e, tid + 64 * j, 1, 0); });
+        issue(N - 1, ld);
+        SFOR(j, 0, 13, { tx[tid + 64 * j] = tn[j]; ty[tid + 64 * j] = te[j]; });
+        __syncthreads();
+        SFOR(e, 0, 13, {
+            constexpr int i = int_of(e);
+            const double wl = wrow[WT_QN + i];   // (dummy without a table: see wrow)
+            const double wn = wt ? wl : P.WN[e];
+            const double xe = tx[tid * 13 + i];
+            const double d = xe - ty[tid * 13 + i];
+            xn[e * 64 + tid] = xe;
+            lam[e] = wn * d;
+            cost += 0.5 * d * lam[e];
+        });
+        if (keep) store_pi(lam, N);
+        deposit(ld);
+        SFOR(a, 0, 4, { u[a] = ld.u[a]; });
+    }
+    // at the top of stage k the tiles hold x_k and yref_k, u holds u_k, xn holds x_{k+1}
+#pragma unroll 1
+    for (int k = N - 1; k >= 0; k--) {
+        double gs[4] = {0.0, 0.0, 0.0, 0.0};   // sum of kbar[9..12] over the RK points: (df/du)' acts on it once (df/du depends on u only)
+        double qp[3], g[4], lo[4], hi[4];   // the position rows of s Q (x_k - yref_k): added behind the reverse sweep, which reads lam[0..2]
+        // one RK4 sub-step forward (stage points parked) and in reverse; LAST: sub-step 0, the last one in this order -- the loads of
+        // stage k - 1 are in flight during its forward half and take the tiles over before its reverse half, so that they hold no
+        // register while the reverse sweep needs most; the stage terms that read the tiles are formed before that
+        auto substep = [&](int m, auto last_) {
+            constexpr bool LAST = decltype(last_)::value;
+            double xs[13], xt[13], kk[13], acc[13], sx[10];   // sx: sum of the Xbar's rows 3..12 (+ s Q (x_k - yref_k) in the last sub-step)
+            if (LAST && k > 0) issue(k - 1, ld);
+            SFOR(e, 0, 13, { xs[e] = tx[tid * 13 + int_of(e)]; });
+            // RK4 steps from x_k: j < m plain ones to the start state of sub-step m, then the sub-step itself (the stage points of every
+            // step are parked; the last step's stay)
+#pragma unroll 1
+            for (int j = LAST ? 0 : -m; j <= 0; j++) {
+                if (j > (LAST ? 0 : -m)) SFOR(e, 0, 13, { xs[e] += (h / 6.0) * acc[e]; });
+                SFOR(e, 0, 13, { xt[e] = xs[e]; acc[e] = 0.0; });
+#pragma unroll 1
+                for (int p = 0; p < 4; p++) {
+                    f_expl(xt, u, kk, mk);
+                    const double cw = (p == 0 || p == 3) ? 1.0 : 2.0, cs = p == 2 ? h : 0.5 * h;
+                    SFOR(e, 0, 13, { acc[e] += cw * kk[e]; });
+                    if (p < 3) {
+                        SFOR(e, 0, 13, { xt[e] = xs[e] + cs * kk[e]; });
+                        SFOR(i, 0, 10, { pts[(p * 10 + i) * 64 + tid] = xt[3 + i]; });
+                    }
+                }
+            }
+            if (m == M - 1) SFOR(e, 0, 13, { r_eq = max_nan(r_eq, fabs(xn[e * 64 + tid] - (xs[e] + (h / 6.0) * acc[e]))); });
+            if (LAST) {   // (xs = x_k here)
+                SFOR(e, 0, 13, {
+                    constexpr int i = int_of(e);
+                    const double wl = wrow[i];   // (dummy without a table: see wrow)
+                    const double wq = wt ? wl : ws[e];
+                    const double d = xs[e] - ty[tid * 17 + i];
+                    xn[e * 64 + tid] = xs[e];
+                    const double qd = wq * d;
+                    if (e < 3) qp[e] = qd; else sx[e < 3 ? 0 : e - 3] = qd;
+                    cost += 0.5 * d * qd;
+                });
+                SFOR(a, 0, 4, {
+                    const double wl = wrow[WT_R + a];   // (dummy without a table: see wrow)
+                    const double wr = wt ? wl : ws[13 + a];
+                    const double d = u[a] - ty[tid * 17 + 13 + a];
+                    g[a] = wr * d;
+                    cost += 0.5 * d * g[a];
+                });
+                if (k > 0) deposit(ld);
+                SFOR(a, 0, 4, { lo[a] = P.u_min; hi[a] = P.u_max; });
+                if (P.lbs) SFOR(a, 0, 4, { lo[a] = gm(P.lbs)[i4b + (size_t)k * i4s + a]; hi[a] = gm(P.ubs)[i4b + (size_t)k * i4s + a]; });
+            }
+            // reverse mode: kbar_4 = h/6 lam, kbar_3 = h/3 lam + h Xbar_4, kbar_2 = h/3 lam + h/2 Xbar_3, kbar_1 = h/6 lam + h/2 Xbar_2,
+            // Xbar_i = (df/dx)(X_i)' kbar_i, lam <- lam + sum Xbar_i
+            double kb[13], xb[13];
+            SFOR(e, 0, 13, { xb[e] = 0.0; });
+            if (!LAST) SFOR(i, 0, 10, { sx[i] = 0.0; });
+#pragma unroll 1
+            for (int p = 3; p >= 0; p--) {   // one Jacobian point live at a time
+                const double ca = (p == 0 || p == 3) ? h / 6.0 : h / 3.0;
+                const double cb = p == 3 ? 0.0 : (p == 2 ? h : 0.5 * h);
+                SFOR(e, 0, 13, { kb[e] = ca * lam[e] + cb * xb[e]; });
+                if (p > 0) SFOR(i, 0, 10, { xt[3 + i] = pts[((p - 1) * 10 + i) * 64 + tid]; });
+                else SFOR(i, 0, 10, { xt[3 + i] = xs[3 + i]; });
+                JacPoint J;
+                jac_point(xt, J);
+                jtvp(J, kb, xb, mk);
+                SFOR(i, 0, 4, { gs[i] += kb[9 + i]; });
+                SFOR(i, 0, 10, { sx[i] += xb[3 + i]; });
+            }
+            SFOR(i, 0, 10, { lam[3 + i] += sx[i]; });
+        };
+#pragma unroll 1
+        for (int m = M - 1; m > 0; m--) substep(m, std::false_type());
+        substep(0, std::true_type());
+        // pi_k, g_k, residuals of the box
+        SFOR(e, 0, 3, { lam[e] += qp[e]; });
+        SFOR(a, 0, 4, {
+            constexpr double sa = (a < 2) ? 1.0 : -1.0;             // w1 w2 | -w3 -w4   (cfnmpc_model.hpp: ju_col)
+            constexpr double sb = (a == 0 || a == 3) ? 1.0 : -1.0;  // w1 -w2 -w3 w4
+            constexpr double sc = (a == 0 || a == 2) ? 1.0 : -1.0;  // w1 -w2 w3 -w4
+            g[a] += 2.0 * u[a] * (mk.kt() * gs[0] + mk.ka() * sa * gs[1] + mk.kb() * sb * gs[2] + mk.kc() * sc * gs[3]);
+            double c = u[a] - g[a];   // clip(u - g, lb, ub) by comparisons: NaN stays
+            c = c < lo[a] ? lo[a] : c;
+            c = c > hi[a] ? hi[a] : c;
+            r_stat = max_nan(r_stat, fabs(u[a] - c));
+            r_ineq = max_nan(r_ineq, fmax(lo[a] - u[a], u[a] - hi[a]));
+        });
+        if (keep) {
+            if (valid) SFOR(a, 0, 4, { gm(A.gu)[i4b + (size_t)k * i4s + a] = g[a]; });
+            store_pi(lam, k);
+        }
+        SFOR(a, 0, 4, { u[a] = ld.u[a]; });
+    }
+    {   // x_0 = x0 (xn holds x_0 now)
+        double t[13];
+        SFOR(j, 0, 13, { t[j] = *el13(P.x0, tid + 64 * j, 1, 0); });
+        __syncthreads();
+        SFOR(j, 0, 13, { tx[tid + 64 * j] = t[j]; });
+        __syncthreads();
+        SFOR(e, 0, 13, { r_eq = max_nan(r_eq, fabs(xn[e * 64 + tid] - tx[tid * 13 + int_of(e)])); });
+    }
+    if (valid) {
+        if (cost != cost || r_stat != r_stat || r_eq != r_eq) cost = r_stat = r_eq = r_ineq = __builtin_nan("");   // a NaN anywhere in the row: in every result
+        gm(A.cost)[raw] = cost;
+        gm(A.res)[(size_t)raw * 3 + 0] = r_stat;
+        gm(A.res)[(size_t)raw * 3 + 1] = r_eq;
+        gm(A.res)[(size_t)raw * 3 + 2] = r_ineq;
+    }
+}
+__global__ __launch_bounds__(64) void k_nlp_eval(Params P, NlpArgs A) { nlp_eval_body<false>(P, A); }
+__global__ __launch_bounds__(64) void k_nlp_eval_par(Params P, NlpArgs A) { nlp_eval_body<true>(P, A); }
+
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
@@ -3806,6 +4022,10 @@ void launch_reinit_failed(const Params& P, hipStream_t st) {
 void launch_sqp_check(const Params& P, const SqpArgs& A, hipStream_t st) {
     if (P.mpar) hipLaunchKernelGGL(k_sqp_check_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
     else hipLaunchKernelGGL(k_sqp_check, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
+}
+void launch_nlp_eval(const Params& P, const NlpArgs& A, hipStream_t st) {
+    if (P.mpar) hipLaunchKernelGGL(k_nlp_eval_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
+    else hipLaunchKernelGGL(k_nlp_eval, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
 }
 void launch_init_iterate(const Params& P, int mode, hipStream_t st) {
     if (P.mpar) hipLaunchKernelGGL(k_init_iterate_par, dim3((P.B + 255) / 256), dim3(256), 0, st, P, mode);

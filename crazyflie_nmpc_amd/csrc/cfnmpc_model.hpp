@@ -213,6 +213,28 @@ __device__ __forceinline__ void jvp(const JacPoint& J, const double* __restrict_
     o[7] = o7; o[8] = o8; o[9] = o9; o[10] = o10; o[11] = o11; o[12] = o12;
 }
 
+// out = (df/dx)(point)' v: the transposed product of jvp<true, true> at the same Jacobian point (reverse mode, k_nlp_eval).
+// v, out: 13 entries; out[0..2] = 0 (nothing depends on position).
+template <class K = NomK>
+__device__ __forceinline__ void jtvp(const JacPoint& J, const double* __restrict__ v, double* __restrict__ o, const K& mk = K()) {
+    const double q1 = J.q[0], q2 = J.q[1], q3 = J.q[2], q4 = J.q[3];
+    const double vx = J.v[0], vy = J.v[1], vz = J.v[2];
+    const double wx = J.w[0], wy = J.w[1], wz = J.w[2];
+    const double p0 = v[0], p1 = v[1], p2 = v[2], a = v[3], b = v[4], c = v[5], d = v[6];
+    const double g7 = 2 * mk.g0() * v[7], g8 = 2 * mk.g0() * v[8], g9 = 4 * mk.g0() * v[9];
+    o[0] = 0; o[1] = 0; o[2] = 0;
+    o[3] = J.Jpq[0] * p0 + J.Jpq[4] * p1 + J.Jpq[8] * p2 + 0.5 * (wx * b + wy * c + wz * d) + q3 * g7 - q2 * g8 - q1 * g9;
+    o[4] = J.Jpq[1] * p0 + J.Jpq[5] * p1 + J.Jpq[9] * p2 + 0.5 * (-wx * a - wz * c + wy * d) - q4 * g7 - q1 * g8;
+    o[5] = J.Jpq[2] * p0 + J.Jpq[6] * p1 + J.Jpq[10] * p2 + 0.5 * (-wy * a + wz * b - wx * d) + q1 * g7 - q4 * g8;
+    o[6] = J.Jpq[3] * p0 + J.Jpq[7] * p1 + J.Jpq[11] * p2 + 0.5 * (-wz * a - wy * b + wx * c) - q2 * g7 - q3 * g8 - q4 * g9;
+    o[7] = J.R[0] * p0 + J.R[3] * p1 + J.R[6] * p2 - wz * v[8] + wy * v[9];
+    o[8] = J.R[1] * p0 + J.R[4] * p1 + J.R[7] * p2 + wz * v[7] - wx * v[9];
+    o[9] = J.R[2] * p0 + J.R[5] * p1 + J.R[8] * p2 - wy * v[7] + wx * v[8];
+    o[10] = 0.5 * (-q2 * a + q1 * b + q4 * c - q3 * d) + vz * v[8] - vy * v[9] + mk.kwy() * (wz * v[11]) + mk.kwz() * (wy * v[12]);
+    o[11] = 0.5 * (-q3 * a - q4 * b + q1 * c + q2 * d) - vz * v[7] + vx * v[9] + mk.kwx() * (wz * v[10]) + mk.kwz() * (wx * v[12]);
+    o[12] = 0.5 * (-q4 * a + q3 * b - q2 * c + q1 * d) + vy * v[7] - vx * v[8] + mk.kwx() * (wy * v[10]) + mk.kwy() * (wx * v[11]);
+}
+
 // df/du column c (rows 9..12 only): d v'_z, d w'_x, d w'_y, d w'_z
 __device__ __forceinline__ void ju_col(int c, const double* __restrict__ u, double* __restrict__ o4) {
     const double uc = 2.0 * u[c];

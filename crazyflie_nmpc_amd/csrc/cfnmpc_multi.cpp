@@ -390,6 +390,30 @@ int cfnmpc_multi_get_stats(cfnmpc_multi* m, int* status, int* qp_iter, double* r
     return sync_all(m);
 }
 
+// ---- NLP evaluation over the whole fleet (cfnmpc_eval_nlp per shard; host arrays in the caller's order, synchronous) ----------
+int cfnmpc_multi_eval_nlp(cfnmpc_multi* m) {
+    if (!m) return CFNMPC_EINVAL;
+    for (Shard& s : m->sh) RC_TRY_SYNC(m, m->mixed ? cfnmpc_fleet_eval_nlp(s.f, s.st) : cfnmpc_eval_nlp(s.s, 0, s.st));
+    return sync_all(m);
+}
+
+int cfnmpc_multi_get_nlp_stats(cfnmpc_multi* m, double* cost, double* res) {
+    if (!m || (!cost && !res)) return CFNMPC_EINVAL;
+    if (m->mixed) {
+        for (Shard& s : m->sh) {
+            const size_t n = s.idx.size();
+            s.h.resize(4 * n);
+            RC_TRY(cfnmpc_fleet_get_nlp_stats(s.f, s.h.data(), s.h.data() + n, CFNMPC_ON_HOST, s.st));
+            if (cost) from_shard(s, s.h.data(), cost, 1);
+            if (res) from_shard(s, s.h.data() + n, res, 3);
+        }
+        return CFNMPC_OK;
+    }
+    for (Shard& s : m->sh)
+        RC_TRY_SYNC(m, cfnmpc_get_nlp_stats(s.s, cost ? cost + s.lo : nullptr, res ? res + (size_t)s.lo * 3 : nullptr, CFNMPC_ON_HOST_ASYNC, s.st));
+    return sync_all(m);
+}
+
 // ---- solution sensitivities with respect to x0 (host arrays over the whole fleet, caller's order; synchronous) ---------------
 int cfnmpc_multi_eval_sens_x0(cfnmpc_multi* m, double act_tol) {
     if (!m) return CFNMPC_EINVAL;

@@ -258,6 +258,15 @@ struct SqpArgs {
 };
 // after the step of iteration A.j, BEFORE the host swaps the iterate buffers (reads P.xit / P.uit and P.xitn / P.uitn)
 void launch_sqp_check(const Params& P, const SqpArgs& A, hipStream_t st);
+// NLP evaluation at the current iterate (cfnmpc_eval_nlp): results owned by the solver (not part of
+// Params: no kernel of a solve sees them)
+struct NlpArgs {
+    double* cost;   // [B]
+    double* res;    // [B][3]: res_stat, res_eq, res_ineq
+    double* pi;     // costates in the x-iterate's layout, (N + 1) x SZ_V13 per block, internal order; NULL: not kept
+    double* gu;     // reduced gradient in the u-iterate's layout (Params.v4b); NULL with pi
+};
+void launch_nlp_eval(const Params& P, const NlpArgs& A, hipStream_t st);
 // solution sensitivities with respect to x0 (cfnmpc_eval_sens_x0 / cfnmpc_get_sens_x0; kernels: cfnmpc_sens.hpp, DESIGN.md
 // section 5.14): buffers owned by the solver, allocated at its first evaluation (not part of Params: no RTI kernel sees them)
 struct SensArgs {

@@ -187,6 +187,18 @@ class MixedHorizonFleet:
         _check(self._L.cfnmpc_fleet_get_u(self._h, int(stage), p, dev, st), "cfnmpc_fleet_get_u")
         return out
 
+    def eval_nlp(self, stream=None):
+        """cfnmpc_fleet_eval_nlp: NLP cost and KKT residuals at every bucket's current iterate (BatchSolver.eval_nlp; the
+        multipliers have one shape per horizon: through the bucket's solver)"""
+        _check(self._L.cfnmpc_fleet_eval_nlp(self._h, _launch_stream(stream, self._device)), "cfnmpc_fleet_eval_nlp")
+
+    def nlp_stats(self):
+        """-> (cost [B], res [B, 3] = res_stat, res_eq, res_ineq) of the last eval_nlp, in the fleet's vehicle order"""
+        cost = np.empty(self.B); res = np.empty((self.B, 3))
+        _check(self._L.cfnmpc_fleet_get_nlp_stats(self._h, cost.ctypes.data_as(C.c_void_p), res.ctypes.data_as(C.c_void_p), 0,
+                                                  _launch_stream(None, self._device)), "cfnmpc_fleet_get_nlp_stats")
+        return cost, res
+
     def eval_sens_x0(self, act_tol=1e-6, stream=None):
         """cfnmpc_fleet_eval_sens_x0: sensitivities w.r.t. x0 of every bucket's last QP (BatchSolver.eval_sens_x0)"""
         _check(self._L.cfnmpc_fleet_eval_sens_x0(self._h, float(act_tol), _launch_stream(stream, self._device)),

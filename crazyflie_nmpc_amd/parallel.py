@@ -176,6 +176,17 @@ class MultiGpuFleet:
     def sync(self):
         self._check(self._L.cfnmpc_multi_sync(self._h), "cfnmpc_multi_sync")
 
+    def eval_nlp(self):
+        """cfnmpc_multi_eval_nlp: NLP cost and KKT residuals at every shard's current iterate (synchronous)"""
+        self._check(self._L.cfnmpc_multi_eval_nlp(self._h), "cfnmpc_multi_eval_nlp")
+
+    def nlp_stats(self):
+        """-> (cost [B], res [B, 3] = res_stat, res_eq, res_ineq) of the last eval_nlp, host arrays in the caller's order"""
+        vp = self._C.c_void_p
+        cost = np.empty(self.B); res = np.empty((self.B, 3))
+        self._check(self._L.cfnmpc_multi_get_nlp_stats(self._h, cost.ctypes.data_as(vp), res.ctypes.data_as(vp)), "cfnmpc_multi_get_nlp_stats")
+        return cost, res
+
     def eval_sens_x0(self, act_tol=1e-6):
         """cfnmpc_multi_eval_sens_x0: sensitivities w.r.t. x0 of every shard's last QP (synchronous)"""
         self._check(self._L.cfnmpc_multi_eval_sens_x0(self._h, float(act_tol)), "cfnmpc_multi_eval_sens_x0")

@@ -290,6 +290,33 @@ class BatchSolver:
                                             rs.ctypes.data_as(C.c_void_p), 0, _launch_stream(None, self._device)), "cfnmpc_get_sqp_stats")
         return st, it, rs
 
+    def eval_nlp(self, keep_multipliers=False, stream=None):
+        """NLP cost, KKT residuals and (keep_multipliers) costates / reduced gradient at the current iterate, from the data in
+        force (include/cfnmpc.h: cfnmpc_eval_nlp); needs no solve and disturbs none.  Asynchronous on `stream`.  Read with
+        nlp_stats() / nlp_multipliers()."""
+        _check(self._L.cfnmpc_eval_nlp(self._h, 1 if keep_multipliers else 0, _launch_stream(stream, self._device)), "cfnmpc_eval_nlp")
+
+    def nlp_stats(self, out=None):
+        """-> (cost [B], res [B, 3] = res_stat, res_eq, res_ineq) of the last eval_nlp; `out` = two torch device tensors
+        (float64) to keep them on the device (filled on torch's current stream)"""
+        if out is not None:
+            pc, dev, strm, _a = _arg(out[0], (self.B,), device=self._device)
+            pr, _d, _s, _b = _arg(out[1], (self.B, 3), device=self._device)
+            _check(self._L.cfnmpc_get_nlp_stats(self._h, pc, pr, dev, strm), "cfnmpc_get_nlp_stats")
+            return out
+        cost = np.empty(self.B); res = np.empty((self.B, 3))
+        _check(self._L.cfnmpc_get_nlp_stats(self._h, cost.ctypes.data_as(C.c_void_p), res.ctypes.data_as(C.c_void_p), 0,
+                                            _launch_stream(None, self._device)), "cfnmpc_get_nlp_stats")
+        return cost, res
+
+    def nlp_multipliers(self):
+        """-> (pi [B, N + 1, 13] costates in the public state order, gu [B, N, 4] reduced gradient dJ/du_k) of the last
+        eval_nlp(keep_multipliers=True)"""
+        pi = np.empty((self.B, self.N + 1, NX)); gu = np.empty((self.B, self.N, NU))
+        _check(self._L.cfnmpc_get_nlp_multipliers(self._h, pi.ctypes.data_as(C.c_void_p), gu.ctypes.data_as(C.c_void_p), 0,
+                                                  _launch_stream(None, self._device)), "cfnmpc_get_nlp_multipliers")
+        return pi, gu
+
     def eval_sens_x0(self, act_tol=1e-6, stream=None):
         """Sensitivities of the last QP's solution with respect to x0 (include/cfnmpc.h: cfnmpc_eval_sens_x0): the active set
         of the current iterate (inputs within act_tol of a bound) and the masked Riccati gains.  Read with sens_x0()."""

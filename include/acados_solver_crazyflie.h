@@ -90,6 +90,16 @@ ocp_nlp_out *ocp_nlp_out_create(ocp_nlp_config *config, ocp_nlp_dims *dims);
 void ocp_nlp_out_destroy(void *out);
 void ocp_nlp_eval_param_sens(ocp_nlp_solver *solver, char *field, int stage, int index, ocp_nlp_out *sens_out);
 
+/* ---- NLP cost and true KKT residuals at the iterate the last acados_solve() left (include/cfnmpc.h: cfnmpc_eval_nlp), with the
+ *      data that solve put in force.  ocp_nlp_eval_cost / ocp_nlp_eval_residuals evaluate (one evaluation serves both until the
+ *      next solve or acados_cfnmpc_init_iterate); ocp_nlp_get(config, solver, field, &v) reads one double: "cost_value", "res_stat" (projected-gradient
+ *      residual of the input box, complementarity folded in), "res_eq", "res_ineq" -- and evaluates first if nothing has since
+ *      the solve.  Any other field leaves v untouched ("pi" is not offered: acados' sign and index convention for it is not
+ *      pinned here).  nlp_out->inf_norm_res keeps its meaning: the last QP's residual. */
+void ocp_nlp_eval_cost(ocp_nlp_solver *solver, ocp_nlp_in *in, ocp_nlp_out *out);
+void ocp_nlp_eval_residuals(ocp_nlp_solver *solver, ocp_nlp_in *in, ocp_nlp_out *out);
+void ocp_nlp_get(ocp_nlp_config *config, ocp_nlp_solver *solver, const char *field, void *value);
+
 /* ---- extension (not in acados): choose the initial iterate after acados_create():
  *      0 = acados default (x_k = [0,0,0,1,0..], u_k = 0), 1 = x_k = current lbx, u_k = hover. */
 int acados_cfnmpc_init_iterate(int mode);

@@ -388,6 +388,33 @@ int cfnmpc_get_sens_x0(cfnmpc_solver *s, int stage, int n_stages, double *du /*[
                        double *dx /*[B][n_stages][13][13] or NULL*/, int on_device, void *stream);
 int cfnmpc_get_sens_active(cfnmpc_solver *s, signed char *act /*[B][N][4]*/, int on_device, void *stream);
 
+/* NLP cost, KKT residuals, costates and reduced gradient at the CURRENT iterate w = (x_0..x_N, u_0..u_{N-1}) (DESIGN.md section
+ * 5.16), from the data in force now and nothing else: x0, yref / yref_e, the uniform or per-instance weights times the cost
+ * scaling (s, s_e), the scalar or per-stage box, the nominal or per-instance model parameters, erk_steps (Phi = that many RK4
+ * steps over dt).  It needs no preceding solve, does not depend on the route the QP of a row took, and writes nothing that a
+ * solve, getter or option reads.  Per instance:
+ *   cost     = sum_{k<N} 1/2 s (y_k - yref_k)' W (y_k - yref_k) + 1/2 s_e (x_N - yref_e)' W_N (x_N - yref_e),  y_k = (x_k, u_k);
+ *   pi_N     = s_e W_N (x_N - yref_e),  pi_k = s Q (x_k - yref_k^x) + A_k' pi_{k+1},  A_k = dPhi/dx (x_k, u_k): the costates that
+ *              put the x-stationarity of stages 1..N at zero; pi_0 is the multiplier of x_0 = x0;
+ *   g_k      = s R (u_k - yref_k^u) + B_k' pi_{k+1},  B_k = dPhi/du: the reduced gradient dJ/du_k along the trajectory;
+ *   res_stat = max_{k,a} |u_{k,a} - clip(u_{k,a} - g_{k,a}, lb_{k,a}, ub_{k,a})|, the projected-gradient (natural) residual of the
+ *              box: |g| for an input inside the box, zero for an input on a bound (lb = ub included) whose gradient points
+ *              outward, continuous in between, no activity tolerance; it folds complementarity in (there is no res_comp);
+ *   res_eq   = max(|x_0 - x0|, max_k |x_{k+1} - Phi(x_k, u_k)|),  res_ineq = largest box violation -- the formulas of
+ *              cfnmpc_solve_sqp's res_eq / res_ineq.
+ * A NaN in the iterate of a row sticks in every result of that row.
+ *   cfnmpc_eval_nlp: asynchronous on `stream`.  keep_multipliers = 0 stores cost and the three residuals (4 doubles per
+ *     instance); 1 additionally stores pi and g -- their two buffers are allocated at the first such call
+ *     (cfnmpc_workspace_bytes counts them from then on: ((B + 3) / 4 + 1) * (544 N + 416) bytes together).
+ *   cfnmpc_get_nlp_stats / cfnmpc_get_nlp_multipliers: the LAST evaluation's snapshot (no invalidation tracking: a solve or a
+ *     change of data in between does not show).  pi in the public state order.  CFNMPC_EINVAL before any evaluation, for the
+ *     multipliers when the last evaluation did not keep them, and when both pointers are NULL. */
+int cfnmpc_eval_nlp(cfnmpc_solver *s, int keep_multipliers, void *stream);
+int cfnmpc_get_nlp_stats(cfnmpc_solver *s, double *cost /*[B] or NULL*/, double *res /*[B][3]: stat, eq, ineq; or NULL*/,
+                         int on_device, void *stream);
+int cfnmpc_get_nlp_multipliers(cfnmpc_solver *s, double *pi /*[B][N+1][13] or NULL*/, double *gu /*[B][N][4] or NULL*/,
+                               int on_device, void *stream);
+
 /* Output stage of the reference node for the whole fleet, on the device (NMPC::iteration,
  * acados_mpc.cpp:619-670): from the current iterate (u0 = inputs of stage 0, u1 = stage 1, x4 =
  * state of stage 4) it forms what the node publishes per vehicle,
@@ -515,6 +542,12 @@ int cfnmpc_fleet_get_sqp_stats(cfnmpc_fleet *f, int *status, int *sqp_iter, doub
 int cfnmpc_fleet_eval_sens_x0(cfnmpc_fleet *f, double act_tol, void *stream);
 int cfnmpc_fleet_get_sens_x0(cfnmpc_fleet *f, int stage, int n_stages, double *du /*[B][n_stages][4][13] or NULL*/,
                              double *dx /*[B][n_stages][13][13] or NULL*/, int on_device, void *stream);
+/* cfnmpc_eval_nlp (keep_multipliers = 0) on every bucket, cfnmpc_get_nlp_stats in the fleet's vehicle order: cost [B], res [B][3]
+ * (host arrays, on_device 0 or 2, are filled synchronously).  The multipliers have one shape per horizon: evaluate and read them
+ * through the bucket's solver (cfnmpc_fleet_bucket). */
+int cfnmpc_fleet_eval_nlp(cfnmpc_fleet *f, void *stream);
+int cfnmpc_fleet_get_nlp_stats(cfnmpc_fleet *f, double *cost /*[B] or NULL*/, double *res /*[B][3] or NULL*/, int on_device,
+                               void *stream);
 
 /* ---- one fleet across several GPUs of a node, from ONE process --------------------------------
  * The reference owns one vehicle per process (acados_mpc.cpp:76-82); instances are independent, so a
@@ -570,6 +603,10 @@ int cfnmpc_multi_set_weights_batch(cfnmpc_multi *m, const double *W, const doubl
  * synchronous; for cfnmpc_multi_create_horizons the range is limited by the shortest horizon, as for a fleet. */
 int cfnmpc_multi_eval_sens_x0(cfnmpc_multi *m, double act_tol);
 int cfnmpc_multi_get_sens_x0(cfnmpc_multi *m, int stage, int n_stages, double *du /*host or NULL*/, double *dx /*host or NULL*/);
+/* cfnmpc_eval_nlp (keep_multipliers = 0) per shard and its results over the whole fleet (both create variants): host arrays in
+ * the caller's order, synchronous */
+int cfnmpc_multi_eval_nlp(cfnmpc_multi *m);
+int cfnmpc_multi_get_nlp_stats(cfnmpc_multi *m, double *cost /*[B] host or NULL*/, double *res /*[B][3] host or NULL*/);
 
 const char *cfnmpc_version(void);
 
