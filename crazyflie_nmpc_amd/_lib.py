@@ -13,13 +13,13 @@ LIB_PATH = os.environ.get("CFNMPC_LIB") or os.path.join(_HERE, "libcfnmpc.so")  
 SYMBOLS = [
     "cfnmpc_default_opts", "cfnmpc_default_opts_v", "cfnmpc_opts_size", "cfnmpc_abi_version", "cfnmpc_create", "cfnmpc_free", "cfnmpc_batch", "cfnmpc_horizon",
     "cfnmpc_workspace_bytes", "cfnmpc_set_x0", "cfnmpc_set_yref", "cfnmpc_set_weights", "cfnmpc_set_box", "cfnmpc_get_cmd", "cfnmpc_set_yref_windows", "cfnmpc_init_iterate",
-    "cfnmpc_set_iterate", "cfnmpc_get_iterate", "cfnmpc_solve", "cfnmpc_solve_sqp", "cfnmpc_get_sqp_stats", "cfnmpc_step_host", "cfnmpc_get_u", "cfnmpc_get_x",
+    "cfnmpc_set_iterate", "cfnmpc_get_iterate", "cfnmpc_solve", "cfnmpc_solve_sqp", "cfnmpc_get_sqp_stats", "cfnmpc_set_sqp_globalization", "cfnmpc_get_sqp_globalization", "cfnmpc_get_sqp_ls_stats", "cfnmpc_step_host", "cfnmpc_get_u", "cfnmpc_get_x",
     "cfnmpc_get_stats", "cfnmpc_sim", "cfnmpc_estimate", "cfnmpc_debug_get_linearisation", "cfnmpc_debug_linearise", "cfnmpc_debug_start_factor", "cfnmpc_debug_get_factor",
     "cfnmpc_debug_get_head", "cfnmpc_debug_get_viol", "cfnmpc_debug_get_list_counts", "cfnmpc_debug_get_condensed", "cfnmpc_set_box_stages", "cfnmpc_set_profiling", "cfnmpc_get_profile", "cfnmpc_get_profile_kernels", "cfnmpc_get_profile_steps", "cfnmpc_version",
     "cfnmpc_fleet_create", "cfnmpc_fleet_free", "cfnmpc_fleet_batch", "cfnmpc_fleet_min_horizon", "cfnmpc_fleet_max_horizon",
     "cfnmpc_fleet_num_buckets", "cfnmpc_fleet_bucket", "cfnmpc_fleet_workspace_bytes", "cfnmpc_fleet_set_x0",
     "cfnmpc_fleet_set_yref", "cfnmpc_fleet_set_weights", "cfnmpc_fleet_init_iterate", "cfnmpc_fleet_solve",
-    "cfnmpc_fleet_get_u", "cfnmpc_fleet_get_x", "cfnmpc_fleet_get_stats", "cfnmpc_fleet_solve_sqp", "cfnmpc_fleet_get_sqp_stats", "cfnmpc_fleet_set_box", "cfnmpc_fleet_set_box_stages", "cfnmpc_fleet_get_cmd",
+    "cfnmpc_fleet_get_u", "cfnmpc_fleet_get_x", "cfnmpc_fleet_get_stats", "cfnmpc_fleet_solve_sqp", "cfnmpc_fleet_get_sqp_stats", "cfnmpc_fleet_set_sqp_globalization", "cfnmpc_fleet_get_sqp_ls_stats", "cfnmpc_fleet_set_box", "cfnmpc_fleet_set_box_stages", "cfnmpc_fleet_get_cmd",
     "cfnmpc_multi_create", "cfnmpc_multi_free", "cfnmpc_multi_batch", "cfnmpc_multi_num_shards", "cfnmpc_multi_shard",
     "cfnmpc_multi_set_x0", "cfnmpc_multi_set_yref", "cfnmpc_multi_set_weights", "cfnmpc_multi_init_iterate", "cfnmpc_multi_solve",
     "cfnmpc_multi_sync", "cfnmpc_multi_set_box", "cfnmpc_multi_set_box_stages", "cfnmpc_multi_get_u", "cfnmpc_multi_get_x", "cfnmpc_multi_get_cmd", "cfnmpc_multi_get_stats",
@@ -96,6 +96,9 @@ def lib():
     L.cfnmpc_solve.argtypes = [vp, i32, vp]
     L.cfnmpc_solve_sqp.argtypes = [vp, i32, dbl, dbl, dbl, vp, vp]
     L.cfnmpc_get_sqp_stats.argtypes = [vp, vp, vp, vp, i32, vp]
+    L.cfnmpc_set_sqp_globalization.argtypes = [vp, i32, dbl, dbl, dbl]
+    L.cfnmpc_get_sqp_globalization.argtypes = [vp, vp, vp, vp, vp]
+    L.cfnmpc_get_sqp_ls_stats.argtypes = [vp, vp, vp, vp, vp, i32, vp]
     L.cfnmpc_step_host.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.cfnmpc_get_u.argtypes = [vp, i32, vp, i32, vp]
     L.cfnmpc_get_x.argtypes = [vp, i32, vp, i32, vp]
@@ -167,6 +170,8 @@ def lib():
     L.cfnmpc_fleet_get_stats.argtypes = [vp, vp, vp, vp, i32, vp]
     L.cfnmpc_fleet_solve_sqp.argtypes = [vp, i32, dbl, dbl, dbl, vp, vp]
     L.cfnmpc_fleet_get_sqp_stats.argtypes = [vp, vp, vp, vp, i32, vp]
+    L.cfnmpc_fleet_set_sqp_globalization.argtypes = [vp, i32, dbl, dbl, dbl]
+    L.cfnmpc_fleet_get_sqp_ls_stats.argtypes = [vp, vp, vp, vp, vp, i32, vp]
     L.cfnmpc_multi_create.argtypes = [C.POINTER(vp), i32, vp, i32, C.POINTER(Opts)]
     for n in ("free", "batch", "num_shards", "sync"):
         getattr(L, "cfnmpc_multi_" + n).argtypes = [vp]

@@ -60,6 +60,14 @@ struct cfnmpc_solver {
     cfn::SqpArgs sqp;
     unsigned* h_sqp_cnt;
     hipEvent_t sqp_ev;
+    // globalisation of the SQP solve (cfnmpc_set_sqp_globalization): the setting (mode, alpha_min; eta / reduction / T in ls),
+    // k_sqp_ls's per-instance state (allocated at the first globalised solve), whether the RUNNING solve is globalised, and
+    // what the last solve was (-1: none yet, else its mode) for cfnmpc_get_sqp_ls_stats
+    int glob_mode;
+    double glob_alpha_min;
+    cfn::LsArgs ls;
+    bool ls_active;
+    int ls_last;
     // stage-cost scaling (cfnmpc_set_cost_scaling): the weights as the caller set them; P.W = stage_scale * W_set,
     // P.WN = terminal_scale * WN_set
     double W_set[17], WN_set[13];
@@ -315,6 +323,12 @@ int cfnmpc_create(cfnmpc_solver** out, int batch, const cfnmpc_opts* opts) {
     std::memset(&s->sqp, 0, sizeof s->sqp);
     s->h_sqp_cnt = nullptr;
     s->sqp_ev = nullptr;
+    s->glob_mode = CFNMPC_SQP_FULL_STEP;
+    s->glob_alpha_min = 1.0 / 1024.0;
+    std::memset(&s->ls, 0, sizeof s->ls);
+    s->ls.eta = 1e-4; s->ls.reduction = 0.5; s->ls.T = 10;
+    s->ls_active = false;
+    s->ls_last = -1;
     std::memset(&s->nlp, 0, sizeof s->nlp);
     s->nlp_state = 0;
     int simds = 1024;   // SIMDs of the device the solver is created on
@@ -902,8 +916,15 @@ namespace {
 
 // One RTI step (linearise -> QP -> full step) on `st`, the body of cfnmpc_solve's loop and one iteration of the full SQP solve.
 // reinit: cfnmpc_opts.reinit_failed applies (cfnmpc_solve; not inside an SQP solve, whose failed rows stop instead).
-// chk (may be NULL): the SQP solve's convergence check, launched behind the step's kernels and BEFORE the host swaps the
-// iterate buffers (it reads both); the launches of the step itself are the same with or without it.
+// chk (may be NULL): the SQP solve's convergence check (in a globalised solve: the line search that contains it), launched
+// behind the step's kernels and BEFORE the host swaps the iterate buffers (it reads both; the line search writes the new one);
+// the launches of the step itself are the same with or without it.
+// behind the step of an SQP iteration: the convergence check, or in a globalised solve the line search that contains it
+void launch_sqp_close(cfnmpc_solver* s, const cfn::SqpArgs& chk, hipStream_t st) {
+    if (s->ls_active) cfn::launch_sqp_ls(s->P, chk, s->ls, st);
+    else cfn::launch_sqp_check(s->P, chk, st);
+}
+
 int rti_step(cfnmpc_solver* s, hipStream_t st, bool reinit, const cfn::SqpArgs* chk) {
     invalidate_sens(s);   // (until the step is through)
     hipEvent_t* e = nullptr;
@@ -955,12 +976,12 @@ int rti_step(cfnmpc_solver* s, hipStream_t st, bool reinit, const cfn::SqpArgs* 
         if (ok) {
             HIP_TRY(hipGraphLaunch(s->gexec[p], st));
             HIP_TRY(hipEventRecord(s->glaunched[p], st));
-            if (chk) cfn::launch_sqp_check(s->P, *chk, st);
+            if (chk) launch_sqp_close(s, *chk, st);
             std::swap(s->P.xit, s->P.xitn);
             std::swap(s->P.uit, s->P.uitn);
             s->parity ^= 1;
             s->lin_valid = false;
-            s->sens_src = chk ? 2 : 1;
+            s->sens_src = chk ? (s->ls_active ? 0 : 2) : 1;
             return CFNMPC_OK;
         }
     }
@@ -976,12 +997,13 @@ int rti_step(cfnmpc_solver* s, hipStream_t st, bool reinit, const cfn::SqpArgs* 
             cfn::launch_qp(s->P, st, e ? e + 2 : nullptr);
         }
         if (e) HIP_TRY(hipEventRecord(e[6], st));
-        if (chk) cfn::launch_sqp_check(s->P, *chk, st);
+        if (chk) launch_sqp_close(s, *chk, st);
         std::swap(s->P.xit, s->P.xitn);   // the step's kernels wrote every instance's new iterate there
         std::swap(s->P.uit, s->P.uitn);
         s->parity ^= 1;
         s->lin_valid = false;   // the iterate moved
-        s->sens_src = chk ? 2 : 1;   // (cfnmpc_eval_sens_x0: the QP of this step)
+        // (cfnmpc_eval_sens_x0: the QP of this step -- not behind a line search: that QP belongs to w_{j-1}, the iterate is w_j)
+        s->sens_src = chk ? (s->ls_active ? 0 : 2) : 1;
         return CFNMPC_OK;
     }
 #ifdef CFN_DEV   // overlapped preparation: development builds only (CFNMPC_OVERLAP=1); s->overlap is 0 in the product
@@ -1033,6 +1055,19 @@ int sqp_begin(cfnmpc_solver* s, int max_iter, double tol_step, double tol_eq, do
     s->sqp.max_iter = max_iter;
     s->sqp.tol_step = tol_step; s->sqp.tol_eq = tol_eq; s->sqp.tol_ineq = tol_ineq;
     s->sqp.j = 0;
+    // globalised solve: k_sqp_ls's state at the first one (iteration 1 ignores what an earlier solve left in it)
+    if (s->glob_mode == CFNMPC_SQP_MERIT_BACKTRACKING && !s->ls.n_fail) {
+        const size_t B = s->P.B;
+        cfn::LsArgs a = s->ls;
+        int rc2 = dev_alloc(s, &a.alpha, B);
+        if (rc2 == CFNMPC_OK) rc2 = dev_alloc(s, &a.mu, B);
+        if (rc2 == CFNMPC_OK) rc2 = dev_alloc(s, &a.n_short, B);
+        if (rc2 == CFNMPC_OK) rc2 = dev_alloc(s, &a.n_fail, B);
+        if (rc2 != CFNMPC_OK) return rc2;   // (what was allocated stays with the solver; the next solve allocates again)
+        s->ls = a;
+    }
+    s->ls_active = s->glob_mode == CFNMPC_SQP_MERIT_BACKTRACKING;
+    s->ls_last = s->glob_mode;
     // once per solve: both counters to zero (the check kernel of iteration j clears the counter of iteration j + 1 itself);
     // the done flags need no reset, iteration 1 ignores them
     HIP_TRY(hipMemsetAsync(s->sqp.cnt, 0, 2 * sizeof(unsigned), (hipStream_t)stream));
@@ -1061,6 +1096,55 @@ int sqp_wait(cfnmpc_solver* s, unsigned* open) {
 }
 
 int sqp_iterations(const cfnmpc_solver* s) { return s->sqp.j; }
+
+int sqp_set_globalization(cfnmpc_solver* s, int mode, double eta, double reduction, double alpha_min) {
+    if (!s || (mode != CFNMPC_SQP_FULL_STEP && mode != CFNMPC_SQP_MERIT_BACKTRACKING)) return CFNMPC_EINVAL;
+    if (eta == 0.0) eta = 1e-4;
+    if (reduction == 0.0) reduction = 0.5;
+    if (alpha_min == 0.0) alpha_min = 1.0 / 1024.0;
+    if (!(eta > 0.0 && eta < 0.5) || !(reduction > 0.0 && reduction < 1.0) || !(alpha_min > 0.0 && alpha_min <= 1.0))
+        return CFNMPC_EINVAL;
+    int T = 0;   // the smallest T with reduction^T <= alpha_min, the powers by repeated multiplication as in k_sqp_ls
+    for (double a = 1.0; a > alpha_min; a *= reduction)
+        if (++T > 32) return CFNMPC_EINVAL;
+    s->glob_mode = mode;
+    s->glob_alpha_min = alpha_min;
+    s->ls.eta = eta; s->ls.reduction = reduction; s->ls.T = T;
+    return CFNMPC_OK;
+}
+
+int sqp_get_ls_stats(cfnmpc_solver* s, double* alpha, double* mu, int* n_short, int* n_fail, int on_device, void* stream) {
+    if (!s || s->ls_last < 0 || (!alpha && !mu && !n_short && !n_fail)) return CFNMPC_EINVAL;
+    DeviceGuard dg(s);
+    hipStream_t st = (hipStream_t)stream;
+    const bool host = is_host(on_device);
+    const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    const size_t B = s->P.B;
+    if (s->ls_last == CFNMPC_SQP_FULL_STEP) {   // full steps: alpha = 1, no penalty, nothing shortened (no buffer needed)
+        if (host) {
+            if (alpha) std::fill_n(alpha, B, 1.0);
+            if (mu) std::fill_n(mu, B, 0.0);
+            if (n_short) std::fill_n(n_short, B, 0);
+            if (n_fail) std::fill_n(n_fail, B, 0);
+            return CFNMPC_OK;
+        }
+        if (alpha) {
+            const std::vector<double> one(B, 1.0);
+            HIP_TRY(hipMemcpyAsync(alpha, one.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipStreamSynchronize(st));   // (the source goes out of scope)
+        }
+        if (mu) HIP_TRY(hipMemsetAsync(mu, 0, B * sizeof(double), st));
+        if (n_short) HIP_TRY(hipMemsetAsync(n_short, 0, B * sizeof(int), st));
+        if (n_fail) HIP_TRY(hipMemsetAsync(n_fail, 0, B * sizeof(int), st));
+        return CFNMPC_OK;
+    }
+    if (alpha) HIP_TRY(hipMemcpyAsync(alpha, s->ls.alpha, B * sizeof(double), kind, st));
+    if (mu) HIP_TRY(hipMemcpyAsync(mu, s->ls.mu, B * sizeof(double), kind, st));
+    if (n_short) HIP_TRY(hipMemcpyAsync(n_short, s->ls.n_short, B * sizeof(int), kind, st));
+    if (n_fail) HIP_TRY(hipMemcpyAsync(n_fail, s->ls.n_fail, B * sizeof(int), kind, st));
+    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
 
 int sqp_get_stats(cfnmpc_solver* s, int* status, int* sqp_iter, double* res, int on_device, void* stream) {
     if (!s) return CFNMPC_EINVAL;
@@ -1105,6 +1189,23 @@ int cfnmpc_solve_sqp(cfnmpc_solver* s, int max_iter, double tol_step, double tol
 
 int cfnmpc_get_sqp_stats(cfnmpc_solver* s, int* status, int* sqp_iter, double* res, int on_device, void* stream) {
     return cfn::sqp_get_stats(s, status, sqp_iter, res, on_device, stream);
+}
+
+int cfnmpc_set_sqp_globalization(cfnmpc_solver* s, int mode, double eta, double reduction, double alpha_min) {
+    return cfn::sqp_set_globalization(s, mode, eta, reduction, alpha_min);
+}
+
+int cfnmpc_get_sqp_globalization(const cfnmpc_solver* s, int* mode, double* eta, double* reduction, double* alpha_min) {
+    if (!s || (!mode && !eta && !reduction && !alpha_min)) return CFNMPC_EINVAL;
+    if (mode) *mode = s->glob_mode;
+    if (eta) *eta = s->ls.eta;
+    if (reduction) *reduction = s->ls.reduction;
+    if (alpha_min) *alpha_min = s->glob_alpha_min;
+    return CFNMPC_OK;
+}
+
+int cfnmpc_get_sqp_ls_stats(cfnmpc_solver* s, double* alpha, double* mu, int* n_short, int* n_fail, int on_device, void* stream) {
+    return cfn::sqp_get_ls_stats(s, alpha, mu, n_short, n_fail, on_device, stream);
 }
 
 int cfnmpc_step_host(cfnmpc_solver* s, const double* x0, const double* yref, const double* yref_e, double* u,

@@ -493,6 +493,43 @@ int cfnmpc_fleet_get_sqp_stats(cfnmpc_fleet* f, int* status, int* sqp_iter, doub
     });
 }
 
+int cfnmpc_fleet_set_sqp_globalization(cfnmpc_fleet* f, int mode, double eta, double reduction, double alpha_min) {
+    if (!f || f->bk.empty()) return CFNMPC_EINVAL;
+    // (the check does not depend on the bucket: the first refusal comes before anything has changed)
+    for (Bucket& b : f->bk) RC_TRY(cfn::sqp_set_globalization(b.s, mode, eta, reduction, alpha_min));
+    return CFNMPC_OK;
+}
+
+int cfnmpc_fleet_get_sqp_ls_stats(cfnmpc_fleet* f, double* alpha, double* mu, int* n_short, int* n_fail, int on_device, void* stream) {
+    if (!f || (!alpha && !mu && !n_short && !n_fail)) return CFNMPC_EINVAL;
+    FleetDevice fd(f);
+    if (!on_device) {
+        for (Bucket& b : f->bk) {
+            f->h_ints.resize((size_t)2 * b.count);
+            f->h_rows.resize((size_t)2 * b.count);
+            int* hs = f->h_ints.data(), *hf = hs + b.count;
+            double* ha = f->h_rows.data(), *hm = ha + b.count;
+            RC_TRY(cfn::sqp_get_ls_stats(b.s, ha, hm, hs, hf, 0, stream));
+            for (int r = 0; r < b.count; r++) {
+                if (alpha) alpha[b.idx[r]] = ha[r];
+                if (mu) mu[b.idx[r]] = hm[r];
+                if (n_short) n_short[b.idx[r]] = hs[r];
+                if (n_fail) n_fail[b.idx[r]] = hf[r];
+            }
+        }
+        return CFNMPC_OK;
+    }
+    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) {
+        RC_TRY(staging(b));
+        RC_TRY(cfn::sqp_get_ls_stats(b.s, b.d_rows, b.d_rows + b.count, b.d_ints, b.d_ints + b.count, 1, st));
+        if (alpha) rows<double, false>(b.d_rows, alpha, b.d_idx, b.count, 1, 1, st);
+        if (mu) rows<double, false>(b.d_rows + b.count, mu, b.d_idx, b.count, 1, 1, st);
+        if (n_short) rows<int, false>(b.d_ints, n_short, b.d_idx, b.count, 1, 1, st);
+        if (n_fail) rows<int, false>(b.d_ints + b.count, n_fail, b.d_idx, b.count, 1, 1, st);
+        return (int)CFNMPC_OK;
+    });
+}
+
 // ---- NLP evaluation at every bucket's current iterate (include/cfnmpc.h: cfnmpc_eval_nlp) -------------
 int cfnmpc_fleet_eval_nlp(cfnmpc_fleet* f, void* stream) {
     if (!f) return CFNMPC_EINVAL;

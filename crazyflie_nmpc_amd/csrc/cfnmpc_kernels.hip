@@ -3588,6 +3588,283 @@ __global__ __launch_bounds__(64) void k_sqp_check(Params P, SqpArgs A) { sqp_che
 __global__ __launch_bounds__(64) void k_sqp_check_par(Params P, SqpArgs A) { sqp_check_body<true>(P, A); }
 
 // =============================================================================================
+// globalised SQP solve (cfnmpc_set_sqp_globalization): l1 merit backtracking behind SQP iteration j
+// =============================================================================================
+// Takes k_sqp_check's place: w = w_{j-1} in P.xit / P.uit, the step's candidate w^ in P.xitn / P.uitn, d = w^ - w.  Same mapping
+// (lane per instance, 13-vectors through the el13 tiles, reference rows through k_nlp_eval's 68-double tile, the next stage's loads
+// in flight during this stage's integration).  With c(v) = (x_0 - x0, the defects x_{k+1} - Phi(x_k, u_k), the box violations),
+// c1 = |c|_1, gd = grad J(w)'d and dHd = d' H d of the least-squares cost (J(w + a d) - J(w) = a gd + a^2 dHd / 2 exactly):
+//   first sweep  two integrations per stage (Phi at w and at w^): gd, dHd, c1(w), res_step = |d|_inf and the trial a = 1;
+//   penalty      mu <- max(mu, (gd + dHd / 2) / ((1 - 0.5) c1(w))) if c1(w) > 0 (mu = 0 at iteration 1, never decreases);
+//   test         a gd + a^2 dHd / 2 + mu (c1(w + a d) - c1(w)) <= eta a (gd - mu c1(w)) -- differences only, no trial evaluates
+//                the cost;
+//   more trials  a_t = reduction^t, one sweep (one integration per stage) per round of a wave-uniform loop, every lane at its own
+//                t; lanes that are through (accepted, frozen, QP status 4, idle) stay in the barriers and compute nothing; a lane
+//                without an accepted trial takes a_T (counted in n_fail);
+//   write        w_j = w + a d over the candidate through the tile, only for lanes with a < 1 (a = 1: w^ stays, bit for bit).
+// res_eq / res_ineq are those of the accepted trial, res_step is the FULL step |d|_inf; classification, frozen rows and the
+// counter of open rows as in k_sqp_check.  A NaN fails every comparison: the lane ends at a_T and the NaN sticks (max_nan, nan_pos).
+__device__ __forceinline__ double nan_pos(double v) { return (v > 0.0 || v != v) ? v : 0.0; }   // max(v, 0), NaN sticks
+template <bool PAR>
+__device__ __forceinline__ void sqp_ls_body(const Params& P, const SqpArgs& A, const LsArgs& G) {
+    __shared__ double xs_o[2 * 64 * 13], xs_n[2 * 64 * 13], ty[64 * 17], ws[17], sal[64];   // (two pairs of tiles: first sweep)
+    __shared__ int sfrz[64];
+    const int N = P.N;
+    const int tid = threadIdx.x;
+    const int raw = blockIdx.x * 64 + tid;
+    const bool valid = raw < P.B;
+    const int inst = valid ? raw : P.NW * 4 + (tid & 3);   // idle lanes: spare block
+    const size_t w = (size_t)(inst >> 2);
+    const int q = inst & 3;
+    const int w0 = blockIdx.x * 16;
+    const int M = P.erk_steps;
+    const double h = P.dt / M;
+    const ModelK<PAR> mk = model_k<PAR>(P, inst);
+    const size_t i4b = P.v4b ? ((size_t)w * N * 4 + q) * 4 : (size_t)inst * N * 4;   // this lane's 4-vectors (Params.v4b)
+    const size_t i4s = P.v4b ? 16 : 4;
+    auto el13 = [&](const double* f, int e, int stages, int k) -> gdouble* {   // (k_forward's accessor)
+        const int bk = (int)(__umul24((unsigned)e, div_magic(52)) >> 16), off = e - bk * 52;
+        const unsigned bo = (__umul24((unsigned)imin(bk, P.NW - w0), (unsigned)(stages * SZ_V13)) + (unsigned)off) * 8u;
+        const char* base = (const char*)(gm(f) + ((size_t)w0 * stages + k) * SZ_V13);
+        return (gdouble*)(base + bo);
+    };
+    auto el17 = [&](const double* f, int e, int k) -> gdouble* {   // (k_nlp_eval's accessor of the reference rows)
+        const int bk = (int)(__umul24((unsigned)e, div_magic(68)) >> 16), off = e - bk * 68;
+        const unsigned bo = (__umul24((unsigned)imin(bk, P.NW - w0), (unsigned)(N * SZ_Y)) + (unsigned)off) * 8u;
+        const char* base = (const char*)(gm(f) + ((size_t)w0 * N + k) * SZ_Y);
+        return (gdouble*)(base + bo);
+    };
+    // weights in force as in k_nlp_eval: the uniform stage weights from an LDS table, the per-instance row loaded either way
+    // (from x0 while unset: dummy loads, in bounds, dropped by the select next to each)
+    if (tid == 0) SFOR(e, 0, 17, { ws[e] = P.W[e]; });
+    const bool wt = P.wtab != nullptr;
+    const gdouble* wrow = wt ? gm(P.wtab) + (size_t)inst * WT_STRIDE : gm(P.x0);
+    const bool frozen = valid && A.j > 1 && gm(A.done)[raw] != 0;
+    const bool search = valid && !frozen && gm(P.status)[raw] != 4;   // (QP status 4: the step kept the iterate, d = 0)
+    sfrz[tid] = frozen ? 1 : 0;
+    __syncthreads();
+    const bool any_frozen = __any(frozen);
+    bool mine[13];   // element tid + 64 j of the group's tile belongs to a frozen instance
+    SFOR(j, 0, 13, { mine[j] = sfrz[(tid + 64 * j) / 13] != 0; });
+    // Phi(x, u): M = P.erk_steps RK4 steps over h = dt / M; x and the result in the INTERNAL order
+    auto rk4 = [&](const double (&xi)[13], const double (&u)[4], double (&ph)[13]) {
+        double x[13], xt[13], kk[13], ks[13];
+        SFOR(e, 0, 13, { x[e] = xi[int_of(e)]; });
+#pragma unroll 1
+        for (int m = 0; m < M; m++) {
+            f_expl(x, u, kk, mk);
+            SFOR(e, 0, 13, { ks[e] = kk[e]; xt[e] = x[e] + 0.5 * h * kk[e]; });
+            f_expl(xt, u, kk, mk);
+            SFOR(e, 0, 13, { ks[e] += 2.0 * kk[e]; xt[e] = x[e] + 0.5 * h * kk[e]; });
+            f_expl(xt, u, kk, mk);
+            SFOR(e, 0, 13, { ks[e] += 2.0 * kk[e]; xt[e] = x[e] + h * kk[e]; });
+            f_expl(xt, u, kk, mk);
+            SFOR(e, 0, 13, { x[e] += (h / 6.0) * (ks[e] + kk[e]); });
+        }
+        SFOR(i, 0, 13, { constexpr int e = ext_of(i); ph[i] = x[e]; });
+    };
+    auto load_x0 = [&](double (&ph)[13]) {   // what x_0 must equal
+        double t[13];
+        SFOR(j, 0, 13, { t[j] = *el13(P.x0, tid + 64 * j, 1, 0); });
+        __syncthreads();
+        SFOR(j, 0, 13, { xs_n[tid + 64 * j] = t[j]; });
+        __syncthreads();
+        SFOR(i, 0, 13, { ph[i] = xs_n[tid * 13 + i]; });
+    };
+    struct Ld { double o[13], n[13], uo[4], un[4]; };   // stage k: old / candidate state (tile elements), old / candidate inputs
+    auto issue = [&](int k, Ld& L) {
+        SFOR(j, 0, 13, { L.o[j] = *el13(P.xit, tid + 64 * j, N + 1, k); L.n[j] = *el13(P.xitn, tid + 64 * j, N + 1, k); });
+        const size_t ku = (size_t)imin(k, N - 1);
+        SFOR(a, 0, 4, { L.uo[a] = gm(P.uit)[i4b + ku * i4s + a]; L.un[a] = gm(P.uitn)[i4b + ku * i4s + a]; });
+    };
+    auto issue_y = [&](int k, double (&y)[17]) {   // reference row of stage k < N; the terminal reference (13-vector) at k = N
+        if (k < N) SFOR(j, 0, 17, { y[j] = *el17(P.yref, tid + 64 * j, k); });
+        else SFOR(j, 0, 17, { y[j] = j < 13 ? *el13(P.yref_e, tid + 64 * imin(j, 12), 1, 0) : 0.0; });
+    };
+    auto deposit = [&](const Ld& L) {
+        __syncthreads();
+        SFOR(j, 0, 13, { xs_o[tid + 64 * j] = L.o[j]; xs_n[tid + 64 * j] = L.n[j]; });
+        __syncthreads();
+    };
+
+    // ---- first sweep: gd, dHd, c1(w), |d|_inf, and the trial alpha = 1 ----
+    // The loads of stage k + 1 are split over the stage's two integrations so that neither carries all 51 doubles: the states
+    // (26) are in flight during Phi at w and land in the OTHER pair of tiles behind it, the reference row and the inputs (25)
+    // during Phi at w^; the candidate state is read back from its tile for the second integration.
+    double gd = 0.0, dHd = 0.0, c1w = 0.0, c1t = 0.0, r_step = 0.0, r_eq = 0.0, r_ineq = 0.0;
+    {
+        double pho[13], phn[13];   // what x_k must equal at w / at w^
+        load_x0(phn);
+        SFOR(i, 0, 13, { pho[i] = phn[i]; });
+        double uo[4], un[4], y[17];
+        {
+            double o[13], n[13];
+            SFOR(j, 0, 13, { o[j] = *el13(P.xit, tid + 64 * j, N + 1, 0); n[j] = *el13(P.xitn, tid + 64 * j, N + 1, 0); });
+            issue_y(0, y);
+            SFOR(a, 0, 4, { uo[a] = gm(P.uit)[i4b + a]; un[a] = gm(P.uitn)[i4b + a]; });
+            __syncthreads();
+            SFOR(j, 0, 13, { xs_o[tid + 64 * j] = o[j]; xs_n[tid + 64 * j] = n[j]; });
+        }
+        for (int k = 0; k <= N; k++) {
+            double* const to = xs_o + (k & 1) * (64 * 13);   // stage k's tiles (filled during stage k - 1)
+            double* const tn = xs_n + (k & 1) * (64 * 13);
+            __syncthreads();
+            SFOR(j, 0, 17, { ty[tid + 64 * j] = y[j]; });
+            __syncthreads();
+            double xo[13];
+            SFOR(i, 0, 13, { xo[i] = to[tid * 13 + i]; });
+            // frozen rows: w_{j-1} over the candidate (stage k has been read in full)
+            if (any_frozen) {
+                SFOR(j, 0, 13, { if (mine[j]) *el13(P.xitn, tid + 64 * j, N + 1, k) = to[tid + 64 * j]; });
+                if (frozen && k < N) SFOR(a, 0, 4, { gm(P.uitn)[i4b + (size_t)k * i4s + a] = uo[a]; });
+            }
+            const bool term = k == N;
+            const int ys = term ? 13 : 17;
+            SFOR(i, 0, 13, {
+                const double wl = wrow[(term ? WT_QN : 0) + i];   // (dummy without a table: see wrow)
+                const double wu = term ? P.WN[ext_of(i)] : ws[ext_of(i)];
+                const double wq = wt ? wl : wu;
+                const double xn = tn[tid * 13 + i];
+                const double d = xn - xo[i];
+                const double en = fabs(xn - phn[i]);
+                r_step = max_nan(r_step, fabs(d));
+                r_eq = max_nan(r_eq, en);
+                c1t += en;
+                c1w += fabs(xo[i] - pho[i]);
+                gd += wq * (xo[i] - ty[tid * ys + i]) * d;
+                dHd += wq * d * d;
+            });
+            if (term) break;
+            SFOR(a, 0, 4, {
+                const double wl = wrow[WT_R + a];   // (dummy without a table: see wrow)
+                const double wr = wt ? wl : ws[13 + a];
+                const double d = un[a] - uo[a];
+                r_step = max_nan(r_step, fabs(d));
+                gd += wr * (uo[a] - ty[tid * 17 + 13 + a]) * d;
+                dHd += wr * d * d;
+                double lo = P.u_min, hi = P.u_max;
+                if (P.lbs) { lo = gm(P.lbs)[i4b + (size_t)k * i4s + a]; hi = gm(P.ubs)[i4b + (size_t)k * i4s + a]; }
+                r_ineq = max_nan(r_ineq, fmax(lo - un[a], un[a] - hi));
+                c1t += nan_pos(lo - un[a]) + nan_pos(un[a] - hi);
+                c1w += nan_pos(lo - uo[a]) + nan_pos(uo[a] - hi);
+            });
+            {   // Phi at w, the next stage's states in flight
+                double o[13], n[13];
+                SFOR(j, 0, 13, { o[j] = *el13(P.xit, tid + 64 * j, N + 1, k + 1); n[j] = *el13(P.xitn, tid + 64 * j, N + 1, k + 1); });
+                rk4(xo, uo, pho);
+                double* const to2 = xs_o + ((k + 1) & 1) * (64 * 13);   // (last read before this stage's first barrier)
+                double* const tn2 = xs_n + ((k + 1) & 1) * (64 * 13);
+                SFOR(j, 0, 13, { to2[tid + 64 * j] = o[j]; tn2[tid + 64 * j] = n[j]; });
+            }
+            {   // Phi at w^ (read back from its tile), the next stage's reference row and inputs in flight
+                double xn[13], u2[4];
+                SFOR(i, 0, 13, { xn[i] = tn[tid * 13 + i]; });
+                SFOR(a, 0, 4, { u2[a] = un[a]; });
+                issue_y(k + 1, y);
+                const size_t ku = (size_t)imin(k + 1, N - 1);
+                SFOR(a, 0, 4, { uo[a] = gm(P.uit)[i4b + ku * i4s + a]; un[a] = gm(P.uitn)[i4b + ku * i4s + a]; });
+                rk4(xn, u2, phn);
+            }
+        }
+    }
+    __syncthreads();
+    // ---- penalty, directional derivative, the test at alpha = 1 ----
+    double mu = (valid && A.j > 1) ? gm(G.mu)[raw] : 0.0;
+    if (c1w > 0.0) {
+        const double cand = (gd + 0.5 * dHd) / (0.5 * c1w);   // rho = 0.5
+        if (cand > mu) mu = cand;
+    }
+    const double D = gd - mu * c1w;
+    double alpha = 1.0;
+    int t = 0;
+    bool fail = false;
+    bool open_ls = search && !(gd + 0.5 * dHd + mu * (c1t - c1w) <= G.eta * D);
+    if (open_ls && G.T == 0) { open_ls = false; fail = true; }
+    // ---- further trials: every open lane at its own alpha ----
+    while (__any(open_ls)) {
+        if (open_ls) { t++; alpha *= G.reduction; }
+        double ph[13];
+        load_x0(ph);
+        double s1 = 0.0, seq = 0.0, siq = 0.0;
+        Ld cur, nxt;
+        issue(0, cur);
+        for (int k = 0; k <= N; k++) {
+            deposit(cur);
+            double xt[13], ut[4];
+            SFOR(i, 0, 13, { const double xo = xs_o[tid * 13 + i]; xt[i] = fma(alpha, xs_n[tid * 13 + i] - xo, xo); });
+            SFOR(a, 0, 4, { ut[a] = fma(alpha, cur.un[a] - cur.uo[a], cur.uo[a]); });
+            if (k < N) issue(k + 1, nxt);
+            if (open_ls) {
+                SFOR(i, 0, 13, { const double e = fabs(xt[i] - ph[i]); seq = max_nan(seq, e); s1 += e; });
+                if (k < N) {
+                    SFOR(a, 0, 4, {
+                        double lo = P.u_min, hi = P.u_max;
+                        if (P.lbs) { lo = gm(P.lbs)[i4b + (size_t)k * i4s + a]; hi = gm(P.ubs)[i4b + (size_t)k * i4s + a]; }
+                        siq = max_nan(siq, fmax(lo - ut[a], ut[a] - hi));
+                        s1 += nan_pos(lo - ut[a]) + nan_pos(ut[a] - hi);
+                    });
+                    rk4(xt, ut, ph);
+                }
+            }
+            if (k < N) cur = nxt;
+        }
+        if (open_ls) {
+            const bool acc = alpha * gd + 0.5 * alpha * alpha * dHd + mu * (s1 - c1w) <= G.eta * alpha * D;
+            if (acc || t >= G.T) {
+                fail = !acc;
+                r_eq = seq; r_ineq = siq;
+                open_ls = false;
+            }
+        }
+    }
+    // ---- w_j = w + alpha d over the candidate, where alpha < 1 ----
+    const bool shortened = search && alpha < 1.0;
+    if (__any(shortened)) {
+        __syncthreads();
+        sal[tid] = shortened ? alpha : 1.0;
+        __syncthreads();
+        double ao[13];   // step length of the instance that owns element tid + 64 j
+        SFOR(j, 0, 13, { ao[j] = sal[(tid + 64 * j) / 13]; });
+        Ld cur, nxt;
+        issue(0, cur);
+        for (int k = 0; k <= N; k++) {
+            if (k < N) issue(k + 1, nxt);
+            SFOR(j, 0, 13, { if (ao[j] < 1.0) *el13(P.xitn, tid + 64 * j, N + 1, k) = fma(ao[j], cur.n[j] - cur.o[j], cur.o[j]); });
+            if (shortened && k < N)
+                SFOR(a, 0, 4, { gm(P.uitn)[i4b + (size_t)k * i4s + a] = fma(alpha, cur.un[a] - cur.uo[a], cur.uo[a]); });
+            if (k < N) cur = nxt;
+        }
+    }
+    bool open = false;
+    if (valid && !frozen) {
+        int st;
+        bool dn;
+        if (gm(P.status)[raw] == 4) { st = 4; dn = true; }
+        else if (r_step <= A.tol_step && r_eq <= A.tol_eq && r_ineq <= A.tol_ineq) { st = 0; dn = true; }
+        else { st = 2; dn = A.j >= A.max_iter; }
+        gm(A.res)[(size_t)raw * 3 + 0] = r_step;
+        gm(A.res)[(size_t)raw * 3 + 1] = r_eq;
+        gm(A.res)[(size_t)raw * 3 + 2] = r_ineq;
+        gm(A.status)[raw] = st;
+        gm(A.iter)[raw] = A.j;
+        gm(A.done)[raw] = dn ? 1 : 0;
+        const int ns = A.j > 1 ? gm(G.n_short)[raw] : 0, nf = A.j > 1 ? gm(G.n_fail)[raw] : 0;
+        gm(G.alpha)[raw] = alpha;
+        gm(G.mu)[raw] = mu;
+        gm(G.n_short)[raw] = ns + (shortened ? 1 : 0);
+        gm(G.n_fail)[raw] = nf + (fail ? 1 : 0);
+        open = !dn;
+    }
+    const unsigned long long m = __ballot(open);
+    if (tid == 0) {
+        if (m) atomicAdd(A.cnt + (A.j & 1), (unsigned)__popcll(m));
+        if (blockIdx.x == 0) A.cnt[(A.j + 1) & 1] = 0u;
+    }
+}
+__global__ __launch_bounds__(64) void k_sqp_ls(Params P, SqpArgs A, LsArgs G) { sqp_ls_body<false>(P, A, G); }
+__global__ __launch_bounds__(64) void k_sqp_ls_par(Params P, SqpArgs A, LsArgs G) { sqp_ls_body<true>(P, A, G); }
+
+// =============================================================================================
 // NLP evaluation at the current iterate (cfnmpc_eval_nlp)
 // =============================================================================================
 // Cost, KKT residuals, costates and reduced gradient of the NLP at w = (P.xit, P.uit), from the data in force (x0, yref, weights
@@ -4022,6 +4299,10 @@ void launch_reinit_failed(const Params& P, hipStream_t st) {
 void launch_sqp_check(const Params& P, const SqpArgs& A, hipStream_t st) {
     if (P.mpar) hipLaunchKernelGGL(k_sqp_check_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
     else hipLaunchKernelGGL(k_sqp_check, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
+}
+void launch_sqp_ls(const Params& P, const SqpArgs& A, const LsArgs& G, hipStream_t st) {
+    if (P.mpar) hipLaunchKernelGGL(k_sqp_ls_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A, G);
+    else hipLaunchKernelGGL(k_sqp_ls, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A, G);
 }
 void launch_nlp_eval(const Params& P, const NlpArgs& A, hipStream_t st) {
     if (P.mpar) hipLaunchKernelGGL(k_nlp_eval_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);

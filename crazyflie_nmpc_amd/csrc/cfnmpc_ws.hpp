@@ -258,6 +258,17 @@ struct SqpArgs {
 };
 // after the step of iteration A.j, BEFORE the host swaps the iterate buffers (reads P.xit / P.uit and P.xitn / P.uitn)
 void launch_sqp_check(const Params& P, const SqpArgs& A, hipStream_t st);
+// merit-function backtracking line search of a globalised SQP solve (cfnmpc_set_sqp_globalization):
+// per-instance state of k_sqp_ls, which takes k_sqp_check's place in the iterations of such a solve; owned by the solver,
+// allocated at its first globalised solve
+struct LsArgs {
+    double *alpha, *mu;      // [B]: step length of the instance's last executed iteration, its penalty (0 before iteration 1)
+    int *n_short, *n_fail;   // [B]: iterations taken with alpha < 1 / without an accepted trial
+    double eta, reduction;   // sufficient-decrease constant, alpha_t = reduction^t (by repeated multiplication)
+    int T;                   // last trial: the smallest T with reduction^T <= alpha_min
+};
+// in place of launch_sqp_check: searches, writes w_j = w + alpha (w^ - w) over the candidate in P.xitn / P.uitn, classifies, counts
+void launch_sqp_ls(const Params& P, const SqpArgs& A, const LsArgs& G, hipStream_t st);
 // NLP evaluation at the current iterate (cfnmpc_eval_nlp): results owned by the solver (not part of
 // Params: no kernel of a solve sees them)
 struct NlpArgs {

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import NU, NX, NY
-from .solver import _arg, _check, default_opts, _launch_stream, _torch_device
+from .solver import SQP_MODES, _arg, _check, _sqp_mode, default_opts, _launch_stream, _torch_device
 from .synthetic import regulation_row
 
 
@@ -179,6 +179,25 @@ class MixedHorizonFleet:
                                                   rs.ctypes.data_as(C.c_void_p), 0, _launch_stream(None, self._device)),
                "cfnmpc_fleet_get_sqp_stats")
         return st, it, rs
+
+    def set_sqp_globalization(self, mode="merit_backtracking", eta=0, reduction=0, alpha_min=0):
+        """BatchSolver.set_sqp_globalization for every bucket (cfnmpc_fleet_set_sqp_globalization)"""
+        m = _sqp_mode(mode)
+        _check(self._L.cfnmpc_fleet_set_sqp_globalization(self._h, m, float(eta), float(reduction), float(alpha_min)),
+               "cfnmpc_fleet_set_sqp_globalization")
+        self._sqp_glob = (SQP_MODES[m], float(eta) or 1e-4, float(reduction) or 0.5, float(alpha_min) or 2.0 ** -10)
+
+    def sqp_globalization(self):
+        """-> (mode, eta, reduction, alpha_min) in force (the last accepted setting; the defaults before one)"""
+        return getattr(self, "_sqp_glob", (SQP_MODES[0], 1e-4, 0.5, 2.0 ** -10))
+
+    def sqp_ls_stats(self):
+        """-> (alpha [B], mu [B], n_short [B], n_fail [B]) of the last solve_sqp, in the fleet's vehicle order"""
+        al = np.empty(self.B); mu = np.empty(self.B); ns = np.empty(self.B, dtype=np.int32); nf = np.empty(self.B, dtype=np.int32)
+        _check(self._L.cfnmpc_fleet_get_sqp_ls_stats(self._h, al.ctypes.data_as(C.c_void_p), mu.ctypes.data_as(C.c_void_p),
+                                                     ns.ctypes.data_as(C.c_void_p), nf.ctypes.data_as(C.c_void_p), 0,
+                                                     _launch_stream(None, self._device)), "cfnmpc_fleet_get_sqp_ls_stats")
+        return al, mu, ns, nf
 
     def get_u(self, stage, out=None):
         if out is None:

@@ -18,6 +18,12 @@ from . import _lib
 from ._lib import NU, NX, NY, Opts
 
 INIT_ACADOS, INIT_HOVER = 0, 1
+SQP_MODES = ("full_step", "merit_backtracking")   # CFNMPC_SQP_FULL_STEP, CFNMPC_SQP_MERIT_BACKTRACKING
+
+
+def _sqp_mode(mode):
+    """globalisation mode by name (or by its number, passed through for the library to judge)"""
+    return SQP_MODES.index(mode) if mode in SQP_MODES else int(mode)
 
 # per-instance model parameters (include/cfnmpc.h: cfnmpc_set_model_params), export_ode_model.py:33-42 order, l = arm length
 NP = 8
@@ -289,6 +295,28 @@ class BatchSolver:
         _check(self._L.cfnmpc_get_sqp_stats(self._h, st.ctypes.data_as(C.c_void_p), it.ctypes.data_as(C.c_void_p),
                                             rs.ctypes.data_as(C.c_void_p), 0, _launch_stream(None, self._device)), "cfnmpc_get_sqp_stats")
         return st, it, rs
+
+    def set_sqp_globalization(self, mode="merit_backtracking", eta=0, reduction=0, alpha_min=0):
+        """Globalisation of solve_sqp (include/cfnmpc.h: cfnmpc_set_sqp_globalization): "full_step" (the default of a new solver)
+        or "merit_backtracking", the l1 merit line search along every iteration's QP step; eta, reduction, alpha_min = 0 select
+        the defaults 1e-4, 0.5, 2**-10.  Stays with the solver; solve() ignores it."""
+        _check(self._L.cfnmpc_set_sqp_globalization(self._h, _sqp_mode(mode), float(eta), float(reduction), float(alpha_min)),
+               "cfnmpc_set_sqp_globalization")
+
+    def sqp_globalization(self):
+        """-> (mode, eta, reduction, alpha_min) in force"""
+        m = C.c_int(0); e = C.c_double(0); r = C.c_double(0); a = C.c_double(0)
+        _check(self._L.cfnmpc_get_sqp_globalization(self._h, C.byref(m), C.byref(e), C.byref(r), C.byref(a)), "cfnmpc_get_sqp_globalization")
+        return SQP_MODES[m.value], e.value, r.value, a.value
+
+    def sqp_ls_stats(self):
+        """-> (alpha [B], mu [B], n_short [B], n_fail [B]) of the last solve_sqp: step length of the last executed iteration,
+        penalty, iterations with alpha < 1, iterations without an accepted trial"""
+        al = np.empty(self.B); mu = np.empty(self.B); ns = np.empty(self.B, dtype=np.int32); nf = np.empty(self.B, dtype=np.int32)
+        _check(self._L.cfnmpc_get_sqp_ls_stats(self._h, al.ctypes.data_as(C.c_void_p), mu.ctypes.data_as(C.c_void_p),
+                                               ns.ctypes.data_as(C.c_void_p), nf.ctypes.data_as(C.c_void_p), 0,
+                                               _launch_stream(None, self._device)), "cfnmpc_get_sqp_ls_stats")
+        return al, mu, ns, nf
 
     def eval_nlp(self, keep_multipliers=False, stream=None):
         """NLP cost, KKT residuals and (keep_multipliers) costates / reduced gradient at the current iterate, from the data in

@@ -341,6 +341,35 @@ int cfnmpc_solve_sqp(cfnmpc_solver *s, int max_iter, double tol_step, double tol
 int cfnmpc_get_sqp_stats(cfnmpc_solver *s, int *status, int *sqp_iter, double *res /*[B][3]: step, eq, ineq*/,
                          int on_device, void *stream);
 
+/* Globalisation of cfnmpc_solve_sqp (acados: globalization = MERIT_BACKTRACKING beside nlp_solver_type = SQP; DESIGN.md section
+ * 5.17).  CFNMPC_SQP_FULL_STEP (default) is the solve described above.  With CFNMPC_SQP_MERIT_BACKTRACKING every iteration j
+ * searches along the step of its QP: w = w_{j-1}, w^ = the QP's candidate, d = w^ - w, per instance
+ *   c(v)  = (x_0 - x0, the N defects x_{k+1} - Phi(x_k, u_k), the box violations max(lb - u, 0) + max(u - ub, 0)), c1 = |c|_1;
+ *   gd    = sum_k s (W o (y_k - yref_k)).d_k + s_e (W_N o (x_N - yref_e)).d_xN,  dHd = sum_k s W.d_k^2 + s_e W_N.d_xN^2 at w
+ *           (the data of cfnmpc_eval_nlp; the cost is a linear least-squares form: J(w + a d) - J(w) = a gd + a^2 dHd / 2);
+ *   mu    = 0 at iteration 1; if c1(w) > 0: mu <- max(mu, (gd + dHd / 2) / ((1 - 0.5) c1(w))); it never decreases in a solve;
+ *   D     = gd - mu c1(w);
+ *   a_t   = reduction^t, t = 0 .. T, T the smallest integer with reduction^T <= alpha_min; the first t with
+ *           a_t gd + a_t^2 dHd / 2 + mu (c1(w + a_t d) - c1(w)) <= eta a_t D is accepted (differences only: no trial evaluates
+ *           the cost); without one the iteration takes a_T and counts in n_fail.  A NaN fails every comparison.
+ * w_j = w + a d (a = 1: the candidate, bit for bit); res_eq and res_ineq are those of w_j; res_step stays |d|_inf, the FULL
+ * step of the QP, so that a short step cannot pass for convergence.  An instance whose QP failed (status 4) kept its iterate
+ * and is not searched; classification, frozen instances and sqp_iter are those of the full-step solve.
+ * cfnmpc_set_sqp_globalization: eta, reduction, alpha_min = 0 select the defaults 1e-4, 0.5, 2^-10.  CFNMPC_EINVAL (nothing
+ * changes): a mode other than the two, eta outside (0, 0.5), reduction outside (0, 1), alpha_min outside (0, 1], T > 32.  The
+ * setting stays with the solver; cfnmpc_solve_sqp reads it, cfnmpc_solve does not.  cfnmpc_eval_sens_x0 is refused
+ * (CFNMPC_EINVAL) after a globalised solve: the last QP belongs to w_{j-1}, not to the iterate the solve left.
+ * cfnmpc_get_sqp_ls_stats, of the last cfnmpc_solve_sqp: alpha = step length of the instance's last executed iteration (1 after
+ * a full-step solve), mu = its penalty, n_short = its iterations with alpha < 1, n_fail = those without an accepted trial.
+ * Any pointer may be NULL, not all; CFNMPC_EINVAL before the first cfnmpc_solve_sqp.  The buffers (two doubles, two ints per
+ * instance) are allocated at the first globalised solve (cfnmpc_workspace_bytes counts them from then on). */
+#define CFNMPC_SQP_FULL_STEP 0
+#define CFNMPC_SQP_MERIT_BACKTRACKING 1
+int cfnmpc_set_sqp_globalization(cfnmpc_solver *s, int mode, double eta, double reduction, double alpha_min);
+int cfnmpc_get_sqp_globalization(const cfnmpc_solver *s, int *mode, double *eta, double *reduction, double *alpha_min);
+int cfnmpc_get_sqp_ls_stats(cfnmpc_solver *s, double *alpha /*[B]*/, double *mu /*[B]*/, int *n_short /*[B]*/,
+                            int *n_fail /*[B]*/, int on_device, void *stream);
+
 /* One complete control step from HOST buffers with a single synchronisation -- what the node
  * does per sample (acados_mpc.cpp:581-625: set lbx/ubx, N+1 yref rows, acados_solve(), read u/x):
  * x0 [B][13], yref [B][N][17], yref_e [B][13] in; one RTI step; the whole iterate out
@@ -536,6 +565,10 @@ int cfnmpc_fleet_solve_sqp(cfnmpc_fleet *f, int max_iter, double tol_step, doubl
                            void *stream);
 /* cfnmpc_get_sqp_stats in the fleet's vehicle order: status [B], sqp_iter [B], res [B][3] */
 int cfnmpc_fleet_get_sqp_stats(cfnmpc_fleet *f, int *status, int *sqp_iter, double *res, int on_device, void *stream);
+/* cfnmpc_set_sqp_globalization on every bucket (checked before anything changes), cfnmpc_get_sqp_ls_stats in the fleet's
+ * vehicle order */
+int cfnmpc_fleet_set_sqp_globalization(cfnmpc_fleet *f, int mode, double eta, double reduction, double alpha_min);
+int cfnmpc_fleet_get_sqp_ls_stats(cfnmpc_fleet *f, double *alpha, double *mu, int *n_short, int *n_fail, int on_device, void *stream);
 /* Solution sensitivities w.r.t. x0 of every bucket's last QP (cfnmpc_eval_sens_x0), rows in the fleet's vehicle order.  The range
  * is limited by the shortest horizon: dx up to stage Nmin, du below it.  Host arrays (on_device 0 or 2) are filled
  * synchronously. */
