@@ -161,6 +161,11 @@ int dev_alloc(cfnmpc_solver* s, T** p, size_t count) {
     if (hipMalloc(&q, count * sizeof(T)) != hipSuccess) return CFNMPC_ENOMEM;
     s->allocs.push_back(q);   // (before the memset: cfnmpc_free releases it on any later failure)
     if (hipMemset(q, 0, count * sizeof(T)) != hipSuccess) return CFNMPC_EHIP;
+    // hipMemset of device memory only ENQUEUES the fill on the null stream.  Buffers allocated at first use (the sensitivity
+    // arguments, the weight table, the line-search state, ...) are written right afterwards by kernels on the CALLER's stream; on
+    // a non-blocking stream (the shards of cfnmpc_multi, the buckets of cfnmpc_fleet) those are not ordered behind the null
+    // stream, and the fill could land on top of what they wrote.  Complete it here: allocations are off the step's path.
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return CFNMPC_EHIP;
     s->bytes += count * sizeof(T);
     *p = static_cast<T*>(q);
     return CFNMPC_OK;
