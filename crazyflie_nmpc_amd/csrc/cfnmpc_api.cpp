@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/cfnmpc.h"
+#include "cfnmpc_host.hpp"
 #include "cfnmpc_model.hpp"
 #include "cfnmpc_ws.hpp"
 #include "cfnmpc_sqp.h"
@@ -97,29 +98,8 @@ struct cfnmpc_solver {
 
 namespace {
 
-#define HIP_TRY(expr)                                                                               \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) {                                                                     \
-            std::fprintf(stderr, "cfnmpc: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_),   \
-                         __FILE__, __LINE__);                                                       \
-            return CFNMPC_EHIP;                                                                     \
-        }                                                                                           \
-    } while (0)
-
-// The solver lives on the device that was current at cfnmpc_create; every entry point that touches
-// it makes that device current for the duration of the call (a caller that drives several GPUs
-// from one thread may have another one selected).
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    explicit DeviceGuard(const cfnmpc_solver* s) {
-        if (s && hipGetDevice(&prev) == hipSuccess && prev != s->device) switched = hipSetDevice(s->device) == hipSuccess;
-    }
-    ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
+using cfn::DeviceGuard;
+using cfn::is_host;
 
 constexpr size_t MAX_PROFILED_STEPS = 4096;   // cfnmpc_get_profile resets the count
 constexpr size_t EV_PER_STEP = 7;
@@ -151,9 +131,6 @@ inline Choice choose_kernels(int batch, int N, int simds) {
     c.forward_split = true;
     return c;
 }
-
-// `on_device` argument: 0 host (synchronous), 2 host (enqueued only), anything else: device pointer
-inline bool is_host(int on_device) { return on_device == CFNMPC_ON_HOST || on_device == CFNMPC_ON_HOST_ASYNC; }
 
 template <typename T>
 int dev_alloc(cfnmpc_solver* s, T** p, size_t count) {
@@ -207,6 +184,17 @@ int get_field(cfnmpc_solver* s, double* dst, int on_device, int S, int E, int pe
         HIP_TRY(hipMemcpyAsync(dst, ddst, n * sizeof(double), hipMemcpyDeviceToHost, st));
         if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
     }
+    return CFNMPC_OK;
+}
+
+// The flat getters: device arrays of the solver -> the caller's host or device arrays, one copy per output that was asked for
+// (dst != nullptr) on `st`; complete on return for CFNMPC_ON_HOST.
+struct Out { void* dst; const void* src; size_t bytes; };
+int copy_out(std::initializer_list<Out> outs, int on_device, hipStream_t st) {
+    const hipMemcpyKind kind = is_host(on_device) ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    for (const Out& o : outs)
+        if (o.dst) HIP_TRY(hipMemcpyAsync(o.dst, o.src, o.bytes, kind, st));
+    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
     return CFNMPC_OK;
 }
 
@@ -273,14 +261,8 @@ int cfnmpc_abi_version(void) { return CFNMPC_ABI_VERSION; }
 
 int cfnmpc_create(cfnmpc_solver** out, int batch, const cfnmpc_opts* opts) {
     if (!out || batch <= 0) return CFNMPC_EINVAL;
-    // ABI guard: the first field is the size the caller's filler saw -- read BEFORE the struct is copied
-    if (opts && opts->struct_size != (int)sizeof(cfnmpc_opts)) {
-        std::fprintf(stderr, "cfnmpc: cfnmpc_opts of %d bytes handed to a library built for %d (ABI %d): rebuild against include/cfnmpc.h\n",
-                     opts->struct_size, (int)sizeof(cfnmpc_opts), CFNMPC_ABI_VERSION);
-        return CFNMPC_EINVAL;
-    }
     cfnmpc_opts o;
-    if (opts) o = *opts; else cfnmpc_default_opts(&o);
+    RC_TRY(cfn::take_opts(opts, &o));
     // Overlapped preparation (the next step's linearisation beside the constrained rows' kernels, double-buffered A / B / b):
     // measured slower at every fleet size -- since round 6 an experiment of the development build
     // (make DEV=1; CFNMPC_OVERLAP=1 in the environment), not an option of the product.
@@ -539,7 +521,7 @@ int cfnmpc_create(cfnmpc_solver** out, int batch, const cfnmpc_opts* opts) {
 
 int cfnmpc_free(cfnmpc_solver* s) {
     if (!s) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     if (s->aux) { (void)hipStreamSynchronize(s->aux); (void)hipStreamDestroy(s->aux); }
     if (s->P.as_side2) {
         (void)hipStreamSynchronize((hipStream_t)s->P.as_side2);
@@ -574,13 +556,13 @@ unsigned long long cfnmpc_workspace_bytes(const cfnmpc_solver* s) { return s ? s
 
 int cfnmpc_set_x0(cfnmpc_solver* s, const double* x0, int on_device, void* stream) {
     if (!s || !x0) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     return put_field(s, x0, on_device, 1, 13, 1, s->P.x0, (hipStream_t)stream);
 }
 
 int cfnmpc_set_yref(cfnmpc_solver* s, const double* yref, const double* yref_e, int on_device, void* stream) {
     if (!s || !yref || !yref_e) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     int rc = put_field(s, yref, on_device, s->P.N, 17, 1, s->P.yref, (hipStream_t)stream);
     if (rc != CFNMPC_OK) return rc;
     return put_field(s, yref_e, on_device, 1, 13, 1, s->P.yref_e, (hipStream_t)stream);
@@ -589,7 +571,7 @@ int cfnmpc_set_yref(cfnmpc_solver* s, const double* yref, const double* yref_e, 
 int cfnmpc_set_yref_windows(cfnmpc_solver* s, const double* traj, int n_rows, int* mode, int* iter,
                             const double* des_xyz, double uss, void* stream) {
     if (!s || !mode || !iter || !des_xyz) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     if (n_rows > 0 && (!traj || n_rows < s->P.N + 1)) return CFNMPC_EINVAL;
     if (n_rows <= 0 && traj) return CFNMPC_EINVAL;
     cfn::launch_windows(s->P, traj, n_rows > 0 ? n_rows : 0, mode, iter, des_xyz, uss, (hipStream_t)stream);
@@ -631,7 +613,7 @@ int cfnmpc_set_weights(cfnmpc_solver* s, const double* W, const double* WN) {
     invalidate_graphs(s);
     invalidate_sens(s);
     if (s->P.wtab) {   // "for all instances": each part given replaces that part in every row
-        DeviceGuard dg(s);
+        DeviceGuard dg(s->device);
         for (size_t i = 0; i < (size_t)s->P.B; i++) {
             if (W) std::copy_n(W, 17, s->w_rows.data() + i * 17);
             if (WN) std::copy_n(WN, 13, s->wn_rows.data() + i * 13);
@@ -643,7 +625,7 @@ int cfnmpc_set_weights(cfnmpc_solver* s, const double* W, const double* WN) {
 
 int cfnmpc_set_weights_batch(cfnmpc_solver* s, const double* W, const double* WN, int on_device, void* stream) {
     if (!s) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     cfn::Params& P = s->P;
     // not covered: the fused start solve (k_linfactor's weight table is shared by the four rows of a wavefront), partial
     // condensing (one weight vector per workgroup), the development build's overlapped preparation
@@ -691,7 +673,7 @@ int cfnmpc_set_weights_batch(cfnmpc_solver* s, const double* W, const double* WN
 
 int cfnmpc_get_weights_batch(cfnmpc_solver* s, double* W, double* WN, int on_device, void* stream) {
     if (!s || (!W && !WN)) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     const size_t B = s->P.B;
     std::vector<double> w = s->w_rows, wn = s->wn_rows;
     if (w.empty()) {
@@ -720,7 +702,7 @@ int cfnmpc_set_cost_scaling(cfnmpc_solver* s, double stage_scale, double termina
     for (int i = 0; i < 13; i++) s->P.WN[i] = terminal_scale * s->WN_set[i];
     invalidate_graphs(s);
     if (s->P.wtab) {   // rescales the rows in force
-        DeviceGuard dg(s);
+        DeviceGuard dg(s->device);
         return upload_weight_rows(s, nullptr);
     }
     return CFNMPC_OK;
@@ -743,7 +725,7 @@ int cfnmpc_erk_steps(const cfnmpc_solver* s) { return s ? s->P.erk_steps : CFNMP
 static_assert(CFNMPC_NP == cfn::NPAR, "parameter row");
 int cfnmpc_set_model_params(cfnmpc_solver* s, const double* p, int on_device, void* stream) {
     if (!s) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     cfn::Params& P = s->P;
     if (!p) {   // back to the folded constants (the default kernels)
         if (P.mpar) { P.mpar = nullptr; s->lin_valid = false; invalidate_graphs(s); }
@@ -788,7 +770,7 @@ int cfnmpc_set_model_params(cfnmpc_solver* s, const double* p, int on_device, vo
 
 int cfnmpc_get_model_params(cfnmpc_solver* s, double* p, int on_device, void* stream) {
     if (!s || !p) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     const size_t B = s->P.B, n = B * cfn::NPAR;
     std::vector<double> nom;
     const double* src = s->mp_rows.data();
@@ -815,7 +797,7 @@ int cfnmpc_set_box(cfnmpc_solver* s, double u_min, double u_max) {
 
 int cfnmpc_set_box_stages(cfnmpc_solver* s, const double* lb, const double* ub, int on_device, void* stream) {
     if (!s || ((lb == nullptr) != (ub == nullptr))) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     cfn::Params& P = s->P;
     if (!lb) {                       // back to the scalar box of cfnmpc_set_box
         if (P.lbs) { s->lbs_keep = P.lbs; s->ubs_keep = P.ubs; }
@@ -865,7 +847,7 @@ int cfnmpc_set_box_stages(cfnmpc_solver* s, const double* lb, const double* ub, 
 
 int cfnmpc_get_cmd(cfnmpc_solver* s, double* cmd_vel, int* motvel, int on_device, void* stream) {
     if (!s || !cmd_vel) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     hipStream_t st = (hipStream_t)stream;
     const size_t B = s->P.B;
     if (!is_host(on_device)) {
@@ -887,7 +869,7 @@ int cfnmpc_get_cmd(cfnmpc_solver* s, double* cmd_vel, int* motvel, int on_device
 
 int cfnmpc_init_iterate(cfnmpc_solver* s, int mode, void* stream) {
     if (!s || (mode != CFNMPC_INIT_ACADOS && mode != CFNMPC_INIT_HOVER)) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     cfn::launch_init_iterate(s->P, mode, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     if (s->P.as_warm) HIP_TRY(hipMemsetAsync(s->P.wvalid, 0, sizeof(int) * (size_t)s->P.B, (hipStream_t)stream));   // a new iterate: no set to start from
@@ -898,7 +880,7 @@ int cfnmpc_init_iterate(cfnmpc_solver* s, int mode, void* stream) {
 
 int cfnmpc_set_iterate(cfnmpc_solver* s, const double* x, const double* u, int on_device, void* stream) {
     if (!s || !x || !u) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     s->lin_valid = false;
     invalidate_sens(s);
     if (s->P.as_warm) HIP_TRY(hipMemsetAsync(s->P.wvalid, 0, sizeof(int) * (size_t)s->P.B, (hipStream_t)stream));
@@ -909,7 +891,7 @@ int cfnmpc_set_iterate(cfnmpc_solver* s, const double* x, const double* u, int o
 
 int cfnmpc_get_iterate(cfnmpc_solver* s, double* x, double* u, int on_device, void* stream) {
     if (!s || !x || !u) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     int rc = get_field(s, x, on_device, s->P.N + 1, 13, 1, 0, s->P.N + 1, s->P.xit, (hipStream_t)stream);
     if (rc != CFNMPC_OK) return rc;
     return get_field(s, u, on_device, s->P.N, 4, 0, 0, s->P.N, s->P.uit, (hipStream_t)stream);
@@ -1054,7 +1036,7 @@ int sqp_check_args(const cfnmpc_solver* s, int max_iter, double tol_step, double
 int sqp_begin(cfnmpc_solver* s, int max_iter, double tol_step, double tol_eq, double tol_ineq, void* stream) {
     const int rc = sqp_check_args(s, max_iter, tol_step, tol_eq, tol_ineq);
     if (rc != CFNMPC_OK) return rc;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     if (!s->h_sqp_cnt) HIP_TRY(hipHostMalloc((void**)&s->h_sqp_cnt, 2 * sizeof(unsigned), hipHostMallocDefault));
     if (!s->sqp_ev) HIP_TRY(hipEventCreateWithFlags(&s->sqp_ev, hipEventDisableTiming));
     s->sqp.max_iter = max_iter;
@@ -1081,7 +1063,7 @@ int sqp_begin(cfnmpc_solver* s, int max_iter, double tol_step, double tol_eq, do
 
 // enqueues SQP iteration s->sqp.j + 1 (step + check) and the read-back of its count of open rows; records s->sqp_ev behind it
 int sqp_iterate(cfnmpc_solver* s, void* stream) {
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     hipStream_t st = (hipStream_t)stream;
     s->sqp.j++;
     const int rc = rti_step(s, st, false, &s->sqp);
@@ -1094,7 +1076,7 @@ int sqp_iterate(cfnmpc_solver* s, void* stream) {
 
 // waits for the last enqueued iteration; *open = its rows not yet done
 int sqp_wait(cfnmpc_solver* s, unsigned* open) {
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     HIP_TRY(hipEventSynchronize(s->sqp_ev));
     *open = *(volatile unsigned*)s->h_sqp_cnt;
     return CFNMPC_OK;
@@ -1120,10 +1102,9 @@ int sqp_set_globalization(cfnmpc_solver* s, int mode, double eta, double reducti
 
 int sqp_get_ls_stats(cfnmpc_solver* s, double* alpha, double* mu, int* n_short, int* n_fail, int on_device, void* stream) {
     if (!s || s->ls_last < 0 || (!alpha && !mu && !n_short && !n_fail)) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     hipStream_t st = (hipStream_t)stream;
     const bool host = is_host(on_device);
-    const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     const size_t B = s->P.B;
     if (s->ls_last == CFNMPC_SQP_FULL_STEP) {   // full steps: alpha = 1, no penalty, nothing shortened (no buffer needed)
         if (host) {
@@ -1143,25 +1124,16 @@ int sqp_get_ls_stats(cfnmpc_solver* s, double* alpha, double* mu, int* n_short, 
         if (n_fail) HIP_TRY(hipMemsetAsync(n_fail, 0, B * sizeof(int), st));
         return CFNMPC_OK;
     }
-    if (alpha) HIP_TRY(hipMemcpyAsync(alpha, s->ls.alpha, B * sizeof(double), kind, st));
-    if (mu) HIP_TRY(hipMemcpyAsync(mu, s->ls.mu, B * sizeof(double), kind, st));
-    if (n_short) HIP_TRY(hipMemcpyAsync(n_short, s->ls.n_short, B * sizeof(int), kind, st));
-    if (n_fail) HIP_TRY(hipMemcpyAsync(n_fail, s->ls.n_fail, B * sizeof(int), kind, st));
-    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return CFNMPC_OK;
+    return copy_out({{alpha, s->ls.alpha, B * sizeof(double)}, {mu, s->ls.mu, B * sizeof(double)},
+                     {n_short, s->ls.n_short, B * sizeof(int)}, {n_fail, s->ls.n_fail, B * sizeof(int)}}, on_device, st);
 }
 
 int sqp_get_stats(cfnmpc_solver* s, int* status, int* sqp_iter, double* res, int on_device, void* stream) {
     if (!s) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
-    hipStream_t st = (hipStream_t)stream;
-    const hipMemcpyKind kind = !is_host(on_device) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    DeviceGuard dg(s->device);
     const size_t B = s->P.B;
-    if (status) HIP_TRY(hipMemcpyAsync(status, s->sqp.status, B * sizeof(int), kind, st));
-    if (sqp_iter) HIP_TRY(hipMemcpyAsync(sqp_iter, s->sqp.iter, B * sizeof(int), kind, st));
-    if (res) HIP_TRY(hipMemcpyAsync(res, s->sqp.res, B * 3 * sizeof(double), kind, st));
-    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return CFNMPC_OK;
+    return copy_out({{status, s->sqp.status, B * sizeof(int)}, {sqp_iter, s->sqp.iter, B * sizeof(int)}, {res, s->sqp.res, B * 3 * sizeof(double)}},
+                    on_device, (hipStream_t)stream);
 }
 
 }  // namespace cfn
@@ -1170,7 +1142,7 @@ extern "C" {
 
 int cfnmpc_solve(cfnmpc_solver* s, int n_rti, void* stream) {
     if (!s || n_rti < 1) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     hipStream_t st = (hipStream_t)stream;
     for (int it = 0; it < n_rti; it++) {
         const int rc = rti_step(s, st, s->reinit_failed != 0, nullptr);
@@ -1216,7 +1188,7 @@ int cfnmpc_get_sqp_ls_stats(cfnmpc_solver* s, double* alpha, double* mu, int* n_
 int cfnmpc_step_host(cfnmpc_solver* s, const double* x0, const double* yref, const double* yref_e, double* u,
                      double* x, int* status, int* qp_iter, double* res, void* stream) {
     if (!s || !x0 || !yref || !yref_e) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     hipStream_t st = (hipStream_t)stream;
     const cfn::Params& P = s->P;
     const size_t B = P.B, N = P.N;
@@ -1263,33 +1235,28 @@ int cfnmpc_step_host(cfnmpc_solver* s, const double* x0, const double* yref, con
 
 int cfnmpc_get_u(cfnmpc_solver* s, int stage, double* u, int on_device, void* stream) {
     if (!s || !u || stage < 0 || stage >= s->P.N) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     return get_field(s, u, on_device, 1, 4, 0, stage, s->P.N, s->P.uit, (hipStream_t)stream);
 }
 
 int cfnmpc_get_x(cfnmpc_solver* s, int stage, double* x, int on_device, void* stream) {
     if (!s || !x || stage < 0 || stage > s->P.N) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     return get_field(s, x, on_device, 1, 13, 1, stage, s->P.N + 1, s->P.xit, (hipStream_t)stream);
 }
 
 int cfnmpc_get_stats(cfnmpc_solver* s, int* status, int* qp_iter, double* res, int on_device, void* stream) {
     if (!s) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
-    hipStream_t st = (hipStream_t)stream;
-    const hipMemcpyKind kind = !is_host(on_device) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    DeviceGuard dg(s->device);
     const size_t B = s->P.B;
-    if (status) HIP_TRY(hipMemcpyAsync(status, s->P.status, B * sizeof(int), kind, st));
-    if (qp_iter) HIP_TRY(hipMemcpyAsync(qp_iter, s->P.iters, B * sizeof(int), kind, st));
-    if (res) HIP_TRY(hipMemcpyAsync(res, s->P.res, B * sizeof(double), kind, st));
-    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return CFNMPC_OK;
+    return copy_out({{status, s->P.status, B * sizeof(int)}, {qp_iter, s->P.iters, B * sizeof(int)}, {res, s->P.res, B * sizeof(double)}},
+                    on_device, (hipStream_t)stream);
 }
 
 // ---- NLP evaluation at the current iterate --------------------------------------------------------
 int cfnmpc_eval_nlp(cfnmpc_solver* s, int keep_multipliers, void* stream) {
     if (!s || (keep_multipliers != 0 && keep_multipliers != 1)) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     cfn::NlpArgs& A = s->nlp;
     if (keep_multipliers && !A.gu) {   // costates in the x-iterate's layout, reduced gradient in the u-iterate's (spare block included)
         const size_t NW = (size_t)s->P.NW + 1, N = s->P.N;
@@ -1309,19 +1276,14 @@ int cfnmpc_eval_nlp(cfnmpc_solver* s, int keep_multipliers, void* stream) {
 
 int cfnmpc_get_nlp_stats(cfnmpc_solver* s, double* cost, double* res, int on_device, void* stream) {
     if (!s || s->nlp_state == 0 || (!cost && !res)) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
-    hipStream_t st = (hipStream_t)stream;
-    const hipMemcpyKind kind = !is_host(on_device) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    DeviceGuard dg(s->device);
     const size_t B = s->P.B;
-    if (cost) HIP_TRY(hipMemcpyAsync(cost, s->nlp.cost, B * sizeof(double), kind, st));
-    if (res) HIP_TRY(hipMemcpyAsync(res, s->nlp.res, B * 3 * sizeof(double), kind, st));
-    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return CFNMPC_OK;
+    return copy_out({{cost, s->nlp.cost, B * sizeof(double)}, {res, s->nlp.res, B * 3 * sizeof(double)}}, on_device, (hipStream_t)stream);
 }
 
 int cfnmpc_get_nlp_multipliers(cfnmpc_solver* s, double* pi, double* gu, int on_device, void* stream) {
     if (!s || s->nlp_state != 2 || (!pi && !gu)) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     const int N = s->P.N;
     if (pi) {
         const int rc = get_field(s, pi, on_device, N + 1, 13, 1, 0, N + 1, s->nlp.pi, (hipStream_t)stream);
@@ -1336,7 +1298,7 @@ int cfnmpc_eval_sens_x0(cfnmpc_solver* s, double act_tol, void* stream) {
     if (!s || !std::isfinite(act_tol) || !(act_tol > 0.0)) return CFNMPC_EINVAL;
     // partial condensing and the fused start solve (start_solve = 2) write no home blocks / gains / checkpoints
     if (s->P.cond_N2 || s->P.fused == 1 || s->sens_src == 0) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     cfn::SensArgs& A = s->sens;
     const size_t NW = (size_t)s->P.NW + 1, N = s->P.N, B = s->P.B;
     if (!A.K) {
@@ -1362,7 +1324,7 @@ int cfnmpc_get_sens_x0(cfnmpc_solver* s, int stage, int n_stages, double* du, do
     const int N = s->P.N;
     if (stage < 0 || n_stages < 1 || (long)stage + n_stages > N + 1 || (!du && !dx) || (du && stage + n_stages > N))
         return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     hipStream_t st = (hipStream_t)stream;
     cfn::SensArgs A = s->sens;
     A.status = s->sens_src == 2 ? s->sqp.status : s->P.status;
@@ -1402,12 +1364,8 @@ int cfnmpc_get_sens_x0(cfnmpc_solver* s, int stage, int n_stages, double* du, do
 
 int cfnmpc_get_sens_active(cfnmpc_solver* s, signed char* act, int on_device, void* stream) {
     if (!s || !act || !s->sens_valid) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t n = (size_t)s->P.B * s->P.N * 4;
-    HIP_TRY(hipMemcpyAsync(act, s->sens.mask, n, is_host(on_device) ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
-    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return CFNMPC_OK;
+    DeviceGuard dg(s->device);
+    return copy_out({{act, s->sens.mask, (size_t)s->P.B * s->P.N * 4}}, on_device, (hipStream_t)stream);
 }
 
 namespace {
@@ -1487,7 +1445,7 @@ int cfnmpc_set_profiling(cfnmpc_solver* s, int enable) {
 // later timed steps are dropped); resets the count like cfnmpc_get_profile_kernels
 int cfnmpc_get_profile_steps(cfnmpc_solver* s, double* ms_steps, int max_steps, int* n_steps) {
     if (!s || !ms_steps || max_steps < 0 || !n_steps) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     size_t n = s->ev_used / EV_PER_STEP;
     if (n > (size_t)max_steps) n = (size_t)max_steps;
     for (size_t i = 0; i < n; i++) {
@@ -1551,7 +1509,7 @@ int cfnmpc_debug_prof(unsigned long long* out, int reset) { (void)hipDeviceSynch
 // either way (bitwise: the same arithmetic).  Leaves the solver ready for cfnmpc_solve.
 int cfnmpc_debug_chunked_pair(cfnmpc_solver* s, int chunk, int reps, double* ms, void* stream) {
     if (!s || chunk < 0 || reps < 1 || !ms) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     hipStream_t st = (hipStream_t)stream;
     cfn::Params P = s->P;
     if (chunk > 0 && !P.Ppark) {
@@ -1592,7 +1550,7 @@ int cfnmpc_debug_chunked_pair(cfnmpc_solver* s, int chunk, int reps, double* ms,
 // bitwise-equal arrays) -- checker of the chunked experiment
 int cfnmpc_debug_checksum(cfnmpc_solver* s, double* out3) {
     if (!s || !out3) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     const cfn::Params& P = s->P;
     HIP_TRY(hipDeviceSynchronize());
     const size_t n[3] = {(size_t)P.NW * P.N * cfn::SZ_K, (size_t)P.NW * 4 * P.N * 4, (size_t)P.NW * cfn::N_CHK * cfn::SZ_PP};
@@ -1616,7 +1574,7 @@ int cfnmpc_debug_start_factor(cfnmpc_solver* s, int mode, int reps, double* ms, 
     // keeps them instance-major and never runs these kernels -- refuse instead of reading and writing in the wrong layout
     if (s->P.cond_N2 || !s->P.v4b) return CFNMPC_EINVAL;
     if (mode == 2 && (s->P.mpar || s->P.wtab)) return CFNMPC_EINVAL;   // (k_linfactor: folded model constants, uniform weights)
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     invalidate_sens(s);   // (rewrites KR / Pchk: they no longer belong to the last QP)
     hipStream_t st = (hipStream_t)stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1647,7 +1605,7 @@ int cfnmpc_debug_start_factor(cfnmpc_solver* s, int mode, int reps, double* ms, 
 // (stages 4, 8, 12, 16, 24, 32; only those below N are written by the kernels), status [B].
 int cfnmpc_debug_get_factor(cfnmpc_solver* s, double* K, double* d, double* Pchk, int* status) {
     if (!s || s->P.cond_N2 || !s->P.v4b) return CFNMPC_EINVAL;   // (as cfnmpc_debug_start_factor)
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     const cfn::Params& P = s->P;
     const size_t NW = P.NW, N = P.N, B = P.B;
     HIP_TRY(hipDeviceSynchronize());
@@ -1690,7 +1648,7 @@ int cfnmpc_debug_get_factor(cfnmpc_solver* s, double* K, double* d, double* Pchk
 // part 1: k_linfactor; part 2: everything behind it + the swap of the iterate buffers; flags bit 0: k_forward_half
 int cfnmpc_debug_solve_part(cfnmpc_solver* s, int part, int flags, void* stream) {
     if (!s || s->P.fused != 1 || s->P.lbs) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     hipStream_t st = (hipStream_t)stream;
     if (part == 1) cfn::launch_linfactor(s->P, st);
     else {
@@ -1709,7 +1667,7 @@ int cfnmpc_debug_solve_part(cfnmpc_solver* s, int part, int flags, void* stream)
 
 int cfnmpc_debug_linearise(cfnmpc_solver* s, void* stream) {
     if (!s) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     invalidate_sens(s);   // (rewrites AR / BR / b: they no longer belong to the last QP)
     cfn::launch_linearise(s->P, s->chunks_all, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
@@ -1721,7 +1679,7 @@ int cfnmpc_debug_get_linearisation(cfnmpc_solver* s, double* A, double* Bm, doub
     // Decodes the row-distributed stage blocks (AR, BR, b) into dense arrays in the EXTERNAL
     // state order: A [B][N][13][13], Bm [B][N][13][4], b [B][N][13].
     if (!s || !A || !Bm || !b) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     const cfn::Params& P = s->P;
     const size_t NW = ((size_t)P.NW / 16 + 1) * 16, N = P.N, B = P.B;   // (whole groups of 16 blocks)
     std::vector<double> ha(NW * N * cfn::SZ_A), hb(NW * N * cfn::SZ_B), hv(NW * N * cfn::SZ_V13);
@@ -1758,7 +1716,7 @@ int cfnmpc_debug_get_linearisation(cfnmpc_solver* s, double* A, double* Bm, doub
 
 int cfnmpc_debug_get_condensed(cfnmpc_solver* s, int block, double* H, double* D, int* m_out) {
     if (!s || !H || !D || !s->P.cond_N2 || block < 0 || block >= s->P.cond_N2) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     const cfn::Params& P = s->P;
     cfn::launch_linearise(P, s->chunks_all, nullptr);
     cfn::launch_pcond(P, nullptr);
@@ -1788,7 +1746,7 @@ int cfnmpc_debug_get_condensed(cfnmpc_solver* s, int block, double* H, double* D
 
 int cfnmpc_debug_get_viol(cfnmpc_solver* s, double* viol) {   // largest bound violation of the unconstrained minimiser (0: feasible)
     if (!s || !viol) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(viol, s->P.viol, (size_t)s->P.B * sizeof(double), hipMemcpyDeviceToHost));
     return CFNMPC_OK;
@@ -1796,7 +1754,7 @@ int cfnmpc_debug_get_viol(cfnmpc_solver* s, double* viol) {   // largest bound v
 
 int cfnmpc_debug_get_head(cfnmpc_solver* s, int* head) {
     if (!s || !head) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(head, s->P.head, (size_t)s->P.B * sizeof(int), hipMemcpyDeviceToHost));
     return CFNMPC_OK;
@@ -1807,7 +1765,7 @@ int cfnmpc_debug_get_head(cfnmpc_solver* s, int* head) {
 // more than 16 stages | LATE rows of a split forward sweep (first violation behind stage 24, appended to the list by part two).
 int cfnmpc_debug_get_list_counts(cfnmpc_solver* s, int* counts) {
     if (!s || !counts) return CFNMPC_EINVAL;
-    DeviceGuard dg(s);
+    DeviceGuard dg(s->device);
     HIP_TRY(hipDeviceSynchronize());
     int h[64];
     HIP_TRY(hipMemcpy(h, s->P.nipm, sizeof h, hipMemcpyDeviceToHost));

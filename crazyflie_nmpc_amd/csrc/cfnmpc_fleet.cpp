@@ -4,8 +4,9 @@
 // owns one vehicle per process; BASELINE.json's config C5 runs N in {30, 50, 100} side by side.
 // A cfnmpc_solver's workspace is blocked by stage for ONE horizon, so a fleet buckets its
 // vehicles by N: one solver per distinct horizon, addressed through index lists.  Fleet-level
-// arrays keep the caller's vehicle order; rows move between that order and the buckets with
-// the row gather / scatter kernel below (device pointers) or on the host (host pointers).
+// arrays keep the caller's vehicle order; rows move between that order and the buckets in ONE
+// place, fleet_io below: an entry point names its arrays as columns
+// (cfnmpc_rows.hpp: Col) and the bucket call they go to or come from.
 // Buckets are solved concurrently, each on its own stream forked from the caller's.
 #include <hip/hip_runtime.h>
 
@@ -14,10 +15,17 @@
 #include <vector>
 
 #include "../../include/cfnmpc.h"
+#include "cfnmpc_host.hpp"
 #include "cfnmpc_model.hpp"
 #include "cfnmpc_sqp.h"
 
 namespace {
+
+using cfn::col;
+using cfn::col_stages;
+using cfn::Cols;
+using cfn::Layout;
+using cfn::Staged;
 
 // dst bucket row r  <-  src fleet row idx[r]   (GATHER)
 // dst fleet row idx[r]  <-  src bucket row r   (!GATHER)
@@ -34,15 +42,14 @@ __global__ void k_rows(const T* __restrict__ src, T* __restrict__ dst, const int
 }
 
 template <typename T, bool GATHER>
-void rows(const T* src, T* dst, const int* idx, int count, int len, long fstride, hipStream_t st) {
+void rows(T* fleet, T* stage, const int* idx, int count, int len, long fstride, hipStream_t st) {
     const int bx = len >= 256 ? 256 : 64;
     // blockIdx.y is limited to 65535: walk the bucket in slabs
     for (int r0 = 0; r0 < count; r0 += 65535) {
         const int n = std::min(65535, count - r0);
-        const T* s = GATHER ? src : src + (long)r0 * len;
-        T* d = GATHER ? dst + (long)r0 * len : dst;
-        hipLaunchKernelGGL((k_rows<T, GATHER>), dim3((len + bx - 1) / bx, n), dim3(bx), 0, st, s, d, idx + r0, n, len,
-                           fstride);
+        T* s = stage + (long)r0 * len;
+        hipLaunchKernelGGL((k_rows<T, GATHER>), dim3((len + bx - 1) / bx, n), dim3(bx), 0, st, GATHER ? fleet : s, GATHER ? s : fleet,
+                           idx + r0, n, len, fstride);
     }
 }
 
@@ -51,45 +58,29 @@ struct Bucket {
     cfnmpc_solver* s = nullptr;
     std::vector<int> idx;       // fleet index of every bucket row
     int* d_idx = nullptr;
-    double* d_rows = nullptr;   // [count][N*17] staging in bucket order (device-pointer calls)
-    int* d_ints = nullptr;      // [2][count]
-    double* d_sens = nullptr;   // [count][rows of cfnmpc_get_sens_x0] staging of device-pointer sensitivity reads (grown on demand)
-    size_t n_sens = 0;
+    void* d_stage = nullptr;    // staging in bucket order of device-pointer calls: n_stage bytes, grown on demand (staging())
+    size_t n_stage = 0;
     hipStream_t st = nullptr;
     hipEvent_t done = nullptr;
 };
 
 }  // namespace
 
+// (the fleet lives on the device that was current at cfnmpc_fleet_create, as its solvers do)
 struct cfnmpc_fleet {
     int B = 0, Nmin = 0, Nmax = 0, device = 0;
-    std::vector<Bucket> bk;      // ascending N (the order of cfnmpc_fleet_bucket)
-    std::vector<int> order;      // bucket indices by decreasing work N x vehicles: launch order, stream priorities
+    std::vector<Bucket> bk;       // ascending N (the order of cfnmpc_fleet_bucket)
+    std::vector<int> order;       // bucket indices by decreasing work N x vehicles: launch order, stream priorities
     hipEvent_t fork = nullptr;
-    std::vector<double> h_rows;  // host staging in bucket order (host-pointer calls)
-    std::vector<int> h_ints;
+    std::vector<double> h_stage;  // host staging in bucket order (host-pointer calls)
 };
-
-#define HIP_TRY(x) do { if ((x) != hipSuccess) return CFNMPC_EHIP; } while (0)
-
-// the fleet lives on the device that was current at cfnmpc_fleet_create (as its solvers do)
-struct FleetDevice {
-    int prev = -1;
-    bool switched = false;
-    explicit FleetDevice(const cfnmpc_fleet* f) {
-        if (f && hipGetDevice(&prev) == hipSuccess && prev != f->device) switched = hipSetDevice(f->device) == hipSuccess;
-    }
-    ~FleetDevice() { if (switched) (void)hipSetDevice(prev); }
-    FleetDevice(const FleetDevice&) = delete;
-    FleetDevice& operator=(const FleetDevice&) = delete;
-};
-#define RC_TRY(x) do { int rc_ = (x); if (rc_ != CFNMPC_OK) return rc_; } while (0)
 
 namespace {
 
 // run fn(bucket, stream) for every bucket on its own stream, forked from / joined to `user`
 template <typename F>
 int on_buckets(cfnmpc_fleet* f, hipStream_t user, F fn) {
+    cfn::DeviceGuard dg(f->device);
     HIP_TRY(hipEventRecord(f->fork, user));
     for (int bi : f->order) {   // (heaviest bucket first)
         Bucket& b = f->bk[bi];
@@ -101,12 +92,65 @@ int on_buckets(cfnmpc_fleet* f, hipStream_t user, F fn) {
     return CFNMPC_OK;
 }
 
-// fleet rows (host) -> bucket order (host staging); returns the staging pointer
-const double* host_gather(cfnmpc_fleet* f, const Bucket& b, const double* src, int len, long fstride) {
-    f->h_rows.resize((size_t)b.count * len);
-    for (int r = 0; r < b.count; r++) std::copy_n(src + (long)b.idx[r] * fstride, len, f->h_rows.data() + (size_t)r * len);
-    return f->h_rows.data();
+// The bucket's device staging, at least `bytes` long.  The first allocation already holds the largest request of the step's
+// calls (yref and yref_e: N x 17 + 13 doubles per vehicle), so those never reallocate; a longer request (a range of
+// sensitivities) replaces the buffer once the bucket's stream -- the only one that uses it -- has drained.
+int staging(Bucket& b, size_t bytes, hipStream_t st) {
+    if (bytes <= b.n_stage) return CFNMPC_OK;
+    if (b.d_stage) {
+        HIP_TRY(hipStreamSynchronize(st));   // (an earlier call may still use the old buffer)
+        (void)hipFree(b.d_stage);
+        b.d_stage = nullptr;
+        b.n_stage = 0;
+    }
+    const size_t want = std::max(bytes, sizeof(double) * (size_t)b.count * (b.N * 17 + 13));
+    if (hipMalloc(&b.d_stage, want) != hipSuccess) return CFNMPC_ENOMEM;
+    b.n_stage = want;
+    return CFNMPC_OK;
 }
+
+// device arrays: the requested columns between the caller's arrays and the bucket's staging, one launch per column on `st`
+template <bool GATHER>
+void dev_rows(const Layout& L, const Bucket& b, hipStream_t st) {
+    for (int i = 0; i < L.n; i++) {
+        void* fl = L.c[i].p, *sg = L.at(b.d_stage, i);
+        if (!fl) continue;
+        if (L.c[i].esz == sizeof(double)) rows<double, GATHER>((double*)fl, (double*)sg, b.d_idx, b.count, (int)L.len[i], (long)L.stride[i], st);
+        else rows<int, GATHER>((int*)fl, (int*)sg, b.d_idx, b.count, (int)L.len[i], (long)L.stride[i], st);
+    }
+}
+
+// Every fleet-level array call.  The columns are laid out in the bucket's staging -- the fleet's host staging for host arrays
+// (on_device 0 or 2: synchronous, bucket after bucket on the caller's stream), else the bucket's device staging, on the
+// bucket's stream inside on_buckets -- and call(bucket, staged columns, on_device, stream) is the bucket's own setter / getter.
+// WRITE: the rows are gathered from the caller's arrays before the call; else scattered to them after it.
+template <bool WRITE, typename F>
+int fleet_io(cfnmpc_fleet* f, int on_device, void* stream, Cols cols, F call) {
+    if (cfn::is_host(on_device)) {
+        cfn::DeviceGuard dg(f->device);
+        for (Bucket& b : f->bk) {
+            const Layout L(cols, b.count, b.N, f->Nmax);
+            f->h_stage.resize((L.bytes + 7) / 8);
+            void* base = f->h_stage.data();
+            if (WRITE) cfn::move_rows<true>(L, base, b.idx.data(), b.count);
+            RC_TRY(call(b, cfn::staged(L, base), (int)CFNMPC_ON_HOST, stream));
+            if (!WRITE) cfn::move_rows<false>(L, base, b.idx.data(), b.count);
+        }
+        return CFNMPC_OK;
+    }
+    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) {
+        const Layout L(cols, b.count, b.N, f->Nmax);
+        RC_TRY(staging(b, L.bytes, st));
+        if (WRITE) dev_rows<true>(L, b, st);
+        RC_TRY(call(b, cfn::staged(L, b.d_stage), (int)CFNMPC_ON_DEVICE, (void*)st));
+        if (!WRITE) dev_rows<false>(L, b, st);
+        return (int)CFNMPC_OK;
+    });
+}
+template <typename F>
+int fleet_write(cfnmpc_fleet* f, int on_device, void* stream, Cols cols, F call) { return fleet_io<true>(f, on_device, stream, cols, call); }
+template <typename F>
+int fleet_read(cfnmpc_fleet* f, int on_device, void* stream, Cols cols, F call) { return fleet_io<false>(f, on_device, stream, cols, call); }
 
 }  // namespace
 
@@ -115,9 +159,8 @@ extern "C" {
 int cfnmpc_fleet_create(cfnmpc_fleet** out, int batch, const int* N_per_instance, const cfnmpc_opts* opts) {
     if (!out || batch < 1 || !N_per_instance) return CFNMPC_EINVAL;
     *out = nullptr;
-    if (opts && opts->struct_size != (int)sizeof(cfnmpc_opts)) return CFNMPC_EINVAL;   // ABI guard (include/cfnmpc.h)
     cfnmpc_opts o;
-    if (opts) o = *opts; else cfnmpc_default_opts(&o);
+    RC_TRY(cfn::take_opts(opts, &o));
     const int cond_N2_req = o.cond_N2;
     if (cond_N2_req < 0) return CFNMPC_EINVAL;
     std::map<int, std::vector<int>> by_n;
@@ -145,8 +188,7 @@ int cfnmpc_fleet_create(cfnmpc_fleet** out, int batch, const int* N_per_instance
         o.cond_N2 = (cond_N2_req > 0 && cond_N2_req < b.N) ? cond_N2_req : 0;
         rc = cfnmpc_create(&b.s, b.count, &o);
         if (rc != CFNMPC_OK) break;
-        if (hipMalloc((void**)&b.d_idx, sizeof(int) * b.count) != hipSuccess ||
-            hipMalloc((void**)&b.d_ints, sizeof(int) * 2 * b.count) != hipSuccess) { rc = CFNMPC_ENOMEM; break; }
+        if (hipMalloc((void**)&b.d_idx, sizeof(int) * b.count) != hipSuccess) { rc = CFNMPC_ENOMEM; break; }
         if (hipMemcpy(b.d_idx, b.idx.data(), sizeof(int) * b.count, hipMemcpyHostToDevice) != hipSuccess ||
             hipEventCreateWithFlags(&b.done, hipEventDisableTiming) != hipSuccess) { rc = CFNMPC_EHIP; break; }
     }
@@ -171,14 +213,12 @@ int cfnmpc_fleet_create(cfnmpc_fleet** out, int batch, const int* N_per_instance
 
 int cfnmpc_fleet_free(cfnmpc_fleet* f) {
     if (!f) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
+    cfn::DeviceGuard dg(f->device);
     (void)hipDeviceSynchronize();
     for (Bucket& b : f->bk) {
         if (b.s) cfnmpc_free(b.s);
         if (b.d_idx) (void)hipFree(b.d_idx);
-        if (b.d_rows) (void)hipFree(b.d_rows);
-        if (b.d_ints) (void)hipFree(b.d_ints);
-        if (b.d_sens) (void)hipFree(b.d_sens);
+        if (b.d_stage) (void)hipFree(b.d_stage);
         if (b.st) (void)hipStreamDestroy(b.st);
         if (b.done) (void)hipEventDestroy(b.done);
     }
@@ -208,45 +248,16 @@ unsigned long long cfnmpc_fleet_workspace_bytes(const cfnmpc_fleet* f) {
     return t;
 }
 
-static int staging(Bucket& b) {
-    if (b.d_rows) return CFNMPC_OK;
-    return hipMalloc((void**)&b.d_rows, sizeof(double) * (size_t)b.count * (b.N * 17 + 13)) == hipSuccess ? CFNMPC_OK : CFNMPC_ENOMEM;
-}
-
 int cfnmpc_fleet_set_x0(cfnmpc_fleet* f, const double* x0, int on_device, void* stream) {
     if (!f || !x0) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
-    if (!on_device) {
-        for (Bucket& b : f->bk) RC_TRY(cfnmpc_set_x0(b.s, host_gather(f, b, x0, 13, 13), 0, stream));
-        return CFNMPC_OK;
-    }
-    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) {
-        RC_TRY(staging(b));
-        rows<double, true>(x0, b.d_rows, b.d_idx, b.count, 13, 13, st);
-        return cfnmpc_set_x0(b.s, b.d_rows, 1, st);
-    });
+    return fleet_write(f, on_device, stream, {col(x0, 13)},
+                       [](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_set_x0(b.s, p.d(0), mode, st); });
 }
 
 int cfnmpc_fleet_set_yref(cfnmpc_fleet* f, const double* yref, const double* yref_e, int on_device, void* stream) {
     if (!f || !yref || !yref_e) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
-    const long fs = (long)f->Nmax * 17;
-    if (!on_device) {
-        std::vector<double> ye;
-        for (Bucket& b : f->bk) {
-            ye.resize((size_t)b.count * 13);
-            for (int r = 0; r < b.count; r++) std::copy_n(yref_e + (long)b.idx[r] * 13, 13, ye.data() + (size_t)r * 13);
-            RC_TRY(cfnmpc_set_yref(b.s, host_gather(f, b, yref, b.N * 17, fs), ye.data(), 0, stream));
-        }
-        return CFNMPC_OK;
-    }
-    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) {
-        RC_TRY(staging(b));
-        double* e = b.d_rows + (size_t)b.count * b.N * 17;
-        rows<double, true>(yref, b.d_rows, b.d_idx, b.count, b.N * 17, fs, st);
-        rows<double, true>(yref_e, e, b.d_idx, b.count, 13, 13, st);
-        return cfnmpc_set_yref(b.s, b.d_rows, e, 1, st);
-    });
+    return fleet_write(f, on_device, stream, {col_stages(yref, 17), col(yref_e, 13)},
+                       [](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_set_yref(b.s, p.d(0), p.d(1), mode, st); });
 }
 
 int cfnmpc_fleet_set_weights(cfnmpc_fleet* f, const double* W, const double* WN) {
@@ -268,44 +279,25 @@ int cfnmpc_fleet_set_cost_scaling(cfnmpc_fleet* f, double stage_scale, double te
     return CFNMPC_OK;
 }
 
-// per-instance model parameters: rows in the fleet's vehicle order -> each bucket's order, each bucket's copy on its own
+// per-instance model parameters: host rows in the fleet's vehicle order -> each bucket's order, each bucket's copy on its own
 // stream (complete when the call returns).  The rows are validated as a whole first, so a bad row leaves every bucket
 // unchanged.  A bucket refuses parameters only for options every bucket shares (start_solve 2 / 3), so the FIRST bucket
 // refuses and nothing has changed either (cfnmpc_fleet_set_erk_steps relies on the same).
 int cfnmpc_fleet_set_model_params(cfnmpc_fleet* f, const double* p) {
     if (!f) return CFNMPC_EINVAL;
     if (p && !cfn::model_params_ok(p, (size_t)f->B * CFNMPC_NP)) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
-    std::vector<double> h;
-    for (Bucket& b : f->bk) {
-        if (!p) { RC_TRY(cfnmpc_set_model_params(b.s, nullptr, CFNMPC_ON_HOST, b.st)); continue; }
-        h.resize((size_t)b.count * CFNMPC_NP);
-        for (int r = 0; r < b.count; r++) std::copy_n(p + (size_t)b.idx[r] * CFNMPC_NP, CFNMPC_NP, h.data() + (size_t)r * CFNMPC_NP);
-        RC_TRY(cfnmpc_set_model_params(b.s, h.data(), CFNMPC_ON_HOST, b.st));
-    }
-    return CFNMPC_OK;
+    return fleet_write(f, CFNMPC_ON_HOST, nullptr, {col(p, CFNMPC_NP)},
+                       [](Bucket& b, Staged q, int mode, void*) { return cfnmpc_set_model_params(b.s, q.d(0), mode, b.st); });
 }
 
-// per-instance cost weights: rows in the fleet's vehicle order -> each bucket's order.  Validated as a whole first, and a bucket
-// refuses rows only for options every bucket shares (start_solve 2 / 3, cond_N2), so the FIRST bucket refuses and nothing has
-// changed (as cfnmpc_fleet_set_model_params).
+// per-instance cost weights: host rows in the fleet's vehicle order -> each bucket's order.  Validated as a whole first, and a
+// bucket refuses rows only for options every bucket shares (start_solve 2 / 3, cond_N2), so the FIRST bucket refuses and nothing
+// has changed (as cfnmpc_fleet_set_model_params).
 int cfnmpc_fleet_set_weights_batch(cfnmpc_fleet* f, const double* W, const double* WN) {
     if (!f) return CFNMPC_EINVAL;
     if (!cfn::weight_rows_ok(W, WN, (size_t)f->B)) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
-    std::vector<double> hw, hn;
-    for (Bucket& b : f->bk) {
-        if (W) {
-            hw.resize((size_t)b.count * 17);
-            for (int r = 0; r < b.count; r++) std::copy_n(W + (size_t)b.idx[r] * 17, 17, hw.data() + (size_t)r * 17);
-        }
-        if (WN) {
-            hn.resize((size_t)b.count * 13);
-            for (int r = 0; r < b.count; r++) std::copy_n(WN + (size_t)b.idx[r] * 13, 13, hn.data() + (size_t)r * 13);
-        }
-        RC_TRY(cfnmpc_set_weights_batch(b.s, W ? hw.data() : nullptr, WN ? hn.data() : nullptr, CFNMPC_ON_HOST, b.st));
-    }
-    return CFNMPC_OK;
+    return fleet_write(f, CFNMPC_ON_HOST, nullptr, {col(W, 17), col(WN, 13)},
+                       [](Bucket& b, Staged p, int mode, void*) { return cfnmpc_set_weights_batch(b.s, p.d(0), p.d(1), mode, b.st); });
 }
 
 int cfnmpc_fleet_set_box(cfnmpc_fleet* f, double u_min, double u_max) {
@@ -318,113 +310,42 @@ int cfnmpc_fleet_set_box(cfnmpc_fleet* f, double u_min, double u_max) {
 // own horizon are ignored); NULL, NULL returns every bucket to the scalar box
 int cfnmpc_fleet_set_box_stages(cfnmpc_fleet* f, const double* lb, const double* ub) {
     if (!f || ((lb == nullptr) != (ub == nullptr))) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
-    std::vector<double> hl, hu;
-    for (Bucket& b : f->bk) {
-        if (!lb) { RC_TRY(cfnmpc_set_box_stages(b.s, nullptr, nullptr, 0, nullptr)); continue; }
-        const size_t row = (size_t)b.N * 4, frow = (size_t)f->Nmax * 4;
-        hl.resize((size_t)b.count * row); hu.resize((size_t)b.count * row);
-        for (int r = 0; r < b.count; r++) {
-            std::copy_n(lb + (size_t)b.idx[r] * frow, row, hl.data() + (size_t)r * row);
-            std::copy_n(ub + (size_t)b.idx[r] * frow, row, hu.data() + (size_t)r * row);
-        }
-        RC_TRY(cfnmpc_set_box_stages(b.s, hl.data(), hu.data(), 0, nullptr));
-    }
-    return CFNMPC_OK;
+    return fleet_write(f, CFNMPC_ON_HOST, nullptr, {col_stages(lb, 4), col_stages(ub, 4)},
+                       [](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_set_box_stages(b.s, p.d(0), p.d(1), mode, st); });
 }
 
 int cfnmpc_fleet_init_iterate(cfnmpc_fleet* f, int mode, void* stream) {
     if (!f) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
     return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) { return cfnmpc_init_iterate(b.s, mode, st); });
 }
 
 int cfnmpc_fleet_solve(cfnmpc_fleet* f, int n_rti, void* stream) {
     if (!f || n_rti < 1) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
     return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) { return cfnmpc_solve(b.s, n_rti, st); });
-}
-
-static int fleet_get(cfnmpc_fleet* f, int stage, double* out, int width, int on_device, void* stream,
-                     int (*get)(cfnmpc_solver*, int, double*, int, void*)) {
-    if (!on_device) {
-        for (Bucket& b : f->bk) {
-            f->h_rows.resize((size_t)b.count * width);
-            RC_TRY(get(b.s, stage, f->h_rows.data(), 0, stream));
-            for (int r = 0; r < b.count; r++) std::copy_n(f->h_rows.data() + (size_t)r * width, width, out + (long)b.idx[r] * width);
-        }
-        return CFNMPC_OK;
-    }
-    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) {
-        RC_TRY(staging(b));
-        RC_TRY(get(b.s, stage, b.d_rows, 1, st));
-        rows<double, false>(b.d_rows, out, b.d_idx, b.count, width, width, st);
-        return (int)CFNMPC_OK;
-    });
 }
 
 int cfnmpc_fleet_get_u(cfnmpc_fleet* f, int stage, double* u, int on_device, void* stream) {
     if (!f || !u || stage < 0 || stage >= f->Nmin) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
-    return fleet_get(f, stage, u, 4, on_device, stream, cfnmpc_get_u);
+    return fleet_read(f, on_device, stream, {col(u, 4)},
+                      [&](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_get_u(b.s, stage, p.d(0), mode, st); });
 }
 
 int cfnmpc_fleet_get_x(cfnmpc_fleet* f, int stage, double* x, int on_device, void* stream) {
     if (!f || !x || stage < 0 || stage > f->Nmin) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
-    return fleet_get(f, stage, x, 13, on_device, stream, cfnmpc_get_x);
+    return fleet_read(f, on_device, stream, {col(x, 13)},
+                      [&](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_get_x(b.s, stage, p.d(0), mode, st); });
 }
 
 int cfnmpc_fleet_get_cmd(cfnmpc_fleet* f, double* cmd_vel, int* motvel, int on_device, void* stream) {
     if (!f || !cmd_vel || f->Nmin < 4) return CFNMPC_EINVAL;   // the output stage reads u1 and x4
-    FleetDevice fd(f);
-    if (!on_device) {
-        for (Bucket& b : f->bk) {
-            f->h_rows.resize((size_t)b.count * 4);
-            f->h_ints.resize((size_t)b.count * 4);
-            RC_TRY(cfnmpc_get_cmd(b.s, f->h_rows.data(), motvel ? f->h_ints.data() : nullptr, 0, stream));
-            for (int r = 0; r < b.count; r++) {
-                std::copy_n(f->h_rows.data() + (size_t)r * 4, 4, cmd_vel + (long)b.idx[r] * 4);
-                if (motvel) std::copy_n(f->h_ints.data() + (size_t)r * 4, 4, motvel + (long)b.idx[r] * 4);
-            }
-        }
-        return CFNMPC_OK;
-    }
-    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) {
-        RC_TRY(staging(b));
-        int* mv = (int*)(b.d_rows + (size_t)b.count * 4);
-        RC_TRY(cfnmpc_get_cmd(b.s, b.d_rows, motvel ? mv : nullptr, 1, st));
-        rows<double, false>(b.d_rows, cmd_vel, b.d_idx, b.count, 4, 4, st);
-        if (motvel) rows<int, false>(mv, motvel, b.d_idx, b.count, 4, 4, st);
-        return (int)CFNMPC_OK;
-    });
+    return fleet_read(f, on_device, stream, {col(cmd_vel, 4), col(motvel, 4)},
+                      [](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_get_cmd(b.s, p.d(0), p.i(1), mode, st); });
 }
 
 int cfnmpc_fleet_get_stats(cfnmpc_fleet* f, int* status, int* qp_iter, double* res, int on_device, void* stream) {
     if (!f) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
-    if (!on_device) {
-        for (Bucket& b : f->bk) {
-            f->h_ints.resize((size_t)2 * b.count);
-            f->h_rows.resize(b.count);
-            int* hs = f->h_ints.data(), *hi = hs + b.count;
-            RC_TRY(cfnmpc_get_stats(b.s, hs, hi, f->h_rows.data(), 0, stream));
-            for (int r = 0; r < b.count; r++) {
-                if (status) status[b.idx[r]] = hs[r];
-                if (qp_iter) qp_iter[b.idx[r]] = hi[r];
-                if (res) res[b.idx[r]] = f->h_rows[r];
-            }
-        }
-        return CFNMPC_OK;
-    }
-    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) {
-        RC_TRY(staging(b));
-        RC_TRY(cfnmpc_get_stats(b.s, b.d_ints, b.d_ints + b.count, b.d_rows, 1, st));
-        if (status) rows<int, false>(b.d_ints, status, b.d_idx, b.count, 1, 1, st);
-        if (qp_iter) rows<int, false>(b.d_ints + b.count, qp_iter, b.d_idx, b.count, 1, 1, st);
-        if (res) rows<double, false>(b.d_rows, res, b.d_idx, b.count, 1, 1, st);
-        return (int)CFNMPC_OK;
-    });
+    return fleet_read(f, on_device, stream, {col(status, 1), col(qp_iter, 1), col(res, 1)},
+                      [](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_get_stats(b.s, p.i(0), p.i(1), p.d(2), mode, st); });
 }
 
 // Full SQP solve over the buckets: every bucket still running enqueues its iteration (step + check + read-back of its count of
@@ -433,7 +354,7 @@ int cfnmpc_fleet_get_stats(cfnmpc_fleet* f, int* status, int* qp_iter, double* r
 int cfnmpc_fleet_solve_sqp(cfnmpc_fleet* f, int max_iter, double tol_step, double tol_eq, double tol_ineq, int* n_iter, void* stream) {
     if (!f) return CFNMPC_EINVAL;
     for (Bucket& b : f->bk) RC_TRY(cfn::sqp_check_args(b.s, max_iter, tol_step, tol_eq, tol_ineq));   // nothing enqueued yet
-    FleetDevice fd(f);
+    cfn::DeviceGuard dg(f->device);
     hipStream_t user = (hipStream_t)stream;
     HIP_TRY(hipEventRecord(f->fork, user));
     std::vector<char> running(f->bk.size(), 1);
@@ -468,29 +389,8 @@ int cfnmpc_fleet_solve_sqp(cfnmpc_fleet* f, int max_iter, double tol_step, doubl
 
 int cfnmpc_fleet_get_sqp_stats(cfnmpc_fleet* f, int* status, int* sqp_iter, double* res, int on_device, void* stream) {
     if (!f) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
-    if (!on_device) {
-        for (Bucket& b : f->bk) {
-            f->h_ints.resize((size_t)2 * b.count);
-            f->h_rows.resize((size_t)3 * b.count);
-            int* hs = f->h_ints.data(), *hi = hs + b.count;
-            RC_TRY(cfn::sqp_get_stats(b.s, hs, hi, f->h_rows.data(), 0, stream));
-            for (int r = 0; r < b.count; r++) {
-                if (status) status[b.idx[r]] = hs[r];
-                if (sqp_iter) sqp_iter[b.idx[r]] = hi[r];
-                if (res) std::copy_n(f->h_rows.data() + (size_t)r * 3, 3, res + (long)b.idx[r] * 3);
-            }
-        }
-        return CFNMPC_OK;
-    }
-    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) {
-        RC_TRY(staging(b));
-        RC_TRY(cfn::sqp_get_stats(b.s, b.d_ints, b.d_ints + b.count, b.d_rows, 1, st));
-        if (status) rows<int, false>(b.d_ints, status, b.d_idx, b.count, 1, 1, st);
-        if (sqp_iter) rows<int, false>(b.d_ints + b.count, sqp_iter, b.d_idx, b.count, 1, 1, st);
-        if (res) rows<double, false>(b.d_rows, res, b.d_idx, b.count, 3, 3, st);
-        return (int)CFNMPC_OK;
-    });
+    return fleet_read(f, on_device, stream, {col(status, 1), col(sqp_iter, 1), col(res, 3)},
+                      [](Bucket& b, Staged p, int mode, void* st) { return cfn::sqp_get_stats(b.s, p.i(0), p.i(1), p.d(2), mode, st); });
 }
 
 int cfnmpc_fleet_set_sqp_globalization(cfnmpc_fleet* f, int mode, double eta, double reduction, double alpha_min) {
@@ -502,70 +402,26 @@ int cfnmpc_fleet_set_sqp_globalization(cfnmpc_fleet* f, int mode, double eta, do
 
 int cfnmpc_fleet_get_sqp_ls_stats(cfnmpc_fleet* f, double* alpha, double* mu, int* n_short, int* n_fail, int on_device, void* stream) {
     if (!f || (!alpha && !mu && !n_short && !n_fail)) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
-    if (!on_device) {
-        for (Bucket& b : f->bk) {
-            f->h_ints.resize((size_t)2 * b.count);
-            f->h_rows.resize((size_t)2 * b.count);
-            int* hs = f->h_ints.data(), *hf = hs + b.count;
-            double* ha = f->h_rows.data(), *hm = ha + b.count;
-            RC_TRY(cfn::sqp_get_ls_stats(b.s, ha, hm, hs, hf, 0, stream));
-            for (int r = 0; r < b.count; r++) {
-                if (alpha) alpha[b.idx[r]] = ha[r];
-                if (mu) mu[b.idx[r]] = hm[r];
-                if (n_short) n_short[b.idx[r]] = hs[r];
-                if (n_fail) n_fail[b.idx[r]] = hf[r];
-            }
-        }
-        return CFNMPC_OK;
-    }
-    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) {
-        RC_TRY(staging(b));
-        RC_TRY(cfn::sqp_get_ls_stats(b.s, b.d_rows, b.d_rows + b.count, b.d_ints, b.d_ints + b.count, 1, st));
-        if (alpha) rows<double, false>(b.d_rows, alpha, b.d_idx, b.count, 1, 1, st);
-        if (mu) rows<double, false>(b.d_rows + b.count, mu, b.d_idx, b.count, 1, 1, st);
-        if (n_short) rows<int, false>(b.d_ints, n_short, b.d_idx, b.count, 1, 1, st);
-        if (n_fail) rows<int, false>(b.d_ints + b.count, n_fail, b.d_idx, b.count, 1, 1, st);
-        return (int)CFNMPC_OK;
-    });
+    return fleet_read(f, on_device, stream, {col(alpha, 1), col(mu, 1), col(n_short, 1), col(n_fail, 1)},
+                      [](Bucket& b, Staged p, int mode, void* st) { return cfn::sqp_get_ls_stats(b.s, p.d(0), p.d(1), p.i(2), p.i(3), mode, st); });
 }
 
 // ---- NLP evaluation at every bucket's current iterate (include/cfnmpc.h: cfnmpc_eval_nlp) -------------
 int cfnmpc_fleet_eval_nlp(cfnmpc_fleet* f, void* stream) {
     if (!f) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
     return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) { return cfnmpc_eval_nlp(b.s, 0, st); });
 }
 
 // rows in the fleet's vehicle order: cost [B], res [B][3]
 int cfnmpc_fleet_get_nlp_stats(cfnmpc_fleet* f, double* cost, double* res, int on_device, void* stream) {
     if (!f || (!cost && !res)) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
-    if (on_device == CFNMPC_ON_HOST || on_device == CFNMPC_ON_HOST_ASYNC) {   // (host arrays: synchronous)
-        for (Bucket& b : f->bk) {
-            f->h_rows.resize((size_t)4 * b.count);
-            double* hc = f->h_rows.data(), *hr = hc + b.count;
-            RC_TRY(cfnmpc_get_nlp_stats(b.s, hc, hr, CFNMPC_ON_HOST, stream));
-            for (int r = 0; r < b.count; r++) {
-                if (cost) cost[b.idx[r]] = hc[r];
-                if (res) std::copy_n(hr + (size_t)r * 3, 3, res + (long)b.idx[r] * 3);
-            }
-        }
-        return CFNMPC_OK;
-    }
-    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) {
-        RC_TRY(staging(b));
-        RC_TRY(cfnmpc_get_nlp_stats(b.s, b.d_rows, b.d_rows + b.count, 1, st));
-        if (cost) rows<double, false>(b.d_rows, cost, b.d_idx, b.count, 1, 1, st);
-        if (res) rows<double, false>(b.d_rows + b.count, res, b.d_idx, b.count, 3, 3, st);
-        return (int)CFNMPC_OK;
-    });
+    return fleet_read(f, on_device, stream, {col(cost, 1), col(res, 3)},
+                      [](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_get_nlp_stats(b.s, p.d(0), p.d(1), mode, st); });
 }
 
 // ---- solution sensitivities with respect to x0 (include/cfnmpc.h: cfnmpc_eval_sens_x0) --------------
 int cfnmpc_fleet_eval_sens_x0(cfnmpc_fleet* f, double act_tol, void* stream) {
     if (!f) return CFNMPC_EINVAL;
-    FleetDevice fd(f);
     return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) { return cfnmpc_eval_sens_x0(b.s, act_tol, st); });
 }
 
@@ -575,38 +431,8 @@ int cfnmpc_fleet_get_sens_x0(cfnmpc_fleet* f, int stage, int n_stages, double* d
     if (!f || stage < 0 || n_stages < 1 || (!du && !dx) || (long)stage + n_stages > f->Nmin + 1 ||
         (du && stage + n_stages > f->Nmin))
         return CFNMPC_EINVAL;
-    FleetDevice fd(f);
-    const size_t wu = du ? (size_t)n_stages * 52 : 0, wx = dx ? (size_t)n_stages * 169 : 0;
-    if (on_device == CFNMPC_ON_HOST || on_device == CFNMPC_ON_HOST_ASYNC) {   // (host arrays: synchronous)
-        for (Bucket& b : f->bk) {
-            f->h_rows.resize((size_t)b.count * (wu + wx));
-            double* hu = du ? f->h_rows.data() : nullptr;
-            double* hx = dx ? f->h_rows.data() + (size_t)b.count * wu : nullptr;
-            RC_TRY(cfnmpc_get_sens_x0(b.s, stage, n_stages, hu, hx, CFNMPC_ON_HOST, stream));
-            for (int r = 0; r < b.count; r++) {
-                if (du) std::copy_n(hu + (size_t)r * wu, wu, du + (size_t)b.idx[r] * wu);
-                if (dx) std::copy_n(hx + (size_t)r * wx, wx, dx + (size_t)b.idx[r] * wx);
-            }
-        }
-        return CFNMPC_OK;
-    }
-    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) {
-        const size_t need = (size_t)b.count * (wu + wx);
-        if (b.n_sens < need) {
-            HIP_TRY(hipStreamSynchronize(st));   // (an earlier read may still use the old buffer)
-            if (b.d_sens) (void)hipFree(b.d_sens);
-            b.d_sens = nullptr;
-            b.n_sens = 0;
-            if (hipMalloc((void**)&b.d_sens, need * sizeof(double)) != hipSuccess) return (int)CFNMPC_ENOMEM;
-            b.n_sens = need;
-        }
-        double* su = du ? b.d_sens : nullptr;
-        double* sx = dx ? b.d_sens + (size_t)b.count * wu : nullptr;
-        RC_TRY(cfnmpc_get_sens_x0(b.s, stage, n_stages, su, sx, 1, st));
-        if (du) rows<double, false>(su, du, b.d_idx, b.count, (int)wu, (long)wu, st);
-        if (dx) rows<double, false>(sx, dx, b.d_idx, b.count, (int)wx, (long)wx, st);
-        return (int)CFNMPC_OK;
-    });
+    return fleet_read(f, on_device, stream, {col(du, (size_t)n_stages * 52), col(dx, (size_t)n_stages * 169)},
+                      [&](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_get_sens_x0(b.s, stage, n_stages, p.d(0), p.d(1), mode, st); });
 }
 
 }  // extern "C"

@@ -15,6 +15,9 @@
 // out over the shards so that sum N_i -- the cost model of a step -- is balanced (cfnmpc_shard_by_horizon below, SURVEY.md
 // section 8e "Partitioning"); a shard is then a cfnmpc_fleet (one solver per horizon bucket) over a NON-contiguous index set
 // and the host arrays of the whole fleet are gathered / scattered per shard.
+//
+// Every entry point names what it does on a shard twice, for its solver (uniform) and for its fleet (mixed); the shards are
+// walked, and the arrays moved, by for_shards and multi_io below.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,9 +25,16 @@
 #include <vector>
 
 #include "../../include/cfnmpc.h"
+#include "cfnmpc_host.hpp"
 #include "cfnmpc_model.hpp"
 
 namespace {
+using cfn::col;
+using cfn::col_stages;
+using cfn::Cols;
+using cfn::Layout;
+using cfn::Staged;
+
 struct Shard {
     int device = 0, lo = 0, hi = 0;
     cfnmpc_solver* s = nullptr;   // uniform horizon: vehicles [lo, hi)
@@ -33,23 +43,7 @@ struct Shard {
     int Nmax = 0;                 // longest horizon of this shard's fleet
     hipStream_t st = nullptr;
     std::vector<double> h;        // host staging in shard order (mixed)
-    std::vector<int> hi_;
 };
-struct Dev {   // current device for the duration of a call
-    int prev = -1;
-    explicit Dev(int d) { (void)hipGetDevice(&prev); if (prev != d) (void)hipSetDevice(d); else prev = -1; }
-    ~Dev() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-// mixed fleets: rows of the whole fleet's host array <-> a shard's staging in shard order (`len` of `fstride` elements per row)
-const double* to_shard(Shard& s, const double* src, size_t len, size_t fstride) {
-    s.h.resize(s.idx.size() * len);
-    for (size_t r = 0; r < s.idx.size(); r++) std::copy_n(src + (size_t)s.idx[r] * fstride, len, s.h.data() + r * len);
-    return s.h.data();
-}
-template <typename T>
-void from_shard(const Shard& s, const T* stage, T* dst, size_t len) {
-    for (size_t r = 0; r < s.idx.size(); r++) std::copy_n(stage + r * len, len, dst + (size_t)s.idx[r] * len);
-}
 }  // namespace
 
 struct cfnmpc_multi {
@@ -59,22 +53,70 @@ struct cfnmpc_multi {
     std::vector<Shard> sh;
 };
 
-#define RC_TRY(x) do { int rc_ = (x); if (rc_ != CFNMPC_OK) return rc_; } while (0)
 // for calls that ENQUEUE transfers on the shards' streams (CFNMPC_ON_HOST_ASYNC): on the first failing shard the earlier
 // shards' copies may still be reading / writing the caller's arrays -- wait for them before the error is returned
-#define RC_TRY_SYNC(m, x) do { int rc_ = (x); if (rc_ != CFNMPC_OK) { (void)sync_all(m); return rc_; } } while (0)
+#define RC_TRY_SYNC(m, x) do { int rc_ = (x); if (rc_ != CFNMPC_OK) { (void)cfnmpc_multi_sync(m); return rc_; } } while (0)
 
-extern "C" {
+namespace {
 
-int cfnmpc_multi_create(cfnmpc_multi** out, int n_shards, const int* device_ids, int total_batch, const cfnmpc_opts* opts) {
+// what both creators check first
+int check_shards(cfnmpc_multi** out, int n_shards, const int* device_ids, int total_batch) {
     if (!out || n_shards < 1 || !device_ids || total_batch < n_shards) return CFNMPC_EINVAL;
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return CFNMPC_EHIP;
     for (int i = 0; i < n_shards; i++) if (device_ids[i] < 0 || device_ids[i] >= ndev) return CFNMPC_EINVAL;
-    if (opts && opts->struct_size != (int)sizeof(cfnmpc_opts)) return CFNMPC_EINVAL;   // ABI guard (include/cfnmpc.h)
+    return CFNMPC_OK;
+}
+
+// on_solver(shard) on every shard of a uniform fleet, on_fleet(shard) on every shard of a mixed one; `wait`: for all the
+// shards' streams afterwards (also behind a failure)
+template <typename FS, typename FF>
+int for_shards(cfnmpc_multi* m, FS on_solver, FF on_fleet, bool wait = false) {
+    int rc = CFNMPC_OK;
+    for (Shard& s : m->sh) {
+        rc = m->mixed ? on_fleet(s) : on_solver(s);
+        if (rc != CFNMPC_OK) break;
+    }
+    if (!wait) return rc;
+    const int rs = cfnmpc_multi_sync(m);
+    return rc != CFNMPC_OK ? rc : rs;
+}
+
+// Host arrays of the whole fleet.  Uniform shards are contiguous: every column is handed over in place, from row `lo` on, and
+// every shard's transfer (+ layout kernel) is ENQUEUED on its own stream first (CFNMPC_ON_HOST_ASYNC), then the shards are
+// waited for -- the copies of different GPUs overlap instead of running one after the other.  Mixed shards stage their rows in
+// shard order; the shard's fleet call is synchronous and waits for that shard only (the other shards keep working meanwhile).
+// WRITE: the rows are gathered before the call, else scattered after it.
+template <bool WRITE, typename FS, typename FF>
+int multi_io(cfnmpc_multi* m, Cols cols, FS on_solver, FF on_fleet) {
+    for (Shard& s : m->sh) {
+        if (!m->mixed) {
+            const Layout L(cols, s.hi - s.lo, m->N, m->N);
+            RC_TRY_SYNC(m, on_solver(s, cfn::in_place(L, s.lo), (int)CFNMPC_ON_HOST_ASYNC));
+            continue;
+        }
+        const Layout L(cols, s.idx.size(), s.Nmax, m->N);
+        s.h.resize((L.bytes + 7) / 8);
+        if (WRITE) cfn::move_rows<true>(L, s.h.data(), s.idx.data(), s.idx.size());
+        RC_TRY_SYNC(m, on_fleet(s, cfn::staged(L, s.h.data()), (int)CFNMPC_ON_HOST));
+        if (!WRITE) cfn::move_rows<false>(L, s.h.data(), s.idx.data(), s.idx.size());
+    }
+    return m->mixed ? (int)CFNMPC_OK : cfnmpc_multi_sync(m);
+}
+template <typename FS, typename FF>
+int multi_write(cfnmpc_multi* m, Cols cols, FS on_solver, FF on_fleet) { return multi_io<true>(m, cols, on_solver, on_fleet); }
+template <typename FS, typename FF>
+int multi_read(cfnmpc_multi* m, Cols cols, FS on_solver, FF on_fleet) { return multi_io<false>(m, cols, on_solver, on_fleet); }
+
+}  // namespace
+
+extern "C" {
+
+int cfnmpc_multi_create(cfnmpc_multi** out, int n_shards, const int* device_ids, int total_batch, const cfnmpc_opts* opts) {
+    RC_TRY(check_shards(out, n_shards, device_ids, total_batch));
     cfnmpc_opts o;
-    if (opts) o = *opts; else cfnmpc_default_opts(&o);
+    RC_TRY(cfn::take_opts(opts, &o));
     cfnmpc_multi* m = new cfnmpc_multi;
     m->B = total_batch;
     m->N = o.N;
@@ -86,7 +128,7 @@ int cfnmpc_multi_create(cfnmpc_multi** out, int n_shards, const int* device_ids,
         s.lo = lo;
         s.hi = lo + base + (i < rem ? 1 : 0);
         lo = s.hi;
-        Dev d(s.device);
+        cfn::DeviceGuard d(s.device);
         rc = cfnmpc_create(&s.s, s.hi - s.lo, &o);
         if (rc == CFNMPC_OK && hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking) != hipSuccess) rc = CFNMPC_EHIP;
         m->sh.push_back(s);
@@ -116,16 +158,12 @@ int cfnmpc_shard_by_horizon(int batch, const int* N_per_instance, int n_shards, 
 
 int cfnmpc_multi_create_horizons(cfnmpc_multi** out, int n_shards, const int* device_ids, int total_batch, const int* N_per_instance,
                                  const cfnmpc_opts* opts) {
-    if (!out || n_shards < 1 || !device_ids || total_batch < n_shards || !N_per_instance) return CFNMPC_EINVAL;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return CFNMPC_EHIP;
-    for (int i = 0; i < n_shards; i++) if (device_ids[i] < 0 || device_ids[i] >= ndev) return CFNMPC_EINVAL;
+    if (!N_per_instance) return CFNMPC_EINVAL;
+    RC_TRY(check_shards(out, n_shards, device_ids, total_batch));
     std::vector<int> of(total_batch);
     RC_TRY(cfnmpc_shard_by_horizon(total_batch, N_per_instance, n_shards, of.data()));
-    if (opts && opts->struct_size != (int)sizeof(cfnmpc_opts)) return CFNMPC_EINVAL;   // ABI guard (include/cfnmpc.h)
     cfnmpc_opts o;
-    if (opts) o = *opts; else cfnmpc_default_opts(&o);
+    RC_TRY(cfn::take_opts(opts, &o));
     cfnmpc_multi* m = new cfnmpc_multi;
     m->B = total_batch;
     m->mixed = true;
@@ -142,7 +180,7 @@ int cfnmpc_multi_create_horizons(cfnmpc_multi** out, int n_shards, const int* de
         hz.resize(s.idx.size());
         for (size_t r = 0; r < s.idx.size(); r++) hz[r] = N_per_instance[s.idx[r]];
         s.Nmax = *std::max_element(hz.begin(), hz.end());
-        Dev d(s.device);
+        cfn::DeviceGuard d(s.device);
         rc = cfnmpc_fleet_create(&s.f, (int)hz.size(), hz.data(), &o);
         if (rc == CFNMPC_OK && hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking) != hipSuccess) rc = CFNMPC_EHIP;
     }
@@ -165,7 +203,7 @@ int cfnmpc_multi_shard_fleet(const cfnmpc_multi* m, int shard, cfnmpc_fleet** fl
 int cfnmpc_multi_free(cfnmpc_multi* m) {
     if (!m) return CFNMPC_EINVAL;
     for (Shard& s : m->sh) {
-        Dev d(s.device);
+        cfn::DeviceGuard d(s.device);
         if (s.st) { (void)hipStreamSynchronize(s.st); (void)hipStreamDestroy(s.st); }
         if (s.s) cfnmpc_free(s.s);
         if (s.f) cfnmpc_fleet_free(s.f);
@@ -188,12 +226,10 @@ int cfnmpc_multi_shard(const cfnmpc_multi* m, int shard, cfnmpc_solver** solver,
     return CFNMPC_OK;
 }
 
-// Host-array I/O of the whole fleet: every shard's transfer (+ layout kernel) is ENQUEUED on its own stream first
-// (CFNMPC_ON_HOST_ASYNC), then the shards are waited for -- the copies of different GPUs overlap instead of
-// running one after the other.
-static int sync_all(cfnmpc_multi* m) {
+int cfnmpc_multi_sync(cfnmpc_multi* m) {
+    if (!m) return CFNMPC_EINVAL;
     for (Shard& s : m->sh) {
-        Dev d(s.device);
+        cfn::DeviceGuard d(s.device);
         if (hipStreamSynchronize(s.st) != hipSuccess) return CFNMPC_EHIP;
     }
     return CFNMPC_OK;
@@ -201,247 +237,138 @@ static int sync_all(cfnmpc_multi* m) {
 
 int cfnmpc_multi_set_x0(cfnmpc_multi* m, const double* x0) {
     if (!m || !x0) return CFNMPC_EINVAL;
-    if (m->mixed) {
-        for (Shard& s : m->sh) RC_TRY(cfnmpc_fleet_set_x0(s.f, to_shard(s, x0, 13, 13), CFNMPC_ON_HOST, s.st));
-        return CFNMPC_OK;
-    }
-    for (Shard& s : m->sh) RC_TRY_SYNC(m, cfnmpc_set_x0(s.s, x0 + (size_t)s.lo * 13, CFNMPC_ON_HOST_ASYNC, s.st));
-    return sync_all(m);
+    return multi_write(m, {col(x0, 13)},
+                       [](Shard& s, Staged p, int mode) { return cfnmpc_set_x0(s.s, p.d(0), mode, s.st); },
+                       [](Shard& s, Staged p, int mode) { return cfnmpc_fleet_set_x0(s.f, p.d(0), mode, s.st); });
 }
 
+// yref [B][N][17] of the whole fleet (N: the longest horizon; a mixed shard's fleet reads the first Nmax_shard rows of each
+// vehicle).  (Uniform: two arrays through ONE staging buffer per shard: the second put is ordered behind the first on the
+// shard's stream.)
 int cfnmpc_multi_set_yref(cfnmpc_multi* m, const double* yref, const double* yref_e) {
     if (!m || !yref || !yref_e) return CFNMPC_EINVAL;
-    if (m->mixed) {   // yref [B][Nmax][17] of the whole fleet; a shard's fleet reads the first Nmax_shard rows of each vehicle
-        std::vector<double> ye;
-        for (Shard& s : m->sh) {
-            ye.resize(s.idx.size() * 13);
-            for (size_t r = 0; r < s.idx.size(); r++) std::copy_n(yref_e + (size_t)s.idx[r] * 13, 13, ye.data() + r * 13);
-            RC_TRY(cfnmpc_fleet_set_yref(s.f, to_shard(s, yref, (size_t)s.Nmax * 17, (size_t)m->N * 17), ye.data(), CFNMPC_ON_HOST, s.st));
-        }
-        return CFNMPC_OK;
-    }
-    // (two arrays through ONE staging buffer per shard: the second put is ordered behind the first on the shard's stream)
-    for (Shard& s : m->sh)
-        RC_TRY_SYNC(m, cfnmpc_set_yref(s.s, yref + (size_t)s.lo * m->N * 17, yref_e + (size_t)s.lo * 13, CFNMPC_ON_HOST_ASYNC, s.st));
-    return sync_all(m);
+    return multi_write(m, {col_stages(yref, 17), col(yref_e, 13)},
+                       [](Shard& s, Staged p, int mode) { return cfnmpc_set_yref(s.s, p.d(0), p.d(1), mode, s.st); },
+                       [](Shard& s, Staged p, int mode) { return cfnmpc_fleet_set_yref(s.f, p.d(0), p.d(1), mode, s.st); });
 }
 
 int cfnmpc_multi_set_box(cfnmpc_multi* m, double u_min, double u_max) {
     if (!m) return CFNMPC_EINVAL;
-    if (m->mixed) {
-        for (Shard& s : m->sh) RC_TRY(cfnmpc_fleet_set_box(s.f, u_min, u_max));
-        return CFNMPC_OK;
-    }
-    for (Shard& s : m->sh) RC_TRY(cfnmpc_set_box(s.s, u_min, u_max));
-    return CFNMPC_OK;
+    return for_shards(m, [&](Shard& s) { return cfnmpc_set_box(s.s, u_min, u_max); },
+                      [&](Shard& s) { return cfnmpc_fleet_set_box(s.f, u_min, u_max); });
 }
 
+// [B][N][4] of the whole fleet; NULL, NULL: back to the scalar box
 int cfnmpc_multi_set_box_stages(cfnmpc_multi* m, const double* lb, const double* ub) {
     if (!m || ((lb == nullptr) != (ub == nullptr))) return CFNMPC_EINVAL;
-    if (m->mixed) {   // [B][Nmax][4] of the whole fleet
-        std::vector<double> hu;
-        for (Shard& s : m->sh) {
-            if (!lb) { RC_TRY(cfnmpc_fleet_set_box_stages(s.f, nullptr, nullptr)); continue; }
-            const size_t len = (size_t)s.Nmax * 4, fs = (size_t)m->N * 4;
-            hu.resize(s.idx.size() * len);
-            for (size_t r = 0; r < s.idx.size(); r++) std::copy_n(ub + (size_t)s.idx[r] * fs, len, hu.data() + r * len);
-            RC_TRY(cfnmpc_fleet_set_box_stages(s.f, to_shard(s, lb, len, fs), hu.data()));
-        }
-        return CFNMPC_OK;
-    }
-    for (Shard& s : m->sh) {
-        const size_t off = (size_t)s.lo * m->N * 4;
-        RC_TRY_SYNC(m, cfnmpc_set_box_stages(s.s, lb ? lb + off : nullptr, ub ? ub + off : nullptr, CFNMPC_ON_HOST_ASYNC, s.st));
-    }
-    return sync_all(m);
+    return multi_write(m, {col_stages(lb, 4), col_stages(ub, 4)},
+                       [](Shard& s, Staged p, int mode) { return cfnmpc_set_box_stages(s.s, p.d(0), p.d(1), mode, s.st); },
+                       [](Shard& s, Staged p, int) { return cfnmpc_fleet_set_box_stages(s.f, p.d(0), p.d(1)); });
 }
 
 int cfnmpc_multi_set_weights(cfnmpc_multi* m, const double* W, const double* WN) {
     if (!m) return CFNMPC_EINVAL;
-    for (Shard& s : m->sh) RC_TRY(m->mixed ? cfnmpc_fleet_set_weights(s.f, W, WN) : cfnmpc_set_weights(s.s, W, WN));
-    return CFNMPC_OK;
+    return for_shards(m, [&](Shard& s) { return cfnmpc_set_weights(s.s, W, WN); },
+                      [&](Shard& s) { return cfnmpc_fleet_set_weights(s.f, W, WN); });
 }
 
 int cfnmpc_multi_set_erk_steps(cfnmpc_multi* m, int num_steps) {
     if (!m) return CFNMPC_EINVAL;
-    for (Shard& s : m->sh) RC_TRY(m->mixed ? cfnmpc_fleet_set_erk_steps(s.f, num_steps) : cfnmpc_set_erk_steps(s.s, num_steps));
-    return CFNMPC_OK;
+    return for_shards(m, [&](Shard& s) { return cfnmpc_set_erk_steps(s.s, num_steps); },
+                      [&](Shard& s) { return cfnmpc_fleet_set_erk_steps(s.f, num_steps); });
 }
 
 int cfnmpc_multi_set_cost_scaling(cfnmpc_multi* m, double stage_scale, double terminal_scale) {
     if (!m) return CFNMPC_EINVAL;
-    for (Shard& s : m->sh)
-        RC_TRY(m->mixed ? cfnmpc_fleet_set_cost_scaling(s.f, stage_scale, terminal_scale) : cfnmpc_set_cost_scaling(s.s, stage_scale, terminal_scale));
-    return CFNMPC_OK;
+    return for_shards(m, [&](Shard& s) { return cfnmpc_set_cost_scaling(s.s, stage_scale, terminal_scale); },
+                      [&](Shard& s) { return cfnmpc_fleet_set_cost_scaling(s.f, stage_scale, terminal_scale); });
 }
 
 int cfnmpc_multi_set_model_params(cfnmpc_multi* m, const double* p) {
     if (!m) return CFNMPC_EINVAL;
     if (p && !cfn::model_params_ok(p, (size_t)m->B * CFNMPC_NP)) return CFNMPC_EINVAL;   // (as a whole: no shard changes)
-    for (Shard& s : m->sh) {
-        if (m->mixed) RC_TRY(cfnmpc_fleet_set_model_params(s.f, p ? to_shard(s, p, CFNMPC_NP, CFNMPC_NP) : nullptr));
-        else RC_TRY(cfnmpc_set_model_params(s.s, p ? p + (size_t)s.lo * CFNMPC_NP : nullptr, CFNMPC_ON_HOST, s.st));
-    }
-    return CFNMPC_OK;
+    return multi_write(m, {col(p, CFNMPC_NP)},
+                       [](Shard& s, Staged q, int mode) { return cfnmpc_set_model_params(s.s, q.d(0), mode, s.st); },
+                       [](Shard& s, Staged q, int) { return cfnmpc_fleet_set_model_params(s.f, q.d(0)); });
 }
 
 int cfnmpc_multi_set_weights_batch(cfnmpc_multi* m, const double* W, const double* WN) {
     if (!m) return CFNMPC_EINVAL;
     if (!cfn::weight_rows_ok(W, WN, (size_t)m->B)) return CFNMPC_EINVAL;   // (as a whole: no shard changes)
-    std::vector<double> hn;
-    for (Shard& s : m->sh) {
-        if (m->mixed) {
-            if (WN) {   // (to_shard's staging buffer holds W)
-                hn.resize(s.idx.size() * 13);
-                for (size_t r = 0; r < s.idx.size(); r++) std::copy_n(WN + (size_t)s.idx[r] * 13, 13, hn.data() + r * 13);
-            }
-            RC_TRY(cfnmpc_fleet_set_weights_batch(s.f, W ? to_shard(s, W, 17, 17) : nullptr, WN ? hn.data() : nullptr));
-        } else {
-            RC_TRY(cfnmpc_set_weights_batch(s.s, W ? W + (size_t)s.lo * 17 : nullptr, WN ? WN + (size_t)s.lo * 13 : nullptr,
-                                            CFNMPC_ON_HOST, s.st));
-        }
-    }
-    return CFNMPC_OK;
+    return multi_write(m, {col(W, 17), col(WN, 13)},
+                       [](Shard& s, Staged p, int mode) { return cfnmpc_set_weights_batch(s.s, p.d(0), p.d(1), mode, s.st); },
+                       [](Shard& s, Staged p, int) { return cfnmpc_fleet_set_weights_batch(s.f, p.d(0), p.d(1)); });
 }
 
 int cfnmpc_multi_init_iterate(cfnmpc_multi* m, int mode) {
     if (!m) return CFNMPC_EINVAL;
-    for (Shard& s : m->sh) RC_TRY(m->mixed ? cfnmpc_fleet_init_iterate(s.f, mode, s.st) : cfnmpc_init_iterate(s.s, mode, s.st));
-    return CFNMPC_OK;
+    return for_shards(m, [&](Shard& s) { return cfnmpc_init_iterate(s.s, mode, s.st); },
+                      [&](Shard& s) { return cfnmpc_fleet_init_iterate(s.f, mode, s.st); });
 }
 
+// asynchronous: every device gets its work before anyone waits
 int cfnmpc_multi_solve(cfnmpc_multi* m, int n_rti) {
     if (!m || n_rti < 1) return CFNMPC_EINVAL;
-    for (Shard& s : m->sh) RC_TRY(m->mixed ? cfnmpc_fleet_solve(s.f, n_rti, s.st) : cfnmpc_solve(s.s, n_rti, s.st));   // asynchronous: every device gets its work before anyone waits
-    return CFNMPC_OK;
-}
-
-int cfnmpc_multi_sync(cfnmpc_multi* m) {
-    if (!m) return CFNMPC_EINVAL;
-    for (Shard& s : m->sh) {
-        Dev d(s.device);
-        if (hipStreamSynchronize(s.st) != hipSuccess) return CFNMPC_EHIP;
-    }
-    return CFNMPC_OK;
+    return for_shards(m, [&](Shard& s) { return cfnmpc_solve(s.s, n_rti, s.st); },
+                      [&](Shard& s) { return cfnmpc_fleet_solve(s.f, n_rti, s.st); });
 }
 
 int cfnmpc_multi_get_u(cfnmpc_multi* m, int stage, double* u) {
-    if (!m || !u) return CFNMPC_EINVAL;
-    if (m->mixed) {   // (a shard's host getter waits for that shard only; the other shards keep working meanwhile)
-        if (stage < 0 || stage >= m->Nmin) return CFNMPC_EINVAL;
-        for (Shard& s : m->sh) {
-            s.h.resize(s.idx.size() * 4);
-            RC_TRY(cfnmpc_fleet_get_u(s.f, stage, s.h.data(), CFNMPC_ON_HOST, s.st));
-            from_shard(s, s.h.data(), u, 4);
-        }
-        return CFNMPC_OK;
-    }
-    for (Shard& s : m->sh) RC_TRY_SYNC(m, cfnmpc_get_u(s.s, stage, u + (size_t)s.lo * 4, CFNMPC_ON_HOST_ASYNC, s.st));
-    return sync_all(m);
+    if (!m || !u || (m->mixed && (stage < 0 || stage >= m->Nmin))) return CFNMPC_EINVAL;
+    return multi_read(m, {col(u, 4)},
+                      [&](Shard& s, Staged p, int mode) { return cfnmpc_get_u(s.s, stage, p.d(0), mode, s.st); },
+                      [&](Shard& s, Staged p, int mode) { return cfnmpc_fleet_get_u(s.f, stage, p.d(0), mode, s.st); });
 }
 
 int cfnmpc_multi_get_x(cfnmpc_multi* m, int stage, double* x) {
-    if (!m || !x) return CFNMPC_EINVAL;
-    if (m->mixed) {
-        if (stage < 0 || stage > m->Nmin) return CFNMPC_EINVAL;
-        for (Shard& s : m->sh) {
-            s.h.resize(s.idx.size() * 13);
-            RC_TRY(cfnmpc_fleet_get_x(s.f, stage, s.h.data(), CFNMPC_ON_HOST, s.st));
-            from_shard(s, s.h.data(), x, 13);
-        }
-        return CFNMPC_OK;
-    }
-    for (Shard& s : m->sh) RC_TRY_SYNC(m, cfnmpc_get_x(s.s, stage, x + (size_t)s.lo * 13, CFNMPC_ON_HOST_ASYNC, s.st));
-    return sync_all(m);
+    if (!m || !x || (m->mixed && (stage < 0 || stage > m->Nmin))) return CFNMPC_EINVAL;
+    return multi_read(m, {col(x, 13)},
+                      [&](Shard& s, Staged p, int mode) { return cfnmpc_get_x(s.s, stage, p.d(0), mode, s.st); },
+                      [&](Shard& s, Staged p, int mode) { return cfnmpc_fleet_get_x(s.f, stage, p.d(0), mode, s.st); });
 }
 
 int cfnmpc_multi_get_cmd(cfnmpc_multi* m, double* cmd_vel, int* motvel) {
     if (!m || !cmd_vel) return CFNMPC_EINVAL;
-    if (m->mixed) {
-        for (Shard& s : m->sh) {
-            s.h.resize(s.idx.size() * 4); s.hi_.resize(s.idx.size() * 4);
-            RC_TRY(cfnmpc_fleet_get_cmd(s.f, s.h.data(), motvel ? s.hi_.data() : nullptr, CFNMPC_ON_HOST, s.st));
-            from_shard(s, s.h.data(), cmd_vel, 4);
-            if (motvel) from_shard(s, s.hi_.data(), motvel, 4);
-        }
-        return CFNMPC_OK;
-    }
-    for (Shard& s : m->sh)
-        RC_TRY_SYNC(m, cfnmpc_get_cmd(s.s, cmd_vel + (size_t)s.lo * 4, motvel ? motvel + (size_t)s.lo * 4 : nullptr, CFNMPC_ON_HOST_ASYNC, s.st));
-    return sync_all(m);
+    return multi_read(m, {col(cmd_vel, 4), col(motvel, 4)},
+                      [](Shard& s, Staged p, int mode) { return cfnmpc_get_cmd(s.s, p.d(0), p.i(1), mode, s.st); },
+                      [](Shard& s, Staged p, int mode) { return cfnmpc_fleet_get_cmd(s.f, p.d(0), p.i(1), mode, s.st); });
 }
 
 int cfnmpc_multi_get_stats(cfnmpc_multi* m, int* status, int* qp_iter, double* res) {
     if (!m) return CFNMPC_EINVAL;
-    if (m->mixed) {
-        for (Shard& s : m->sh) {
-            const size_t n = s.idx.size();
-            s.h.resize(n); s.hi_.resize(2 * n);
-            RC_TRY(cfnmpc_fleet_get_stats(s.f, s.hi_.data(), s.hi_.data() + n, s.h.data(), CFNMPC_ON_HOST, s.st));
-            if (status) from_shard(s, s.hi_.data(), status, 1);
-            if (qp_iter) from_shard(s, s.hi_.data() + n, qp_iter, 1);
-            if (res) from_shard(s, s.h.data(), res, 1);
-        }
-        return CFNMPC_OK;
-    }
-    for (Shard& s : m->sh)
-        RC_TRY_SYNC(m, cfnmpc_get_stats(s.s, status ? status + s.lo : nullptr, qp_iter ? qp_iter + s.lo : nullptr, res ? res + s.lo : nullptr,
-                                CFNMPC_ON_HOST_ASYNC, s.st));
-    return sync_all(m);
+    return multi_read(m, {col(status, 1), col(qp_iter, 1), col(res, 1)},
+                      [](Shard& s, Staged p, int mode) { return cfnmpc_get_stats(s.s, p.i(0), p.i(1), p.d(2), mode, s.st); },
+                      [](Shard& s, Staged p, int mode) { return cfnmpc_fleet_get_stats(s.f, p.i(0), p.i(1), p.d(2), mode, s.st); });
 }
 
 // ---- NLP evaluation over the whole fleet (cfnmpc_eval_nlp per shard; host arrays in the caller's order, synchronous) ----------
 int cfnmpc_multi_eval_nlp(cfnmpc_multi* m) {
     if (!m) return CFNMPC_EINVAL;
-    for (Shard& s : m->sh) RC_TRY_SYNC(m, m->mixed ? cfnmpc_fleet_eval_nlp(s.f, s.st) : cfnmpc_eval_nlp(s.s, 0, s.st));
-    return sync_all(m);
+    return for_shards(m, [](Shard& s) { return cfnmpc_eval_nlp(s.s, 0, s.st); },
+                      [](Shard& s) { return cfnmpc_fleet_eval_nlp(s.f, s.st); }, true);
 }
 
 int cfnmpc_multi_get_nlp_stats(cfnmpc_multi* m, double* cost, double* res) {
     if (!m || (!cost && !res)) return CFNMPC_EINVAL;
-    if (m->mixed) {
-        for (Shard& s : m->sh) {
-            const size_t n = s.idx.size();
-            s.h.resize(4 * n);
-            RC_TRY(cfnmpc_fleet_get_nlp_stats(s.f, s.h.data(), s.h.data() + n, CFNMPC_ON_HOST, s.st));
-            if (cost) from_shard(s, s.h.data(), cost, 1);
-            if (res) from_shard(s, s.h.data() + n, res, 3);
-        }
-        return CFNMPC_OK;
-    }
-    for (Shard& s : m->sh)
-        RC_TRY_SYNC(m, cfnmpc_get_nlp_stats(s.s, cost ? cost + s.lo : nullptr, res ? res + (size_t)s.lo * 3 : nullptr, CFNMPC_ON_HOST_ASYNC, s.st));
-    return sync_all(m);
+    return multi_read(m, {col(cost, 1), col(res, 3)},
+                      [](Shard& s, Staged p, int mode) { return cfnmpc_get_nlp_stats(s.s, p.d(0), p.d(1), mode, s.st); },
+                      [](Shard& s, Staged p, int mode) { return cfnmpc_fleet_get_nlp_stats(s.f, p.d(0), p.d(1), mode, s.st); });
 }
 
 // ---- solution sensitivities with respect to x0 (host arrays over the whole fleet, caller's order; synchronous) ---------------
 int cfnmpc_multi_eval_sens_x0(cfnmpc_multi* m, double act_tol) {
     if (!m) return CFNMPC_EINVAL;
-    for (Shard& s : m->sh) RC_TRY_SYNC(m, m->mixed ? cfnmpc_fleet_eval_sens_x0(s.f, act_tol, s.st) : cfnmpc_eval_sens_x0(s.s, act_tol, s.st));
-    return sync_all(m);
+    return for_shards(m, [&](Shard& s) { return cfnmpc_eval_sens_x0(s.s, act_tol, s.st); },
+                      [&](Shard& s) { return cfnmpc_fleet_eval_sens_x0(s.f, act_tol, s.st); }, true);
 }
 
 int cfnmpc_multi_get_sens_x0(cfnmpc_multi* m, int stage, int n_stages, double* du, double* dx) {
     const int Nlim = m ? (m->mixed ? m->Nmin : m->N) : 0;
     if (!m || stage < 0 || n_stages < 1 || (!du && !dx) || (long)stage + n_stages > Nlim + 1 || (du && stage + n_stages > Nlim))
         return CFNMPC_EINVAL;
-    const size_t wu = du ? (size_t)n_stages * 52 : 0, wx = dx ? (size_t)n_stages * 169 : 0;
-    if (m->mixed) {
-        for (Shard& s : m->sh) {
-            const size_t n = s.idx.size();
-            s.h.resize(n * (wu + wx));
-            double* hu = du ? s.h.data() : nullptr;
-            double* hx = dx ? s.h.data() + n * wu : nullptr;
-            RC_TRY(cfnmpc_fleet_get_sens_x0(s.f, stage, n_stages, hu, hx, CFNMPC_ON_HOST, s.st));
-            if (du) from_shard(s, hu, du, wu);
-            if (dx) from_shard(s, hx, dx, wx);
-        }
-        return CFNMPC_OK;
-    }
-    for (Shard& s : m->sh)
-        RC_TRY_SYNC(m, cfnmpc_get_sens_x0(s.s, stage, n_stages, du ? du + (size_t)s.lo * wu : nullptr, dx ? dx + (size_t)s.lo * wx : nullptr,
-                                          CFNMPC_ON_HOST_ASYNC, s.st));
-    return sync_all(m);
+    return multi_read(m, {col(du, (size_t)n_stages * 52), col(dx, (size_t)n_stages * 169)},
+                      [&](Shard& s, Staged p, int mode) { return cfnmpc_get_sens_x0(s.s, stage, n_stages, p.d(0), p.d(1), mode, s.st); },
+                      [&](Shard& s, Staged p, int mode) { return cfnmpc_fleet_get_sens_x0(s.f, stage, n_stages, p.d(0), p.d(1), mode, s.st); });
 }
 
 }  // extern "C"

@@ -15,7 +15,8 @@
  *       yref   : [B][N][17], yref_e : [B][13]                        (acados_mpc.cpp:584-594)
  *   - `on_device`: 0 (CFNMPC_ON_HOST) host memory, copied synchronously; 2 (CFNMPC_ON_HOST_ASYNC) host memory,
  *     transfer only enqueued on `stream`; any other value: device memory of the solver's GPU (no copy through
- *     the host);
+ *     the host).  A fleet (cfnmpc_fleet_*) takes the value 2 as host memory too but completes the transfer before it
+ *     returns, as with 0;
  *   - every call returns 0 on success, a negative CFNMPC_E* code otherwise; solver *status*
  *     per instance follows acados: 0 success, 2 max. iterations, 4 QP failure.
  *   - a solver (or fleet) lives on the HIP device that is current when it is created; later calls
