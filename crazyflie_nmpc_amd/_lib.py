@@ -28,6 +28,8 @@ SYMBOLS = [
     "cfnmpc_fleet_set_cost_scaling", "cfnmpc_multi_set_erk_steps", "cfnmpc_multi_set_cost_scaling",
     "cfnmpc_set_model_params", "cfnmpc_get_model_params", "cfnmpc_fleet_set_model_params", "cfnmpc_multi_set_model_params",
     "cfnmpc_sim_params",
+    "cfnmpc_set_disturbance", "cfnmpc_get_disturbance", "cfnmpc_sim_dist", "cfnmpc_estimate_disturbance",
+    "cfnmpc_fleet_set_disturbance", "cfnmpc_fleet_get_disturbance", "cfnmpc_multi_set_disturbance",
     "cfnmpc_set_weights_batch", "cfnmpc_get_weights_batch", "cfnmpc_fleet_set_weights_batch", "cfnmpc_multi_set_weights_batch",
     "cfnmpc_eval_sens_x0", "cfnmpc_get_sens_x0", "cfnmpc_get_sens_active", "cfnmpc_fleet_eval_sens_x0", "cfnmpc_fleet_get_sens_x0",
     "cfnmpc_multi_eval_sens_x0", "cfnmpc_multi_get_sens_x0",
@@ -145,6 +147,13 @@ def lib():
     L.cfnmpc_fleet_set_weights_batch.argtypes = [vp, vp, vp]
     L.cfnmpc_multi_set_weights_batch.argtypes = [vp, vp, vp]
     L.cfnmpc_sim_params.argtypes = [i32, vp, vp, vp, dbl, i32, vp, i32, vp]
+    L.cfnmpc_set_disturbance.argtypes = [vp, vp, i32, vp]
+    L.cfnmpc_get_disturbance.argtypes = [vp, vp, i32, vp]
+    L.cfnmpc_sim_dist.argtypes = [i32, vp, vp, vp, vp, dbl, i32, vp, i32, vp]
+    L.cfnmpc_estimate_disturbance.argtypes = [i32, vp, vp, vp, vp, vp, dbl, i32, dbl, dbl, i32, vp]
+    L.cfnmpc_fleet_set_disturbance.argtypes = [vp, vp, i32, vp]
+    L.cfnmpc_fleet_get_disturbance.argtypes = [vp, vp, i32, vp]
+    L.cfnmpc_multi_set_disturbance.argtypes = [vp, vp]
     for name, at in (("cfnmpc_debug_chunked_pair", [vp, i32, i32, vp, vp]), ("cfnmpc_debug_checksum", [vp, vp]),
                      ("cfnmpc_debug_solve_part", [vp, i32, i32, vp])):   # development builds only (make DEV=1, csrc/cfnmpc_dev.h)
         if hasattr(L, name):

@@ -77,6 +77,9 @@ struct cfnmpc_solver {
     // device block of derived constants P.mpar points to while set (allocated at the first call, kept for later ones)
     std::vector<double> mp_rows;
     double* mpar_buf;
+    // per-instance disturbance rows (cfnmpc_set_disturbance): the device table P.dist points to while set (allocated at the first
+    // call, kept for later ones).  While set, P.mpar is set too: the caller's rows, or the nominal ones if there are none
+    double* dist_buf;
     // per-instance cost weights (cfnmpc_set_weights_batch): the caller's unscaled rows [B][17] / [B][13] while set (empty: the
     // uniform W_set / WN_set) and the device table P.wtab points to while set (allocated at the first call, kept for later ones)
     std::vector<double> w_rows, wn_rows;
@@ -723,12 +726,33 @@ int cfnmpc_set_erk_steps(cfnmpc_solver* s, int num_steps) {
 int cfnmpc_erk_steps(const cfnmpc_solver* s) { return s ? s->P.erk_steps : CFNMPC_EINVAL; }
 
 static_assert(CFNMPC_NP == cfn::NPAR, "parameter row");
+static_assert(CFNMPC_ND == cfn::ND, "disturbance row");
+// the table of derived constants (s->mpar_buf, allocated here at first use) from the rows [B][NPAR], NULL = nominal rows:
+// [NK][S] structure-of-arrays over every workspace row (padding rows and the spare block: nominal).  In place, in stream order,
+// complete on return: a captured step graph (which holds the pointer) replays with the new values
+static int upload_mpar(cfnmpc_solver* s, const double* rows, hipStream_t st) {
+    const cfn::Params& P = s->P;
+    const size_t B = P.B, S = ((size_t)P.NW + 1) * 4;
+    std::vector<double> k((size_t)cfn::NK * S);
+    for (size_t i = 0; i < S; i++) {
+        double ki[cfn::NK];
+        cfn::derive_k(rows && i < B ? rows + i * cfn::NPAR : cfn::NOM_P, ki);
+        for (int j = 0; j < cfn::NK; j++) k[(size_t)j * S + i] = ki[j];
+    }
+    if (!s->mpar_buf) RC_TRY(dev_alloc(s, &s->mpar_buf, k.size()));
+    HIP_TRY(hipMemcpyAsync(s->mpar_buf, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
 int cfnmpc_set_model_params(cfnmpc_solver* s, const double* p, int on_device, void* stream) {
     if (!s) return CFNMPC_EINVAL;
     DeviceGuard dg(s->device);
     cfn::Params& P = s->P;
     if (!p) {   // back to the folded constants (the default kernels)
-        if (P.mpar) { P.mpar = nullptr; s->lin_valid = false; invalidate_graphs(s); }
+        if (P.dist) {   // (the _dst kernels stay: they read the constants from the table, nominal rows from here on)
+            if (!s->mp_rows.empty()) RC_TRY(upload_mpar(s, nullptr, (hipStream_t)stream));
+            s->lin_valid = false;
+        } else if (P.mpar) { P.mpar = nullptr; s->lin_valid = false; invalidate_graphs(s); }
         s->mp_rows.clear();
         invalidate_sens(s);
         return CFNMPC_OK;
@@ -746,21 +770,7 @@ int cfnmpc_set_model_params(cfnmpc_solver* s, const double* p, int on_device, vo
         HIP_TRY(hipStreamSynchronize(st));
     }
     if (!cfn::model_params_ok(rows.data(), n)) return CFNMPC_EINVAL;
-    // derived constants, [NK][S] structure-of-arrays over every workspace row (padding rows and the spare block: nominal)
-    const size_t S = ((size_t)P.NW + 1) * 4;
-    std::vector<double> k((size_t)cfn::NK * S);
-    for (size_t i = 0; i < S; i++) {
-        double ki[cfn::NK];
-        cfn::derive_k(i < B ? rows.data() + i * cfn::NPAR : cfn::NOM_P, ki);
-        for (int j = 0; j < cfn::NK; j++) k[(size_t)j * S + i] = ki[j];
-    }
-    if (!s->mpar_buf) {
-        const int rc = dev_alloc(s, &s->mpar_buf, k.size());
-        if (rc != CFNMPC_OK) return rc;
-    }
-    // in place, in stream order, complete on return: a captured step graph (which holds the pointer) replays with the new values
-    HIP_TRY(hipMemcpyAsync(s->mpar_buf, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    RC_TRY(upload_mpar(s, rows.data(), st));
     if (!P.mpar) { P.mpar = s->mpar_buf; invalidate_graphs(s); }   // other kernels from here on
     s->lin_valid = false;
     s->mp_rows = std::move(rows);
@@ -783,6 +793,66 @@ int cfnmpc_get_model_params(cfnmpc_solver* s, double* p, int on_device, void* st
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemcpyAsync(p, src, n * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));   // (src is a host temporary)
+    return CFNMPC_OK;
+}
+
+int cfnmpc_set_disturbance(cfnmpc_solver* s, const double* d, int on_device, void* stream) {
+    if (!s) return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    cfn::Params& P = s->P;
+    hipStream_t st = (hipStream_t)stream;
+    if (!d) {   // back to the kernels in force before: _par while parameter rows are set, else the folded ones
+        if (P.dist) {
+            P.dist = nullptr;
+            if (s->mp_rows.empty()) P.mpar = nullptr;
+            s->lin_valid = false;
+            invalidate_graphs(s);
+        }
+        invalidate_sens(s);
+        return CFNMPC_OK;
+    }
+    // the fused start solve, the partial-condensing sweep and the development build's overlapped preparation have no _dst twins
+    if (P.fused || P.cond_N2 || s->overlap) return CFNMPC_EINVAL;
+    const size_t B = P.B, n = B * cfn::ND, S = ((size_t)P.NW + 1) * 4;
+    const bool host = is_host(on_device);
+    if (host && (!cfn::dist_rows_ok(d, n) || n > s->stage_doubles)) return CFNMPC_EINVAL;
+    if (!s->dist_buf) RC_TRY(dev_alloc(s, &s->dist_buf, (size_t)cfn::ND * S));   // (zero: padding rows and the spare block stay so)
+    if (!P.mpar && s->mp_rows.empty()) RC_TRY(upload_mpar(s, nullptr, st));      // (first rows without parameter rows: nominal table)
+    // rows -> table in place, in stream order: no copy to the host, no synchronisation for a device array; a captured step graph
+    // (which holds the pointer) replays with the new values
+    const double* src = d;
+    if (host) {
+        HIP_TRY(hipMemcpyAsync(s->stage_buf, d, n * sizeof(double), hipMemcpyHostToDevice, st));
+        src = s->stage_buf;
+    }
+    cfn::launch_dist_put((int)B, (int)S, src, s->dist_buf, st);
+    HIP_TRY(hipGetLastError());
+    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));   // (the staging buffer is reused)
+    if (!P.dist) { P.dist = s->dist_buf; P.mpar = s->mpar_buf; invalidate_graphs(s); }   // other kernels from here on
+    s->lin_valid = false;
+    invalidate_sens(s);
+    return CFNMPC_OK;
+}
+
+int cfnmpc_get_disturbance(cfnmpc_solver* s, double* d, int on_device, void* stream) {
+    if (!s || !d) return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    const cfn::Params& P = s->P;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t B = P.B, n = B * cfn::ND, S = ((size_t)P.NW + 1) * 4;
+    const bool host = is_host(on_device);
+    if (!P.dist) {   // none set: zero rows
+        if (host) std::fill_n(d, n, 0.0);
+        else HIP_TRY(hipMemsetAsync(d, 0, n * sizeof(double), st));
+        return CFNMPC_OK;
+    }
+    if (host && n > s->stage_doubles) return CFNMPC_EINVAL;
+    cfn::launch_dist_get((int)B, (int)S, P.dist, host ? s->stage_buf : d, st);
+    HIP_TRY(hipGetLastError());
+    if (host) {
+        HIP_TRY(hipMemcpyAsync(d, s->stage_buf, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
+    }
     return CFNMPC_OK;
 }
 
@@ -1369,44 +1439,60 @@ int cfnmpc_get_sens_active(cfnmpc_solver* s, signed char* act, int on_device, vo
 }
 
 namespace {
-// cfnmpc_sim (p = NULL: the folded constants) and cfnmpc_sim_params (p [batch][NPAR])
-int sim_impl(int batch, const double* x, const double* u, const double* p, double T, int steps, double* xn, int on_device,
-             void* stream) {
-    if (batch <= 0 || !x || !u || !xn || steps < 1 || !(T > 0)) return CFNMPC_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    if (p && is_host(on_device) && !cfn::model_params_ok(p, (size_t)batch * cfn::NPAR)) return CFNMPC_EINVAL;
-    if (!is_host(on_device)) {
-        if (p) cfn::launch_sim_par(batch, x, u, p, T, steps, xn, st);
-        else cfn::launch_sim(batch, x, u, T, steps, xn, st);
-        HIP_TRY(hipGetLastError());
-        return CFNMPC_OK;
-    }
-    // host pointers: device scratch cached per device and grown on demand (the estimator calls this
-    // at 66 Hz with batch 1, acados_estimator.cpp:589 -- no allocation per call); one caller at a time
-    static std::mutex mtx[64];             // one caller at a time PER DEVICE (predictors on different GPUs run concurrently)
+// Device scratch of the entry points that take host arrays without a solver (cfnmpc_sim*, cfnmpc_estimate_disturbance): cached per
+// device and grown on demand (the estimator calls cfnmpc_sim at 66 Hz with batch 1, acados_estimator.cpp:589 -- no allocation
+// per call); one caller at a time PER DEVICE (predictors on different GPUs run concurrently): `lock` is held by the caller
+// until its transfers are complete
+int host_scratch(size_t need, double** out, std::unique_lock<std::mutex>& lock) {
+    static std::mutex mtx[64];
     static double* scratch[64] = {nullptr};
     static size_t cap[64] = {0};
     int devi = 0;
     HIP_TRY(hipGetDevice(&devi));
     if (devi < 0 || devi >= 64) return CFNMPC_EHIP;
-    std::lock_guard<std::mutex> lock(mtx[devi]);
-    const size_t B = batch, need = B * (30 + (p ? cfn::NPAR : 0));
+    lock = std::unique_lock<std::mutex>(mtx[devi]);
     if (cap[devi] < need) {
         if (scratch[devi]) (void)hipFree(scratch[devi]);
         scratch[devi] = nullptr; cap[devi] = 0;
         if (hipMalloc((void**)&scratch[devi], need * 8) != hipSuccess) return CFNMPC_ENOMEM;
         cap[devi] = need;
     }
-    double *dx = scratch[devi], *du = dx + B * 13, *dn = du + B * 4;
+    *out = scratch[devi];
+    return CFNMPC_OK;
+}
+// cfnmpc_sim (p = NULL: the folded constants), cfnmpc_sim_params (p [batch][NPAR]) and cfnmpc_sim_dist (d [batch][ND], p or NULL)
+int sim_impl(int batch, const double* x, const double* u, const double* p, const double* d, double T, int steps, double* xn,
+             int on_device, void* stream) {
+    if (batch <= 0 || !x || !u || !xn || steps < 1 || !(T > 0)) return CFNMPC_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (p && is_host(on_device) && !cfn::model_params_ok(p, (size_t)batch * cfn::NPAR)) return CFNMPC_EINVAL;
+    if (d && is_host(on_device) && !cfn::dist_rows_ok(d, (size_t)batch * cfn::ND)) return CFNMPC_EINVAL;
+    auto launch = [&](const double* x_, const double* u_, const double* p_, const double* d_, double* xn_) {
+        if (d_) cfn::launch_sim_dst(batch, x_, u_, p_, d_, T, steps, xn_, st);
+        else if (p_) cfn::launch_sim_par(batch, x_, u_, p_, T, steps, xn_, st);
+        else cfn::launch_sim(batch, x_, u_, T, steps, xn_, st);
+    };
+    if (!is_host(on_device)) {
+        launch(x, u, p, d, xn);
+        HIP_TRY(hipGetLastError());
+        return CFNMPC_OK;
+    }
+    const size_t B = batch;
+    std::unique_lock<std::mutex> lock;
+    double* dx = nullptr;
+    RC_TRY(host_scratch(B * (30 + (p ? cfn::NPAR : 0) + (d ? cfn::ND : 0)), &dx, lock));
+    double *du = dx + B * 13, *dn = du + B * 4, *dp = nullptr, *dd = nullptr, *next = dn + B * 13;
     HIP_TRY(hipMemcpyAsync(dx, x, B * 13 * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(du, u, B * 4 * 8, hipMemcpyHostToDevice, st));
     if (p) {
-        double* dp = dn + B * 13;
+        dp = next; next += B * cfn::NPAR;
         HIP_TRY(hipMemcpyAsync(dp, p, B * cfn::NPAR * 8, hipMemcpyHostToDevice, st));
-        cfn::launch_sim_par(batch, dx, du, dp, T, steps, dn, st);
-    } else {
-        cfn::launch_sim(batch, dx, du, T, steps, dn, st);
     }
+    if (d) {
+        dd = next;
+        HIP_TRY(hipMemcpyAsync(dd, d, B * cfn::ND * 8, hipMemcpyHostToDevice, st));
+    }
+    launch(dx, du, dp, dd, dn);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(xn, dn, B * 13 * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1416,13 +1502,48 @@ int sim_impl(int batch, const double* x, const double* u, const double* p, doubl
 
 int cfnmpc_sim(int batch, const double* x, const double* u, double T, int steps, double* xn, int on_device,
                void* stream) {
-    return sim_impl(batch, x, u, nullptr, T, steps, xn, on_device, stream);
+    return sim_impl(batch, x, u, nullptr, nullptr, T, steps, xn, on_device, stream);
 }
 
 int cfnmpc_sim_params(int batch, const double* x, const double* u, const double* p, double T, int steps, double* xn,
                       int on_device, void* stream) {
     if (!p) return CFNMPC_EINVAL;
-    return sim_impl(batch, x, u, p, T, steps, xn, on_device, stream);
+    return sim_impl(batch, x, u, p, nullptr, T, steps, xn, on_device, stream);
+}
+
+int cfnmpc_sim_dist(int batch, const double* x, const double* u, const double* p, const double* d, double T, int steps,
+                    double* xn, int on_device, void* stream) {
+    if (!d) return CFNMPC_EINVAL;
+    return sim_impl(batch, x, u, p, d, T, steps, xn, on_device, stream);
+}
+
+int cfnmpc_estimate_disturbance(int batch, const double* x_prev, const double* u_prev, const double* x_meas, const double* p,
+                                double* d, double T, int steps, double gain_a, double gain_w, int on_device, void* stream) {
+    if (batch <= 0 || !x_prev || !u_prev || !x_meas || !d || steps < 1 || !(T > 0)) return CFNMPC_EINVAL;
+    if (!(gain_a > 0 && gain_a <= 1) || !(gain_w > 0 && gain_w <= 1)) return CFNMPC_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (!is_host(on_device)) {
+        cfn::launch_dist_observe(batch, x_prev, u_prev, x_meas, p, d, T, steps, gain_a, gain_w, st);
+        HIP_TRY(hipGetLastError());
+        return CFNMPC_OK;
+    }
+    const size_t B = batch;
+    if (p && !cfn::model_params_ok(p, B * cfn::NPAR)) return CFNMPC_EINVAL;
+    if (!cfn::dist_rows_ok(d, B * cfn::ND)) return CFNMPC_EINVAL;
+    std::unique_lock<std::mutex> lock;
+    double* dxp = nullptr;
+    RC_TRY(host_scratch(B * (30 + cfn::ND + (p ? cfn::NPAR : 0)), &dxp, lock));
+    double *du = dxp + B * 13, *dxm = du + B * 4, *dd = dxm + B * 13, *dp = p ? dd + B * cfn::ND : nullptr;
+    HIP_TRY(hipMemcpyAsync(dxp, x_prev, B * 13 * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(du, u_prev, B * 4 * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dxm, x_meas, B * 13 * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dd, d, B * cfn::ND * 8, hipMemcpyHostToDevice, st));
+    if (p) HIP_TRY(hipMemcpyAsync(dp, p, B * cfn::NPAR * 8, hipMemcpyHostToDevice, st));
+    cfn::launch_dist_observe(batch, dxp, du, dxm, dp, dd, T, steps, gain_a, gain_w, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(d, dd, B * cfn::ND * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
 }
 
 int cfnmpc_estimate(int batch, const double* meas, double* filt, const double* u, double dt, int use_lpf, double delay,
@@ -1573,7 +1694,7 @@ int cfnmpc_debug_start_factor(cfnmpc_solver* s, int mode, int reps, double* ms, 
     // k_factor / k_linfactor address the home 4-vectors in the wave-blocked layout (Params.v4b): a partial-condensing solver
     // keeps them instance-major and never runs these kernels -- refuse instead of reading and writing in the wrong layout
     if (s->P.cond_N2 || !s->P.v4b) return CFNMPC_EINVAL;
-    if (mode == 2 && (s->P.mpar || s->P.wtab)) return CFNMPC_EINVAL;   // (k_linfactor: folded model constants, uniform weights)
+    if (mode == 2 && (s->P.mpar || s->P.dist || s->P.wtab)) return CFNMPC_EINVAL;   // (k_linfactor: folded model constants, no disturbance, uniform weights)
     DeviceGuard dg(s->device);
     invalidate_sens(s);   // (rewrites KR / Pchk: they no longer belong to the last QP)
     hipStream_t st = (hipStream_t)stream;

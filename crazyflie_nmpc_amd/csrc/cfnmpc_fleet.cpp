@@ -290,6 +290,22 @@ int cfnmpc_fleet_set_model_params(cfnmpc_fleet* f, const double* p) {
                        [](Bucket& b, Staged q, int mode, void*) { return cfnmpc_set_model_params(b.s, q.d(0), mode, b.st); });
 }
 
+// per-instance disturbance rows, host or device (the rows of an observer: every control step).  Host rows are validated as a
+// whole first; a bucket refuses rows only for options every bucket shares (start_solve 2 / 3) or, with cond_N2, in the buckets
+// that condense -- checked by the first call on each bucket before anything of that bucket changes.
+int cfnmpc_fleet_set_disturbance(cfnmpc_fleet* f, const double* d, int on_device, void* stream) {
+    if (!f) return CFNMPC_EINVAL;
+    if (d && cfn::is_host(on_device) && !cfn::dist_rows_ok(d, (size_t)f->B * CFNMPC_ND)) return CFNMPC_EINVAL;
+    return fleet_write(f, on_device, stream, {col(d, CFNMPC_ND)},
+                       [](Bucket& b, Staged q, int mode, void* st) { return cfnmpc_set_disturbance(b.s, q.d(0), mode, st); });
+}
+
+int cfnmpc_fleet_get_disturbance(cfnmpc_fleet* f, double* d, int on_device, void* stream) {
+    if (!f || !d) return CFNMPC_EINVAL;
+    return fleet_read(f, on_device, stream, {col(d, CFNMPC_ND)},
+                      [](Bucket& b, Staged q, int mode, void* st) { return cfnmpc_get_disturbance(b.s, q.d(0), mode, st); });
+}
+
 // per-instance cost weights: host rows in the fleet's vehicle order -> each bucket's order.  Validated as a whole first, and a
 // bucket refuses rows only for options every bucket shares (start_solve 2 / 3, cond_N2), so the FIRST bucket refuses and nothing
 // has changed (as cfnmpc_fleet_set_model_params).

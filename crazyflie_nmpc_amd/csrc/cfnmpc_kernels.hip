@@ -144,14 +144,20 @@ __device__ __forceinline__ void erk_group(const double (&x)[13], const double (&
 
 // Model constants of instance `inst` (P.mpar, [NK][(NW + 1) * 4]: one coalesced load per constant for a lane-per-instance wave);
 // PAR = false: the folded constants, nothing read.
-template <bool PAR> using ModelK = typename std::conditional<PAR, ParK, NomK>::type;
-template <bool PAR>
-__device__ __forceinline__ ModelK<PAR> model_k(const Params& P, int inst) {
-    ModelK<PAR> mk;
+// DST (the _dst kernels, on top of PAR): the instance's disturbance row as well (P.dist, [ND][(NW + 1) * 4], the same layout).
+template <bool PAR, bool DST = false> using ModelK = typename std::conditional<DST, DstK, typename std::conditional<PAR, ParK, NomK>::type>::type;
+template <bool PAR, bool DST = false>
+__device__ __forceinline__ ModelK<PAR, DST> model_k(const Params& P, int inst) {
+    static_assert(PAR || !DST, "the _dst kernels read the constants from P.mpar");
+    ModelK<PAR, DST> mk;
     if constexpr (PAR) {
         const gdouble* mp = gm(P.mpar) + inst;
         const size_t S = ((size_t)P.NW + 1) * 4;
         SFOR(j, 0, 8, { mk.c[j] = mp[j * S]; });
+        if constexpr (DST) {
+            const gdouble* dp = gm(P.dist) + inst;
+            SFOR(j, 0, ND, { mk.d[j] = dp[j * S]; });
+        }
     }
     return mk;
 }
@@ -169,6 +175,16 @@ struct ParKG {
     __device__ double kwx() const { return p[5 * S]; }
     __device__ double kwy() const { return p[6 * S]; }
     __device__ double kwz() const { return p[7 * S]; }
+};
+// ... and the disturbance row the same way (k_linearise_dst)
+struct DstKG : ParKG {
+    const gdouble* dp;   // this lane's instance in row 0 of P.dist (the same stride)
+    __device__ double dax() const { return dp[0]; }
+    __device__ double day() const { return dp[S]; }
+    __device__ double daz() const { return dp[2 * S]; }
+    __device__ double dlx() const { return dp[3 * S]; }
+    __device__ double dly() const { return dp[4 * S]; }
+    __device__ double dlz() const { return dp[5 * S]; }
 };
 
 // Lane-per-instance (work-efficient: nothing is computed twice); one workgroup = one wavefront
@@ -203,11 +219,13 @@ static_assert(div_ok(52, 64 * 13), "k_forward: e / 52 by multiply-shift");
 //                   which = 0: P.ilist (count P.nipm[0]), 1: P.ilist2 (P.nipm[NI_LISTED], the interior-point fall-back rows).
 //   ERK (k_linearise_erk): M = P.erk_steps RK4 sub-steps of dt / M per interval (erk_group); whole fleet (GATHER = false) only.
 //   PAR (the _par kernels): the model constants of each lane's instance (P.mpar, model_k) instead of the folded ones; whole fleet only.
-template <bool GATHER, bool CSTORE = false, bool ERK = false, bool PAR = false>
+//   DST (the _dst kernels, with PAR): the instance's disturbance row too (P.dist), read at its uses like the constants.
+template <bool GATHER, bool CSTORE = false, bool ERK = false, bool PAR = false, bool DST = false>
 __device__ __forceinline__ void linearise_body(const Params& P, double* sx, double (*sc)[64 * 13], int* sinst,
                                                const int which = 0) {
     static_assert(!ERK || !GATHER, "ERK sub-steps: whole-fleet kernel only");
     static_assert(!PAR || !GATHER, "per-instance parameters: whole-fleet kernel only");
+    static_assert(!DST || PAR, "disturbance rows: on top of the per-instance constants");
     constexpr bool PAIRS = !GATHER;   // 16-byte stores of whole column groups (below)
     const int tid = threadIdx.x;
     const double h = P.dt;
@@ -222,9 +240,10 @@ __device__ __forceinline__ void linearise_body(const Params& P, double* sx, doub
     __syncthreads();
     const int inst = sinst[tid];
     // PAR: the instance's constants read at their uses (ParKG)
-    using LinK = typename std::conditional<PAR, ParKG, NomK>::type;
+    using LinK = typename std::conditional<DST, DstKG, typename std::conditional<PAR, ParKG, NomK>::type>::type;
     LinK mk{};
-    if constexpr (PAR) mk = ParKG{gm(P.mpar) + inst, (unsigned)(P.NW + 1) * 4u};
+    if constexpr (DST) mk = DstKG{{gm(P.mpar) + inst, (unsigned)(P.NW + 1) * 4u}, gm(P.dist) + inst};
+    else if constexpr (PAR) mk = ParKG{gm(P.mpar) + inst, (unsigned)(P.NW + 1) * 4u};
 #ifdef CFN_DEV   // (P.lin_k1 > 0: only the shooting intervals [lin_k0, lin_k1) -- the stage-chunked hand-over experiment)
     const int ka = P.lin_k1 > 0 ? P.lin_k0 : 0, kb = P.lin_k1 > 0 ? P.lin_k1 : N;
 #else
@@ -491,6 +510,19 @@ KALIGN __global__ __launch_bounds__(64) void k_linearise_erk_par(Params P) {
     __shared__ __attribute__((aligned(16))) double sc[4][64 * 13];
     __shared__ int sinst[64];
     linearise_body<false, false, true, true>(P, sx, sc, sinst);
+}
+// ... and with per-instance disturbance rows on top (cfnmpc_set_disturbance)
+KALIGN __global__ __launch_bounds__(64) void k_linearise_dst(Params P) {
+    __shared__ double sx[2 * 64 * 13];
+    __shared__ __attribute__((aligned(16))) double sc[4][64 * 13];
+    __shared__ int sinst[64];
+    linearise_body<false, false, false, true, true>(P, sx, sc, sinst);
+}
+KALIGN __global__ __launch_bounds__(64) void k_linearise_erk_dst(Params P) {
+    __shared__ double sx[2 * 64 * 13];
+    __shared__ __attribute__((aligned(16))) double sc[4][64 * 13];
+    __shared__ int sinst[64];
+    linearise_body<false, false, true, true, true>(P, sx, sc, sinst);
 }
 #ifdef CFN_DEV   // (overlapped preparation: development builds only)
 __global__ __launch_bounds__(64) void k_linearise_list(Params P) {
@@ -1088,7 +1120,8 @@ __device__ __forceinline__ int head_want(const Params& P, int last_tight) {
 // FUSED_PT form (lf_point) from the carried sub-step state and direction -- what the stored-block sweep computes from
 // k_linearise_erk's A, B, b up to rounding.
 // PAR (the _par kernels): the model constants of each lane's instance (P.mpar, model_k).
-template <bool COND, bool FUSED_PT = false, int SPLIT = 0, bool ERK = false, bool PAR = false>
+// DST (the _dst kernels, with PAR; matrix-free sweeps only): the instance's disturbance row as well (P.dist), loaded once.
+template <bool COND, bool FUSED_PT = false, int SPLIT = 0, bool ERK = false, bool PAR = false, bool DST = false>
 __device__ __forceinline__ void forward_body(const Params& P, double* xs, double* cs, int* sflag) {
     // 13-vectors travel through LDS tiles [instance][13] so that every global access of the wave
     // is a contiguous run (as in k_linearise); K, d, u, v are 32-byte runs per lane already.
@@ -1103,10 +1136,11 @@ __device__ __forceinline__ void forward_body(const Params& P, double* xs, double
     const double h = P.dt;
     // PAR: the instance's constants, loaded once (the one-step condensed sweep: read at their uses instead, ParKG -- carried,
     // they spill more in that form)
+    static_assert(!DST || (PAR && !COND), "disturbance rows: the matrix-free sweeps, on top of the per-instance constants");
     constexpr bool LAZY = PAR && COND && !ERK;
-    using FwdK = typename std::conditional<PAR, typename std::conditional<LAZY, ParKG, ParK>::type, NomK>::type;
+    using FwdK = typename std::conditional<DST, DstK, typename std::conditional<PAR, typename std::conditional<LAZY, ParKG, ParK>::type, NomK>::type>::type;
     FwdK mk{};
-    if constexpr (PAR && !LAZY) mk = model_k<PAR>(P, inst);
+    if constexpr (PAR && !LAZY) mk = model_k<PAR, DST>(P, inst);
     if constexpr (LAZY) mk = FwdK{gm(P.mpar) + inst, (unsigned)(P.NW + 1) * 4u};
     const double margin = P.ah_margin * (P.u_max - P.u_min);
     const gdouble* kp = gm(P.KR) + w * N * SZ_K + q * 4;
@@ -1470,6 +1504,13 @@ CFN_FWD_PAR(k_forward_erk_par, false, true, 0, true, true)
 CFN_FWD_PAR(k_forward_p1_erk_par, false, true, 1, true, true)
 CFN_FWD_PAR(k_forward_p2_erk_par, false, true, 2, true, true)
 CFN_FWD_PAR(k_cforward_erk_par, true, false, 0, true, true)
+// the six matrix-free sweeps with per-instance disturbance rows on top (cfnmpc_set_disturbance)
+CFN_FWD_PAR(k_forward_dst, false, true, 0, false, true, true)
+CFN_FWD_PAR(k_forward_p1_dst, false, true, 1, false, true, true)
+CFN_FWD_PAR(k_forward_p2_dst, false, true, 2, false, true, true)
+CFN_FWD_PAR(k_forward_erk_dst, false, true, 0, true, true, true)
+CFN_FWD_PAR(k_forward_p1_erk_dst, false, true, 1, true, true, true)
+CFN_FWD_PAR(k_forward_p2_erk_dst, false, true, 2, true, true, true)
 #undef CFN_FWD_PAR
 
 // ---------------------------------------------------------------------------------------------
@@ -3195,25 +3236,10 @@ void debug_prof_read(unsigned long long* out, int reset) {
 // =============================================================================================
 // predictor / plant step, layout glue
 // =============================================================================================
-// p (PAR only): per-instance parameters [B][NPAR] (cfnmpc_sim_params), the constants derived per lane as on the host
-template <bool PAR>
-__device__ __forceinline__ void sim_body(int B, const double* __restrict__ x, const double* __restrict__ u,
-                                         const double* __restrict__ p, double T, int steps, double* __restrict__ xn) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B) return;
-    ModelK<PAR> mk;
-    if constexpr (PAR) {
-        double pr[NPAR], kr[NK];
-        SFOR(e, 0, NPAR, { pr[e] = p[(size_t)i * NPAR + e]; });
-        derive_k(pr, kr);
-        SFOR(e, 0, 8, { mk.c[e] = kr[e]; });
-    }
-    double xc[13], uc[4], k1[13], k2[13], k3[13], k4[13], xt[13];
-#pragma unroll
-    for (int e = 0; e < 13; e++) xc[e] = x[(size_t)i * 13 + e];
-#pragma unroll
-    for (int e = 0; e < 4; e++) uc[e] = u[(size_t)i * 4 + e];
-    const double h = T / steps;
+// `steps` classic RK4 steps of h from xc, in place (external order)
+template <class K>
+__device__ __forceinline__ void rk4_steps(double (&xc)[13], const double (&uc)[4], double h, int steps, const K& mk) {
+    double k1[13], k2[13], k3[13], k4[13], xt[13];
     for (int s = 0; s < steps; s++) {
         f_expl(xc, uc, k1, mk);
 #pragma unroll
@@ -3228,16 +3254,97 @@ __device__ __forceinline__ void sim_body(int B, const double* __restrict__ x, co
 #pragma unroll
         for (int e = 0; e < 13; e++) xc[e] += (h / 6.0) * (k1[e] + 2 * k2[e] + 2 * k3[e] + k4[e]);
     }
+}
+// the constants and the disturbance of lane i from instance-major rows: p [B][NPAR] (NULL: the nominal row, derived by the same
+// expressions), d [B][ND] (cfnmpc_sim_dist, cfnmpc_estimate_disturbance)
+__device__ __forceinline__ DstK dst_k_rows(const double* __restrict__ p, const double* __restrict__ d, int i) {
+    DstK mk;
+    double pr[NPAR] = {G0, MQ, IXX, IYY, IZZ, CD, CT, 0.0325}, kr[NK];
+    if (p) SFOR(e, 0, NPAR, { pr[e] = p[(size_t)i * NPAR + e]; });
+    derive_k(pr, kr);
+    SFOR(e, 0, 8, { mk.c[e] = kr[e]; });
+    SFOR(e, 0, ND, { mk.d[e] = d[(size_t)i * ND + e]; });
+    return mk;
+}
+// p (PAR only): per-instance parameters [B][NPAR] (cfnmpc_sim_params), the constants derived per lane as on the host
+// d (DST, with PAR; p may be NULL = nominal): per-instance disturbance rows [B][ND] (cfnmpc_sim_dist)
+template <bool PAR, bool DST = false>
+__device__ __forceinline__ void sim_body(int B, const double* __restrict__ x, const double* __restrict__ u,
+                                         const double* __restrict__ p, const double* __restrict__ d, double T, int steps,
+                                         double* __restrict__ xn) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    ModelK<PAR, DST> mk;
+    if constexpr (DST) {
+        mk = dst_k_rows(p, d, i);
+    } else if constexpr (PAR) {
+        double pr[NPAR], kr[NK];
+        SFOR(e, 0, NPAR, { pr[e] = p[(size_t)i * NPAR + e]; });
+        derive_k(pr, kr);
+        SFOR(e, 0, 8, { mk.c[e] = kr[e]; });
+    }
+    double xc[13], uc[4];
+#pragma unroll
+    for (int e = 0; e < 13; e++) xc[e] = x[(size_t)i * 13 + e];
+#pragma unroll
+    for (int e = 0; e < 4; e++) uc[e] = u[(size_t)i * 4 + e];
+    rk4_steps(xc, uc, T / steps, steps, mk);
 #pragma unroll
     for (int e = 0; e < 13; e++) xn[(size_t)i * 13 + e] = xc[e];
 }
 __global__ void k_sim(int B, const double* __restrict__ x, const double* __restrict__ u, double T, int steps,
                       double* __restrict__ xn) {
-    sim_body<false>(B, x, u, nullptr, T, steps, xn);
+    sim_body<false>(B, x, u, nullptr, nullptr, T, steps, xn);
 }
 __global__ __launch_bounds__(256) void k_sim_par(int B, const double* __restrict__ x, const double* __restrict__ u, const double* __restrict__ p,
                           double T, int steps, double* __restrict__ xn) {
-    sim_body<true>(B, x, u, p, T, steps, xn);
+    sim_body<true>(B, x, u, p, nullptr, T, steps, xn);
+}
+__global__ __launch_bounds__(256) void k_sim_dst(int B, const double* __restrict__ x, const double* __restrict__ u, const double* __restrict__ p,
+                          const double* __restrict__ d, double T, int steps, double* __restrict__ xn) {
+    sim_body<true, true>(B, x, u, p, d, T, steps, xn);
+}
+
+// Disturbance observer (cfnmpc_estimate_disturbance), stateless, one instance per lane: the one-step prediction error of the
+// disturbed model, x^ = Phi(x_prev, u_prev; p, d) with `steps` RK4 sub-steps over T, e = x_meas - x^, fed back into the row
+//   d[0:3] += gain_a / T  R(q_prev) e[7:10]   (body-frame velocity error -> world-frame acceleration),   d[3:6] += gain_w / T  e[10:13].
+// Plant and model are the same map, so a constant true disturbance is a fixed point, reached in one step by gain 1 up to O(T).
+__global__ __launch_bounds__(256) void k_dist_observe(int B, const double* __restrict__ x_prev, const double* __restrict__ u_prev,
+                          const double* __restrict__ x_meas, const double* __restrict__ p, double* __restrict__ d, double T, int steps,
+                          double gain_a, double gain_w) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    const DstK mk = dst_k_rows(p, d, i);
+    double xc[13], uc[4];
+#pragma unroll
+    for (int e = 0; e < 13; e++) xc[e] = x_prev[(size_t)i * 13 + e];
+#pragma unroll
+    for (int e = 0; e < 4; e++) uc[e] = u_prev[(size_t)i * 4 + e];
+    const double q1 = xc[3], q2 = xc[4], q3 = xc[5], q4 = xc[6];
+    rk4_steps(xc, uc, T / steps, steps, mk);
+    const double ex = x_meas[(size_t)i * 13 + 7] - xc[7], ey = x_meas[(size_t)i * 13 + 8] - xc[8], ez = x_meas[(size_t)i * 13 + 9] - xc[9];
+    const double ga = gain_a / T, gw = gain_w / T;
+    double* di = d + (size_t)i * ND;
+    di[0] = mk.d[0] + ga * ((2 * q1 * q1 + 2 * q2 * q2 - 1) * ex - (2 * q1 * q4 - 2 * q2 * q3) * ey + (2 * q1 * q3 + 2 * q2 * q4) * ez);
+    di[1] = mk.d[1] + ga * ((2 * q1 * q4 + 2 * q2 * q3) * ex + (2 * q1 * q1 + 2 * q3 * q3 - 1) * ey - (2 * q1 * q2 - 2 * q3 * q4) * ez);
+    di[2] = mk.d[2] + ga * (-(2 * q1 * q3 - 2 * q2 * q4) * ex + (2 * q1 * q2 + 2 * q3 * q4) * ey + (2 * q1 * q1 + 2 * q4 * q4 - 1) * ez);
+#pragma unroll
+    for (int e = 0; e < 3; e++) di[3 + e] = mk.d[3 + e] + gw * (x_meas[(size_t)i * 13 + 10 + e] - xc[10 + e]);
+}
+// rows d [B][ND] (instance-major) -> the solver's table P.dist [ND][S], S = (NW + 1) * 4 (cfnmpc_set_disturbance; the rows
+// behind B stay zero)
+__global__ __launch_bounds__(256) void k_dist_put(int B, int S, const double* __restrict__ d, double* __restrict__ tab) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;   // element of d, read coalesced
+    if (e >= B * ND) return;
+    const int i = e / ND, j = e - i * ND;
+    tab[(size_t)j * S + i] = d[e];
+}
+// ... and back (cfnmpc_get_disturbance)
+__global__ __launch_bounds__(256) void k_dist_get(int B, int S, const double* __restrict__ tab, double* __restrict__ d) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= B * ND) return;
+    const int i = e / ND, j = e - i * ND;
+    d[e] = tab[(size_t)j * S + i];
 }
 
 // State assembly + delay compensation of the reference estimator, batched, one vehicle per lane
@@ -3478,7 +3585,7 @@ __global__ void k_reinit_failed(Params P) {
 // host has read it before this launch: stream order), so no memset sits between the iterations.
 __device__ __forceinline__ double max_nan(double acc, double v) { return (v > acc || v != v) ? v : acc; }   // NaN sticks
 // PAR: Phi with the model constants of each lane's instance (P.mpar; k_sqp_check_par)
-template <bool PAR>
+template <bool PAR, bool DST = false>
 __device__ __forceinline__ void sqp_check_body(const Params& P, const SqpArgs& A) {
     __shared__ double xs_o[64 * 13], xs_n[64 * 13];
     __shared__ int sfrz[64];
@@ -3492,7 +3599,7 @@ __device__ __forceinline__ void sqp_check_body(const Params& P, const SqpArgs& A
     const int w0 = blockIdx.x * 16;
     const int M = P.erk_steps;
     const double h = P.dt / M;
-    const ModelK<PAR> mk = model_k<PAR>(P, inst);
+    const ModelK<PAR, DST> mk = model_k<PAR, DST>(P, inst);
     const size_t i4b = P.v4b ? ((size_t)w * N * 4 + q) * 4 : (size_t)inst * N * 4;   // this lane's 4-vectors (Params.v4b)
     const size_t i4s = P.v4b ? 16 : 4;
     auto el13 = [&](const double* f, int e, int stages, int k) -> gdouble* {   // (k_forward's accessor)
@@ -3586,6 +3693,7 @@ __device__ __forceinline__ void sqp_check_body(const Params& P, const SqpArgs& A
 }
 __global__ __launch_bounds__(64) void k_sqp_check(Params P, SqpArgs A) { sqp_check_body<false>(P, A); }
 __global__ __launch_bounds__(64) void k_sqp_check_par(Params P, SqpArgs A) { sqp_check_body<true>(P, A); }
+__global__ __launch_bounds__(64) void k_sqp_check_dst(Params P, SqpArgs A) { sqp_check_body<true, true>(P, A); }
 
 // =============================================================================================
 // globalised SQP solve (cfnmpc_set_sqp_globalization): l1 merit backtracking behind SQP iteration j
@@ -3605,7 +3713,7 @@ __global__ __launch_bounds__(64) void k_sqp_check_par(Params P, SqpArgs A) { sqp
 // res_eq / res_ineq are those of the accepted trial, res_step is the FULL step |d|_inf; classification, frozen rows and the
 // counter of open rows as in k_sqp_check.  A NaN fails every comparison: the lane ends at a_T and the NaN sticks (max_nan, nan_pos).
 __device__ __forceinline__ double nan_pos(double v) { return (v > 0.0 || v != v) ? v : 0.0; }   // max(v, 0), NaN sticks
-template <bool PAR>
+template <bool PAR, bool DST = false>
 __device__ __forceinline__ void sqp_ls_body(const Params& P, const SqpArgs& A, const LsArgs& G) {
     __shared__ double xs_o[2 * 64 * 13], xs_n[2 * 64 * 13], ty[64 * 17], ws[17], sal[64];   // (two pairs of tiles: first sweep)
     __shared__ int sfrz[64];
@@ -3619,7 +3727,7 @@ __device__ __forceinline__ void sqp_ls_body(const Params& P, const SqpArgs& A, c
     const int w0 = blockIdx.x * 16;
     const int M = P.erk_steps;
     const double h = P.dt / M;
-    const ModelK<PAR> mk = model_k<PAR>(P, inst);
+    const ModelK<PAR, DST> mk = model_k<PAR, DST>(P, inst);
     const size_t i4b = P.v4b ? ((size_t)w * N * 4 + q) * 4 : (size_t)inst * N * 4;   // this lane's 4-vectors (Params.v4b)
     const size_t i4s = P.v4b ? 16 : 4;
     auto el13 = [&](const double* f, int e, int stages, int k) -> gdouble* {   // (k_forward's accessor)
@@ -3863,6 +3971,7 @@ __device__ __forceinline__ void sqp_ls_body(const Params& P, const SqpArgs& A, c
 }
 __global__ __launch_bounds__(64) void k_sqp_ls(Params P, SqpArgs A, LsArgs G) { sqp_ls_body<false>(P, A, G); }
 __global__ __launch_bounds__(64) void k_sqp_ls_par(Params P, SqpArgs A, LsArgs G) { sqp_ls_body<true>(P, A, G); }
+__global__ __launch_bounds__(64) void k_sqp_ls_dst(Params P, SqpArgs A, LsArgs G) { sqp_ls_body<true, true>(P, A, G); }
 
 // =============================================================================================
 // NLP evaluation at the current iterate (cfnmpc_eval_nlp)
@@ -3885,7 +3994,7 @@ __global__ __launch_bounds__(64) void k_sqp_ls_par(Params P, SqpArgs A, LsArgs G
 // builds the four independent Jacobian points side by side and the kernel spills past 512 registers.
 // A.pi (x-iterate layout, internal order) / A.gu (u-iterate layout) are written when given; NaN sticks (max_nan).
 static_assert(div_ok(68, 64 * 17), "k_nlp_eval: e / 68 by multiply-shift");
-template <bool PAR>
+template <bool PAR, bool DST = false>
 __device__ __forceinline__ void nlp_eval_body(const Params& P, const NlpArgs& A) {
     __shared__ double tx[64 * 13], ty[64 * 17], pts[3 * 10 * 64], xn[13 * 64], ws[17];
     const int N = P.N;
@@ -3898,7 +4007,7 @@ __device__ __forceinline__ void nlp_eval_body(const Params& P, const NlpArgs& A)
     const int w0 = blockIdx.x * 16;
     const int M = P.erk_steps;
     const double h = P.dt / M;
-    const ModelK<PAR> mk = model_k<PAR>(P, inst);
+    const ModelK<PAR, DST> mk = model_k<PAR, DST>(P, inst);
     const size_t i4b = P.v4b ? ((size_t)w * N * 4 + q) * 4 : (size_t)inst * N * 4;   // this lane's 4-vectors (Params.v4b)
     const size_t i4s = P.v4b ? 16 : 4;
     const bool keep = A.pi != nullptr;
@@ -4079,6 +4188,7 @@ __device__ __forceinline__ void nlp_eval_body(const Params& P, const NlpArgs& A)
 }
 __global__ __launch_bounds__(64) void k_nlp_eval(Params P, NlpArgs A) { nlp_eval_body<false>(P, A); }
 __global__ __launch_bounds__(64) void k_nlp_eval_par(Params P, NlpArgs A) { nlp_eval_body<true>(P, A); }
+__global__ __launch_bounds__(64) void k_nlp_eval_dst(Params P, NlpArgs A) { nlp_eval_body<true, true>(P, A); }
 
 // ---------------------------------------------------------------------------------------------
 // launchers
@@ -4086,7 +4196,9 @@ __global__ __launch_bounds__(64) void k_nlp_eval_par(Params P, NlpArgs A) { nlp_
 static inline int imin_h(int a, int b) { return a < b ? a : b; }
 static inline int imax_h(int a, int b) { return a > b ? a : b; }
 void launch_linearise(const Params& P, int chunks, hipStream_t st) {
-    if (P.mpar && P.erk_steps > 1) hipLaunchKernelGGL(k_linearise_erk_par, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
+    if (P.dist && P.erk_steps > 1) hipLaunchKernelGGL(k_linearise_erk_dst, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
+    else if (P.dist) hipLaunchKernelGGL(k_linearise_dst, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
+    else if (P.mpar && P.erk_steps > 1) hipLaunchKernelGGL(k_linearise_erk_par, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
     else if (P.mpar) hipLaunchKernelGGL(k_linearise_par, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
     else if (P.erk_steps > 1) hipLaunchKernelGGL(k_linearise_erk, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
     else hipLaunchKernelGGL(k_linearise, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
@@ -4116,6 +4228,10 @@ void launch_qp_start(const Params& P, hipStream_t st, hipEvent_t* ev, bool skip_
 #ifdef CFN_DEV
         if (P.forward_half) { hipLaunchKernelGGL(k_forward_half, dim3((P.B + 63) / 64), dim3(64), 0, st, P); } else
 #endif
+        if (P.dist) {   // (per-instance disturbance rows: the same choice among the _dst twins)
+            if (P.fwd_split) { if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p1_erk_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_forward_p1_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
+            else { if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_erk_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_forward_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
+        } else
         if (P.mpar) {   // (per-instance model constants: the same choice among the _par twins)
             if (P.fwd_split) { if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p1_erk_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_forward_p1_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
             else { if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_erk_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_forward_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
@@ -4147,6 +4263,8 @@ void launch_cforward(const Params& P, hipStream_t st) {
     else hipLaunchKernelGGL(k_cforward, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
 }
 static void launch_forward_p2(const Params& P, hipStream_t st) {   // second part of the split sweep
+    if (P.dist) { if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p2_erk_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_forward_p2_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
+    else
     if (P.mpar) { if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p2_erk_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_forward_p2_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
     else if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p2_erk, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
     else hipLaunchKernelGGL(k_forward_p2, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
@@ -4269,6 +4387,20 @@ void launch_sim(int B, const double* x, const double* u, double T, int steps, do
 void launch_sim_par(int B, const double* x, const double* u, const double* p, double T, int steps, double* xn, hipStream_t st) {
     hipLaunchKernelGGL(k_sim_par, dim3((B + 255) / 256), dim3(256), 0, st, B, x, u, p, T, steps, xn);
 }
+void launch_sim_dst(int B, const double* x, const double* u, const double* p, const double* d, double T, int steps, double* xn,
+                    hipStream_t st) {
+    hipLaunchKernelGGL(k_sim_dst, dim3((B + 255) / 256), dim3(256), 0, st, B, x, u, p, d, T, steps, xn);
+}
+void launch_dist_observe(int B, const double* x_prev, const double* u_prev, const double* x_meas, const double* p, double* d,
+                         double T, int steps, double gain_a, double gain_w, hipStream_t st) {
+    hipLaunchKernelGGL(k_dist_observe, dim3((B + 255) / 256), dim3(256), 0, st, B, x_prev, u_prev, x_meas, p, d, T, steps, gain_a, gain_w);
+}
+void launch_dist_put(int B, int S, const double* d, double* tab, hipStream_t st) {
+    hipLaunchKernelGGL(k_dist_put, dim3((B * ND + 255) / 256), dim3(256), 0, st, B, S, d, tab);
+}
+void launch_dist_get(int B, int S, const double* tab, double* d, hipStream_t st) {
+    hipLaunchKernelGGL(k_dist_get, dim3((B * ND + 255) / 256), dim3(256), 0, st, B, S, tab, d);
+}
 void launch_estimate(int B, const double* meas, double* filt, const double* u, double dt, int use_lpf, double delay,
                      int steps, double* x_est, double* x_pred, hipStream_t st) {
     hipLaunchKernelGGL(k_estimate, dim3((B + 255) / 256), dim3(256), 0, st, B, meas, filt, u, dt, use_lpf, delay, steps,
@@ -4297,15 +4429,18 @@ void launch_reinit_failed(const Params& P, hipStream_t st) {
     hipLaunchKernelGGL(k_reinit_failed, dim3((P.B + 255) / 256), dim3(256), 0, st, P);
 }
 void launch_sqp_check(const Params& P, const SqpArgs& A, hipStream_t st) {
-    if (P.mpar) hipLaunchKernelGGL(k_sqp_check_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
+    if (P.dist) hipLaunchKernelGGL(k_sqp_check_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
+    else if (P.mpar) hipLaunchKernelGGL(k_sqp_check_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
     else hipLaunchKernelGGL(k_sqp_check, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
 }
 void launch_sqp_ls(const Params& P, const SqpArgs& A, const LsArgs& G, hipStream_t st) {
-    if (P.mpar) hipLaunchKernelGGL(k_sqp_ls_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A, G);
+    if (P.dist) hipLaunchKernelGGL(k_sqp_ls_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A, G);
+    else if (P.mpar) hipLaunchKernelGGL(k_sqp_ls_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A, G);
     else hipLaunchKernelGGL(k_sqp_ls, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A, G);
 }
 void launch_nlp_eval(const Params& P, const NlpArgs& A, hipStream_t st) {
-    if (P.mpar) hipLaunchKernelGGL(k_nlp_eval_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
+    if (P.dist) hipLaunchKernelGGL(k_nlp_eval_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
+    else if (P.mpar) hipLaunchKernelGGL(k_nlp_eval_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
     else hipLaunchKernelGGL(k_nlp_eval, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
 }
 void launch_init_iterate(const Params& P, int mode, hipStream_t st) {

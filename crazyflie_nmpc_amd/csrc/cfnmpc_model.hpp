@@ -16,6 +16,8 @@
 // which the linearisation kernel writes and the Riccati kernels read in compact form.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
+#include <utility>
 
 namespace cfn {
 
@@ -55,6 +57,30 @@ struct ParK {
     __device__ double kwy() const { return c[6]; }
     __device__ double kwz() const { return c[7]; }
 };
+// ---- external disturbance (cfnmpc_set_disturbance) ----------------------------------------------
+// A disturbance row d = [ax, ay, az | alx, aly, alz]: a_w = d[0:3] an acceleration in the WORLD frame [m/s^2], al_b = d[3:6] an
+// angular acceleration in the BODY frame [rad/s^2]:   v_b' += R(q)' a_w,   w' += al_b   (R of p' = R(q) v_b, JacPoint::R).
+// al_b adds nothing to df/dx; R(q)' a_w adds to d v_b' / d q only, the block gravity already occupies (-g0 R' e_z is the
+// disturbance (0, 0, -g0)): the pattern of A is unchanged.  A K type that has dax() .. dlz() carries one instance's row next to
+// its constants (DstK; DstKG in cfnmpc_kernels.hip reads it at its uses); for every other K the terms below are not compiled.
+constexpr int ND = 6;     // include/cfnmpc.h: CFNMPC_ND
+template <class K, class = void> struct has_dist : std::false_type {};
+template <class K> struct has_dist<K, std::void_t<decltype(std::declval<const K&>().dax())>> : std::true_type {};
+struct DstK : ParK {
+    double d[ND];
+    __device__ double dax() const { return d[0]; }
+    __device__ double day() const { return d[1]; }
+    __device__ double daz() const { return d[2]; }
+    __device__ double dlx() const { return d[3]; }
+    __device__ double dly() const { return d[4]; }
+    __device__ double dlz() const { return d[5]; }
+};
+// every entry finite, any sign (cfnmpc_set_disturbance, cfnmpc_sim_dist, cfnmpc_estimate_disturbance)
+inline bool dist_rows_ok(const double* d, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (!(d[i] >= -1.7976931348623157e308 && d[i] <= 1.7976931348623157e308)) return false;   // (NaN fails both)
+    return true;
+}
 // the nominal parameter row (export_ode_model.py:34-42; l = 0.0325 is ARM exactly)
 constexpr double NOM_P[NPAR] = {G0, MQ, IXX, IYY, IZZ, CD, CT, 0.0325};
 static_assert(NOM_P[7] == ARM, "nominal arm length");
@@ -140,6 +166,13 @@ __device__ __forceinline__ void f_expl(const double* __restrict__ x, const doubl
     dx[10] = mk.ka() * (s1 + s2 - s3 - s4) + mk.kwx() * (wy * wz);
     dx[11] = mk.kb() * (s1 - s2 - s3 + s4) + mk.kwy() * (wx * wz);
     dx[12] = mk.kc() * (s1 - s2 + s3 - s4) + mk.kwz() * (wx * wy);
+    if constexpr (has_dist<K>::value) {   // v_b' += R(q)' a_w, w' += al_b
+        const double ax = mk.dax(), ay = mk.day(), az = mk.daz();
+        dx[7] += (2 * q1 * q1 + 2 * q2 * q2 - 1) * ax + (2 * q1 * q4 + 2 * q2 * q3) * ay - (2 * q1 * q3 - 2 * q2 * q4) * az;
+        dx[8] += -(2 * q1 * q4 - 2 * q2 * q3) * ax + (2 * q1 * q1 + 2 * q3 * q3 - 1) * ay + (2 * q1 * q2 + 2 * q3 * q4) * az;
+        dx[9] += (2 * q1 * q3 + 2 * q2 * q4) * ax - (2 * q1 * q2 - 2 * q3 * q4) * ay + (2 * q1 * q1 + 2 * q4 * q4 - 1) * az;
+        dx[10] += mk.dlx(); dx[11] += mk.dly(); dx[12] += mk.dlz();
+    }
 }
 
 // Point data of df/dx at one RK stage point that is shared by all sensitivity columns:
@@ -195,6 +228,14 @@ __device__ __forceinline__ void jvp(const JacPoint& J, const double* __restrict_
         o7 += 2 * mk.g0() * (q3 * a - q4 * b + q1 * c - q2 * d);
         o8 += -2 * mk.g0() * (q2 * a + q1 * b + q4 * c + q3 * d);
         o9 += -4 * mk.g0() * (q1 * a + q4 * d);
+        if constexpr (has_dist<K>::value) {   // d (R(q)' a_w) along the q-part: the rows of dR = (dR / dq) (a, b, c, d), transposed
+            const double ax = mk.dax(), ay = mk.day(), az = mk.daz();
+            const double d14 = q1 * d + q4 * a, d23 = q2 * c + q3 * b, d13 = q1 * c + q3 * a;
+            const double d24 = q2 * d + q4 * b, d12 = q1 * b + q2 * a, d34 = q3 * d + q4 * c;
+            o7 += 4 * (q1 * a + q2 * b) * ax + 2 * (d14 + d23) * ay + 2 * (d24 - d13) * az;
+            o8 += 2 * (d23 - d14) * ax + 4 * (q1 * a + q3 * c) * ay + 2 * (d12 + d34) * az;
+            o9 += 2 * (d13 + d24) * ax + 2 * (d34 - d12) * ay + 4 * (q1 * a + q4 * d) * az;
+        }
     }
     if (HW) {
         const double a = s[10], b = s[11], c = s[12];
@@ -233,6 +274,14 @@ __device__ __forceinline__ void jtvp(const JacPoint& J, const double* __restrict
     o[10] = 0.5 * (-q2 * a + q1 * b + q4 * c - q3 * d) + vz * v[8] - vy * v[9] + mk.kwy() * (wz * v[11]) + mk.kwz() * (wy * v[12]);
     o[11] = 0.5 * (-q3 * a - q4 * b + q1 * c + q2 * d) - vz * v[7] + vx * v[9] + mk.kwx() * (wz * v[10]) + mk.kwz() * (wx * v[12]);
     o[12] = 0.5 * (-q4 * a + q3 * b - q2 * c + q1 * d) + vy * v[7] - vx * v[8] + mk.kwx() * (wy * v[10]) + mk.kwy() * (wx * v[11]);
+    if constexpr (has_dist<K>::value) {   // (d (R(q)' a_w) / dq)' v[7:10] = d (a_w' R(q) l) / dq, l = v[7:10]: Jpq's expressions at l
+        const double ax = mk.dax(), ay = mk.day(), az = mk.daz();
+        const double lx = v[7], ly = v[8], lz = v[9];
+        o[3] += (4 * q1 * lx - 2 * q4 * ly + 2 * q3 * lz) * ax + (4 * q1 * ly + 2 * q4 * lx - 2 * q2 * lz) * ay + (4 * q1 * lz - 2 * q3 * lx + 2 * q2 * ly) * az;
+        o[4] += (4 * q2 * lx + 2 * q3 * ly + 2 * q4 * lz) * ax + (2 * q3 * lx - 2 * q1 * lz) * ay + (2 * q4 * lx + 2 * q1 * ly) * az;
+        o[5] += (2 * q2 * ly + 2 * q1 * lz) * ax + (4 * q3 * ly + 2 * q2 * lx + 2 * q4 * lz) * ay + (-2 * q1 * lx + 2 * q4 * ly) * az;
+        o[6] += (-2 * q1 * ly + 2 * q2 * lz) * ax + (2 * q1 * lx + 2 * q3 * lz) * ay + (4 * q4 * lz + 2 * q2 * lx + 2 * q3 * ly) * az;
+    }
 }
 
 // df/du column c (rows 9..12 only): d v'_z, d w'_x, d w'_y, d w'_z
@@ -309,6 +358,16 @@ __device__ __forceinline__ void lf_point(const double (&xq)[10], const double (&
     dk[10] = mk.kwx() * (oy * wz + wy * oz) + ju[1];
     dk[11] = mk.kwy() * (ox * wz + wx * oz) + ju[2];
     dk[12] = mk.kwz() * (ox * wy + wx * oy) + ju[3];
+    if constexpr (has_dist<K>::value) {   // v_b' += R' a_w = 2 r' a_w and its derivative 2 dr' a_w (diagonal: dR / 2 = 2 h), w' += al_b
+        const double ax = mk.dax(), ay = mk.day(), az = mk.daz();
+        kk[7] += 2.0 * (r0 * ax + r3 * ay + r6 * az);
+        kk[8] += 2.0 * (r1 * ax + r4 * ay + r7 * az);
+        kk[9] += 2.0 * (r2 * ax + r5 * ay + r8 * az);
+        dk[7] += 2.0 * (2.0 * h0 * ax + dr3 * ay + dr6 * az);
+        dk[8] += 2.0 * (dr1 * ax + 2.0 * h4 * ay + dr7 * az);
+        dk[9] += 2.0 * (dr2 * ax + dr5 * ay + 2.0 * h8 * az);
+        kk[10] += mk.dlx(); kk[11] += mk.dly(); kk[12] += mk.dlz();
+    }
 }
 
 }  // namespace cfn

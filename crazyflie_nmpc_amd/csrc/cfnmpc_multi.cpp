@@ -292,6 +292,14 @@ int cfnmpc_multi_set_model_params(cfnmpc_multi* m, const double* p) {
                        [](Shard& s, Staged q, int) { return cfnmpc_fleet_set_model_params(s.f, q.d(0)); });
 }
 
+int cfnmpc_multi_set_disturbance(cfnmpc_multi* m, const double* d) {
+    if (!m) return CFNMPC_EINVAL;
+    if (d && !cfn::dist_rows_ok(d, (size_t)m->B * CFNMPC_ND)) return CFNMPC_EINVAL;   // (as a whole: no shard changes)
+    return multi_write(m, {col(d, CFNMPC_ND)},
+                       [](Shard& s, Staged q, int mode) { return cfnmpc_set_disturbance(s.s, q.d(0), mode, s.st); },
+                       [](Shard& s, Staged q, int mode) { return cfnmpc_fleet_set_disturbance(s.f, q.d(0), mode, s.st); });
+}
+
 int cfnmpc_multi_set_weights_batch(cfnmpc_multi* m, const double* W, const double* WN) {
     if (!m) return CFNMPC_EINVAL;
     if (!cfn::weight_rows_ok(W, WN, (size_t)m->B)) return CFNMPC_EINVAL;   // (as a whole: no shard changes)

@@ -186,6 +186,9 @@ struct Params {
     double* wtab;                // per-instance cost weights (cfnmpc_set_weights_batch), [(NW + 1) * 4][32]: state weights in the internal
                                  // order at [0, 13), input weights at [13, 17), terminal weights (internal order) at [17, 30); effective
                                  // values (scaling applied); padding rows and the spare block uniform; NULL = the uniform W / WN above
+    double* dist;                // per-instance disturbance rows (cfnmpc_set_disturbance), [ND][(NW + 1) * 4] structure-of-arrays like mpar
+                                 // (padding rows and the spare block zero); set only together with mpar (nominal rows if the caller set
+                                 // none); NULL = no disturbance (the folded or _par kernels)
 };
 
 // The linearisation (AR, BR, b) of the HOME blocks: [group of 16 blocks][stage][block of the group][sz] -- a lane-per-instance wave
@@ -239,6 +242,15 @@ void launch_estimate(int B, const double* meas, double* filt, const double* u, d
 void launch_sim(int B, const double* x, const double* u, double T, int steps, double* xn, hipStream_t st);
 // the same with per-instance parameters p [B][NPAR] (instance-major, cfnmpc_sim_params)
 void launch_sim_par(int B, const double* x, const double* u, const double* p, double T, int steps, double* xn, hipStream_t st);
+// ... and per-instance disturbance rows d [B][ND] (cfnmpc_sim_dist; p may be NULL = the nominal row)
+void launch_sim_dst(int B, const double* x, const double* u, const double* p, const double* d, double T, int steps, double* xn,
+                    hipStream_t st);
+// disturbance observer (cfnmpc_estimate_disturbance): d [B][ND] updated in place from the one-step prediction error
+void launch_dist_observe(int B, const double* x_prev, const double* u_prev, const double* x_meas, const double* p, double* d,
+                         double T, int steps, double gain_a, double gain_w, hipStream_t st);
+// rows d [B][ND] <-> the table Params.dist [ND][S] (cfnmpc_set_disturbance / cfnmpc_get_disturbance)
+void launch_dist_put(int B, int S, const double* d, double* tab, hipStream_t st);
+void launch_dist_get(int B, int S, const double* tab, double* d, hipStream_t st);
 // AoS [B][S][E] (external order) <-> wave-blocked vectors; perm13: first 13 entries of each
 // row are states and are permuted to the internal order.
 void launch_put(int B, int S, int E, int perm13, const double* aos, double* blk, hipStream_t st, int v4b = 0);   // v4b: E = 4 fields in the wave-blocked layout (Params.v4b)

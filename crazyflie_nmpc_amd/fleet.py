@@ -128,6 +128,22 @@ class MixedHorizonFleet:
             raise ValueError(f"expected shape {(self.B, 8)}, got {pa.shape}")
         _check(self._L.cfnmpc_fleet_set_model_params(self._h, pa.ctypes.data_as(C.c_void_p)), "cfnmpc_fleet_set_model_params")
 
+    def set_disturbance(self, d=None, stream=None):
+        """per-vehicle disturbance rows [B][6] in the fleet's vehicle order (numpy or a device tensor); None: none"""
+        if d is None:
+            _check(self._L.cfnmpc_fleet_set_disturbance(self._h, None, 0, _launch_stream(stream, self._device)), "cfnmpc_fleet_set_disturbance")
+            return
+        pd, dev, st, _k = _arg(d, (self.B, 6), device=self._device)
+        if stream:
+            st = C.c_void_p(stream)
+        _check(self._L.cfnmpc_fleet_set_disturbance(self._h, pd, dev, st), "cfnmpc_fleet_set_disturbance")
+
+    def disturbance(self):
+        """-> [B][6] rows in force, in the fleet's vehicle order (zeros while none are set)"""
+        out = np.empty((self.B, 6))
+        _check(self._L.cfnmpc_fleet_get_disturbance(self._h, out.ctypes.data_as(C.c_void_p), 0, None), "cfnmpc_fleet_get_disturbance")
+        return out
+
     def set_weights_batch(self, W=None, WN=None):
         """per-vehicle cost weights, host arrays W [B][17] / WN [B][13] in the fleet's vehicle order; None, None: uniform"""
         pw, pn = _weight_rows(self.B, W, WN)

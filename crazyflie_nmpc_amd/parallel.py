@@ -145,6 +145,19 @@ class MultiGpuFleet:
         if rc != 0:
             raise ValueError(f"cfnmpc_multi_set_model_params failed with code {rc}")
 
+    def set_disturbance(self, d=None):
+        """per-vehicle disturbance rows, host array [B][6] of the whole fleet; None: none"""
+        import ctypes as C
+        if d is None:
+            rc = self._L.cfnmpc_multi_set_disturbance(self._h, None)
+        else:
+            da = np.ascontiguousarray(d, dtype=np.float64)
+            if da.shape != (self.B, 6):
+                raise ValueError(f"expected shape {(self.B, 6)}, got {da.shape}")
+            rc = self._L.cfnmpc_multi_set_disturbance(self._h, da.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise ValueError(f"cfnmpc_multi_set_disturbance failed with code {rc}")
+
     def set_weights_batch(self, W=None, WN=None):
         """per-vehicle cost weights, host arrays W [B][17] / WN [B][13] of the whole fleet; None, None: uniform"""
         from .fleet import _weight_rows

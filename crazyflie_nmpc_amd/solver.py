@@ -29,6 +29,9 @@ def _sqp_mode(mode):
 NP = 8
 PARAM_NAMES = ("g0", "mq", "Ixx", "Iyy", "Izz", "Cd", "Ct", "l")
 NOMINAL_PARAMS = np.array([9.8066, 33e-3, 1.395e-5, 1.395e-5, 2.173e-5, 7.9379e-06, 3.25e-4, 0.0325])
+# per-instance disturbance rows (include/cfnmpc.h: cfnmpc_set_disturbance): world-frame acceleration, body-frame angular acceleration
+ND = 6
+DIST_NAMES = ("ax", "ay", "az", "alx", "aly", "alz")
 
 
 def hover_speed(params):
@@ -228,6 +231,26 @@ class BatchSolver:
         """-> [B][NP] rows in force (the nominal row everywhere while none are set)"""
         out = np.empty((self.B, NP))
         _check(self._L.cfnmpc_get_model_params(self._h, out.ctypes.data_as(C.c_void_p), 0, None), "cfnmpc_get_model_params")
+        return out
+
+    def set_disturbance(self, d=None, stream=None):
+        """Per-instance disturbance rows [B][ND] (DIST_NAMES order: a world-frame acceleration [m/s^2] and a body-frame angular
+        acceleration [rad/s^2]; numpy or a device tensor); None: no disturbance.  Cheap enough for every control step: a device
+        tensor is taken without a copy to the host or a synchronisation, and captured step graphs replay with the new values.
+        stream: a raw hipStream_t instead of torch's current stream."""
+        if d is None:
+            _check(self._L.cfnmpc_set_disturbance(self._h, None, 0, _launch_stream(stream, self._device)), "cfnmpc_set_disturbance")
+            return
+        pd, dev, st, _k = _arg(d, (self.B, ND), device=self._device)
+        if stream:
+            st = C.c_void_p(stream)
+        _check(self._L.cfnmpc_set_disturbance(self._h, pd, dev, st), "cfnmpc_set_disturbance")
+
+    def disturbance(self):
+        """-> [B][ND] rows in force (zeros while none are set)"""
+        out = np.empty((self.B, ND))
+        _check(self._L.cfnmpc_get_disturbance(self._h, out.ctypes.data_as(C.c_void_p), 0, _launch_stream(None, self._device)),
+               "cfnmpc_get_disturbance")
         return out
 
     def set_weights_batch(self, W=None, WN=None):
@@ -495,11 +518,45 @@ class BatchSolver:
         return h
 
 
-def sim(x, u, T=0.06, steps=4, out=None, params=None):
+def _rows_like(x, rows, n):
+    """optional rows [B][n] on x's side: -> (pointer or None, keepalive); host rows beside a device x are uploaded"""
+    if rows is None:
+        return None, None
+    B = x.shape[0]
+    if _is_torch(x):
+        import torch
+        if not _is_torch(rows):
+            rows = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.float64), device=x.device)
+        p, _d, _s, k = _arg(rows, (B, n), device=_torch_device())
+        return p, k
+    a = np.ascontiguousarray(rows, dtype=np.float64)
+    if a.shape != (B, n):
+        raise ValueError(f"expected shape {(B, n)}, got {a.shape}")
+    return a.ctypes.data_as(C.c_void_p), a
+
+
+def sim(x, u, T=0.06, steps=4, out=None, params=None, dist=None):
     """Batched predictor / plant step (crazyflie_acados_sim_solve, acados_estimator.cpp:589).  params [B][NP]: each
-    row's own model (cfnmpc_sim_params), e.g. a plant that differs from the controller's model."""
+    row's own model (cfnmpc_sim_params), e.g. a plant that differs from the controller's model.  dist [B][ND]: each row's
+    disturbance (cfnmpc_sim_dist; with or without params)."""
     L = _lib.lib()
     B = x.shape[0]
+    if dist is not None:
+        if _is_torch(x):
+            import torch
+            if out is None:
+                out = torch.empty_like(x)
+            px, _d, st, _k = _arg(x, (B, NX), device=_torch_device()); pu, _d2, _s, _k2 = _arg(u, (B, NU), device=_torch_device()); po, _d3, _s3, _k3 = _arg(out, (B, NX), device=_torch_device())
+            dev = 1
+        else:
+            xa = np.ascontiguousarray(x, dtype=np.float64); ua = np.ascontiguousarray(u, dtype=np.float64)
+            if out is None:
+                out = np.empty_like(xa)
+            px, pu, po, dev, st = xa.ctypes.data_as(C.c_void_p), ua.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), 0, None
+        pp, _kp = _rows_like(x, params, NP)
+        pd, _kd = _rows_like(x, dist, ND)
+        _check(L.cfnmpc_sim_dist(B, px, pu, pp, pd, float(T), int(steps), po, dev, st), "cfnmpc_sim_dist")
+        return out
     if _is_torch(x):
         import torch
         if out is None:
@@ -526,6 +583,31 @@ def sim(x, u, T=0.06, steps=4, out=None, params=None):
     _check(L.cfnmpc_sim(B, xa.ctypes.data_as(C.c_void_p), ua.ctypes.data_as(C.c_void_p), float(T), int(steps),
                         out.ctypes.data_as(C.c_void_p), 0, None), "cfnmpc_sim")
     return out
+
+
+def estimate_disturbance(x_prev, u_prev, x_meas, d, T=0.015, steps=1, gain_a=0.5, gain_w=0.5, params=None):
+    """Disturbance observer (cfnmpc_estimate_disturbance), in place on d [B][ND]: the one-step prediction error of the disturbed
+    model from (x_prev, u_prev) against x_meas, fed back with gains in (0, 1].  All torch device tensors or all numpy, like sim;
+    feed d to BatchSolver.set_disturbance.  -> d"""
+    L = _lib.lib()
+    B = x_prev.shape[0]
+    if _is_torch(x_prev):
+        px, _d, st, _k = _arg(x_prev, (B, NX), device=_torch_device()); pu, _d2, _s, _k2 = _arg(u_prev, (B, NU), device=_torch_device())
+        pm, _d3, _s3, _k3 = _arg(x_meas, (B, NX), device=_torch_device()); pd, _d4, _s4, _k4 = _arg(d, (B, ND), device=_torch_device())
+        dev = 1
+    else:
+        if not (isinstance(d, np.ndarray) and d.dtype == np.float64 and d.flags.c_contiguous and d.shape == (B, ND)):
+            raise ValueError(f"d: expected a contiguous float64 array {(B, ND)} (updated in place)")
+        xa = np.ascontiguousarray(x_prev, dtype=np.float64); ua = np.ascontiguousarray(u_prev, dtype=np.float64)
+        ma = np.ascontiguousarray(x_meas, dtype=np.float64)
+        if xa.shape != (B, NX) or ua.shape != (B, NU) or ma.shape != (B, NX):
+            raise ValueError("expected x_prev, x_meas [B][13] and u_prev [B][4]")
+        px, pu, pm, pd = (a.ctypes.data_as(C.c_void_p) for a in (xa, ua, ma, d))
+        dev, st = 0, None
+    pp, _kp = _rows_like(x_prev, params, NP)
+    _check(L.cfnmpc_estimate_disturbance(B, px, pu, pm, pp, pd, float(T), int(steps), float(gain_a), float(gain_w), dev, st),
+           "cfnmpc_estimate_disturbance")
+    return d
 
 
 def estimate(meas, filt, u, dt=0.015, use_lpf=True, delay=0.06, steps=4):

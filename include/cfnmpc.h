@@ -273,6 +273,26 @@ int cfnmpc_set_cost_scaling(cfnmpc_solver *s, double stage_scale, double termina
 #define CFNMPC_NP 8
 int cfnmpc_set_model_params(cfnmpc_solver *s, const double *p /*[B][CFNMPC_NP] or NULL*/, int on_device, void *stream);
 int cfnmpc_get_model_params(cfnmpc_solver *s, double *p /*[B][CFNMPC_NP]*/, int on_device, void *stream);
+/* Per-instance external disturbance: d [B][CFNMPC_ND], one row per instance,
+ *   d = [ax, ay, az | alx, aly, alz]:  a_w = d[0:3] an acceleration in the WORLD frame [m/s^2] (wind, a payload),
+ *                                      al_b = d[3:6] an angular acceleration in the BODY frame [rad/s^2] (a torque bias),
+ *   v_b' += R(q)' a_w,   w' += al_b      (R(q) the matrix of p' = R(q) v_b).
+ * The linearisation, the matrix-free forward sweeps, the SQP residual and line search and cfnmpc_eval_nlp use each instance's row
+ * on top of its model parameters (cfnmpc_set_model_params; nominal if none are set).  cfnmpc_init_iterate's hover mode and the
+ * hover speed of a parameter row stay disturbance-blind: they are the hover of the undisturbed vehicle.
+ *   cfnmpc_set_disturbance: made to be called every control step (the rows come from an observer, cfnmpc_estimate_disturbance):
+ *     asynchronous on `stream`.  Host arrays are validated (every entry finite, any sign; else CFNMPC_EINVAL and nothing changes)
+ *     and staged (CFNMPC_ON_HOST returns when the transfer is complete); DEVICE arrays are taken as they are, without a copy to the
+ *     host and without synchronisation -- one small kernel.  New values over old ones are written in place: captured step graphs
+ *     stay valid and replay with them; a sensitivity evaluation and a kept linearisation are invalidated, as by
+ *     cfnmpc_set_model_params.  d = NULL returns the solver to the kernels in force before (folded constants, or per-instance
+ *     parameters while those are set); switching between NULL and rows invalidates captured step graphs.  Refused
+ *     (CFNMPC_EINVAL) beside start_solve 2 or 3 and beside cond_N2 > 0 (no disturbed twins of the fused start solve and of the
+ *     condensed sweep); cfnmpc_debug_start_factor mode 2 is refused while rows are set.
+ *   cfnmpc_get_disturbance: the rows in force (zeros while none are set). */
+#define CFNMPC_ND 6
+int cfnmpc_set_disturbance(cfnmpc_solver *s, const double *d /*[B][CFNMPC_ND] or NULL*/, int on_device, void *stream);
+int cfnmpc_get_disturbance(cfnmpc_solver *s, double *d /*[B][CFNMPC_ND]*/, int on_device, void *stream);
 /* Per-instance cost weights: W [B][17] and WN [B][13], one row per instance in the external order of
  * cfnmpc_opts.W / .WN, unscaled -- the effective weights of row i are stage_scale * W[i] and terminal_scale * WN[i], and a later
  * cfnmpc_set_cost_scaling rescales the rows in force.  The reference tunes the 17 Wdiag_* values per vehicle through each node's
@@ -480,6 +500,18 @@ int cfnmpc_sim(int batch, const double *x, const double *u, double T, int steps,
  * differs from the controller's model.  Host arrays are validated (finite, > 0); device arrays are taken as they are. */
 int cfnmpc_sim_params(int batch, const double *x, const double *u, const double *p, double T, int steps, double *xn,
                       int on_device, void *stream);
+/* ... and with per-instance disturbance rows d [batch][CFNMPC_ND] (as cfnmpc_set_disturbance): the disturbed plant.  p as in
+ * cfnmpc_sim_params, or NULL = the nominal row.  Host arrays are validated (d: finite); device arrays are taken as they are. */
+int cfnmpc_sim_dist(int batch, const double *x, const double *u, const double *p, const double *d, double T, int steps,
+                    double *xn, int on_device, void *stream);
+/* Disturbance observer, stateless, one lane per instance: with x^ = Phi(x_prev, u_prev; p, d) (`steps` RK4 sub-steps over T, the
+ * map of cfnmpc_sim_dist) and e = x_meas - x^,
+ *   d[0:3] += gain_a / T * R(q_prev) e[7:10],      d[3:6] += gain_w / T * e[10:13]       (d [batch][CFNMPC_ND], in place).
+ * Gains in (0, 1], else CFNMPC_EINVAL.  A constant disturbance is a fixed point (plant and model are the same map); gain 1 is
+ * dead-beat up to O(T), smaller gains filter measurement noise.  Feed d to cfnmpc_set_disturbance (device arrays: no
+ * synchronisation anywhere in the loop).  p [batch][CFNMPC_NP] or NULL = nominal. */
+int cfnmpc_estimate_disturbance(int batch, const double *x_prev, const double *u_prev, const double *x_meas, const double *p,
+                                double *d, double T, int steps, double gain_a, double gain_w, int on_device, void *stream);
 
 /* ESTIMATOR::predictor() for a fleet (acados_estimator.cpp:521-634), DEVICE pointers only:
  * assembles the 13-state from mocap position, onboard Euler angles [deg, as published by the
@@ -546,6 +578,11 @@ int cfnmpc_fleet_set_erk_steps(cfnmpc_fleet *f, int num_steps);
 int cfnmpc_fleet_set_cost_scaling(cfnmpc_fleet *f, double stage_scale, double terminal_scale);
 /* cfnmpc_set_model_params for a fleet: HOST array [B][CFNMPC_NP] in the fleet's vehicle order (NULL: nominal) */
 int cfnmpc_fleet_set_model_params(cfnmpc_fleet *f, const double *p);
+/* cfnmpc_set_disturbance for a fleet: [B][CFNMPC_ND] in the fleet's vehicle order (NULL: none), host or device like
+ * cfnmpc_fleet_set_x0 (a device array goes through each bucket's staging on the bucket's stream); host rows are validated as a
+ * whole first.  cfnmpc_fleet_get_disturbance: the rows in force. */
+int cfnmpc_fleet_set_disturbance(cfnmpc_fleet *f, const double *d, int on_device, void *stream);
+int cfnmpc_fleet_get_disturbance(cfnmpc_fleet *f, double *d, int on_device, void *stream);
 /* cfnmpc_set_weights_batch for a fleet: HOST arrays [B][17] / [B][13] in the fleet's vehicle order, scattered to the buckets;
  * validated as a whole first (a bad row, or an option that refuses rows, leaves every bucket unchanged; an allocation or copy
  * failure in a later bucket does not undo the earlier ones, as with cfnmpc_fleet_set_model_params) */
@@ -629,6 +666,8 @@ int cfnmpc_multi_set_erk_steps(cfnmpc_multi *m, int num_steps);
 int cfnmpc_multi_set_cost_scaling(cfnmpc_multi *m, double stage_scale, double terminal_scale);
 /* cfnmpc_set_model_params for every shard: HOST array [B][CFNMPC_NP] of the whole fleet (NULL: nominal) */
 int cfnmpc_multi_set_model_params(cfnmpc_multi *m, const double *p);
+/* cfnmpc_set_disturbance for every shard: HOST array [B][CFNMPC_ND] of the whole fleet (NULL: none), validated as a whole first */
+int cfnmpc_multi_set_disturbance(cfnmpc_multi *m, const double *d);
 /* cfnmpc_set_weights_batch for every shard (both create variants): HOST arrays [B][17] / [B][13] of the whole fleet; validated
  * as a whole first (a bad row leaves every shard unchanged; an allocation or copy failure in a later shard does not undo the
  * earlier ones) */
