@@ -35,6 +35,10 @@ SYMBOLS = [
     "cfnmpc_multi_eval_sens_x0", "cfnmpc_multi_get_sens_x0",
     "cfnmpc_eval_nlp", "cfnmpc_get_nlp_stats", "cfnmpc_get_nlp_multipliers", "cfnmpc_fleet_eval_nlp", "cfnmpc_fleet_get_nlp_stats",
     "cfnmpc_multi_eval_nlp", "cfnmpc_multi_get_nlp_stats",
+    "cfnmpc_set_uncertainty", "cfnmpc_set_uncertainty_gain", "cfnmpc_eval_uncertainty", "cfnmpc_get_backoff", "cfnmpc_get_uncertainty",
+    "cfnmpc_tighten_box", "cfnmpc_fleet_set_uncertainty", "cfnmpc_fleet_set_uncertainty_gain", "cfnmpc_fleet_eval_uncertainty",
+    "cfnmpc_fleet_get_backoff", "cfnmpc_fleet_get_uncertainty", "cfnmpc_fleet_tighten_box", "cfnmpc_multi_set_uncertainty",
+    "cfnmpc_multi_set_uncertainty_gain", "cfnmpc_multi_eval_uncertainty", "cfnmpc_multi_get_backoff", "cfnmpc_multi_tighten_box",
 ]
 ABI_VERSION = 9   # CFNMPC_ABI_VERSION of the include/cfnmpc.h this binding was written against
 
@@ -112,6 +116,18 @@ def lib():
     L.cfnmpc_fleet_get_sens_x0.argtypes = [vp, i32, i32, vp, vp, i32, vp]
     L.cfnmpc_multi_eval_sens_x0.argtypes = [vp, dbl]
     L.cfnmpc_multi_get_sens_x0.argtypes = [vp, i32, i32, vp, vp]
+    for pre in ("cfnmpc_", "cfnmpc_fleet_"):
+        getattr(L, pre + "set_uncertainty").argtypes = [vp, vp, vp, i32, vp]
+        getattr(L, pre + "set_uncertainty_gain").argtypes = [vp, i32, vp, i32, vp]
+        getattr(L, pre + "eval_uncertainty").argtypes = [vp, vp]
+        getattr(L, pre + "get_backoff").argtypes = [vp, vp, i32, vp]
+        getattr(L, pre + "get_uncertainty").argtypes = [vp, i32, i32, vp, vp, i32, vp]
+        getattr(L, pre + "tighten_box").argtypes = [vp, dbl, dbl, vp, i32, vp]
+    L.cfnmpc_multi_set_uncertainty.argtypes = [vp, vp, vp]
+    L.cfnmpc_multi_set_uncertainty_gain.argtypes = [vp, i32, vp]
+    L.cfnmpc_multi_eval_uncertainty.argtypes = [vp]
+    L.cfnmpc_multi_get_backoff.argtypes = [vp, vp]
+    L.cfnmpc_multi_tighten_box.argtypes = [vp, dbl, dbl, vp]
     L.cfnmpc_eval_nlp.argtypes = [vp, i32, vp]
     L.cfnmpc_get_nlp_stats.argtypes = [vp, vp, vp, i32, vp]
     L.cfnmpc_get_nlp_multipliers.argtypes = [vp, vp, vp, i32, vp]

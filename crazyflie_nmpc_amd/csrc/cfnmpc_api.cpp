@@ -97,6 +97,22 @@ struct cfnmpc_solver {
     // 2: the multipliers too)
     cfn::NlpArgs nlp;
     int nlp_state;
+    // uncertainty propagation and robust input-bound tightening (cfnmpc_eval_uncertainty / cfnmpc_tighten_box; DESIGN.md
+    // section 5.21); every buffer is allocated at the first call that needs it
+    struct Unc {
+        double* stage = nullptr;     // staging of host arrays, [B][13][13] (the solver's own staging buffer may be shorter)
+        double *S0 = nullptr, *W = nullptr, *K = nullptr;   // the tables (cfnmpc_ws.hpp: UncArgs) ...
+        bool has_S0 = false, has_W = false;                 // ... and whether one is in force (NULL given: zero)
+        int gain_mode = CFNMPC_UNC_GAIN_RICCATI;
+        double* beta = nullptr;      // backoffs, home 4-vector layout
+        bool beta_valid = false;     // until the next evaluation, cfnmpc_init_iterate or cfnmpc_set_iterate
+        bool current = false;        // the evaluation belongs to the last QP (cfnmpc_get_uncertainty sweeps its blocks)
+        bool inputs_moved = false;   // cfnmpc_set_x0 / cfnmpc_set_yref since the last solve
+        int* ncl = nullptr;          // [B] clamped entries of the last tightening
+        // the nominal box while a tightened one is in force: per-stage (the copies below, home layout) or the scalar box
+        double *nom_lb = nullptr, *nom_ub = nullptr;
+        bool tight = false, nom_stages = false;
+    } unc;
 };
 
 namespace {
@@ -198,6 +214,25 @@ int copy_out(std::initializer_list<Out> outs, int on_device, hipStream_t st) {
     for (const Out& o : outs)
         if (o.dst) HIP_TRY(hipMemcpyAsync(o.dst, o.src, o.bytes, kind, st));
     if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
+
+// Host reads of per-row outputs that may exceed any one buffer (cfnmpc_get_sens_x0, cfnmpc_get_uncertainty): the rows in chunks
+// of whole wavefronts through a staging buffer of at most 32 Mi doubles, allocated at the first such read.  `per`: doubles per
+// row; chunk(b0, nb, stage) launches for the rows [b0, b0 + nb) into `stage` and enqueues its copies to the caller's arrays.
+template <typename F>
+int host_row_chunks(cfnmpc_solver* s, size_t per, F chunk) {
+    const size_t B = s->P.B, cap_max = (size_t)1 << 25;
+    if (!s->sens_stage) {
+        const size_t want = std::min(B * (size_t)(s->P.N + 1) * 221, cap_max);
+        const int rc = dev_alloc(s, &s->sens_stage, want);
+        if (rc != CFNMPC_OK) return rc;
+        s->sens_stage_doubles = want;
+    }
+    size_t rows = s->sens_stage_doubles / per;
+    rows = rows >= B ? B : (rows & ~(size_t)3);   // (fewer than four rows: the buffer holds them all)
+    if (rows == 0) return CFNMPC_ENOMEM;   // (unreachable: the buffer holds four rows of the longest range)
+    for (size_t b0 = 0; b0 < B; b0 += rows) RC_TRY(chunk(b0, std::min(rows, B - b0), s->sens_stage));
     return CFNMPC_OK;
 }
 
@@ -560,12 +595,14 @@ unsigned long long cfnmpc_workspace_bytes(const cfnmpc_solver* s) { return s ? s
 int cfnmpc_set_x0(cfnmpc_solver* s, const double* x0, int on_device, void* stream) {
     if (!s || !x0) return CFNMPC_EINVAL;
     DeviceGuard dg(s->device);
+    s->unc.inputs_moved = true;   // (cfnmpc_eval_uncertainty: the data of the next QP, no longer the last one's)
     return put_field(s, x0, on_device, 1, 13, 1, s->P.x0, (hipStream_t)stream);
 }
 
 int cfnmpc_set_yref(cfnmpc_solver* s, const double* yref, const double* yref_e, int on_device, void* stream) {
     if (!s || !yref || !yref_e) return CFNMPC_EINVAL;
     DeviceGuard dg(s->device);
+    s->unc.inputs_moved = true;
     int rc = put_field(s, yref, on_device, s->P.N, 17, 1, s->P.yref, (hipStream_t)stream);
     if (rc != CFNMPC_OK) return rc;
     return put_field(s, yref_e, on_device, 1, 13, 1, s->P.yref_e, (hipStream_t)stream);
@@ -577,6 +614,7 @@ int cfnmpc_set_yref_windows(cfnmpc_solver* s, const double* traj, int n_rows, in
     DeviceGuard dg(s->device);
     if (n_rows > 0 && (!traj || n_rows < s->P.N + 1)) return CFNMPC_EINVAL;
     if (n_rows <= 0 && traj) return CFNMPC_EINVAL;
+    s->unc.inputs_moved = true;
     cfn::launch_windows(s->P, traj, n_rows > 0 ? n_rows : 0, mode, iter, des_xyz, uss, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return CFNMPC_OK;
@@ -585,7 +623,49 @@ int cfnmpc_set_yref_windows(cfnmpc_solver* s, const double* traj, int n_rows, in
 // kernel arguments changed (weights, box): the captured steps hold the old ones
 static void invalidate_graphs(cfnmpc_solver* s) { s->gvalid[0] = s->gvalid[1] = false; }
 // the QP's data changed since the last solve: no sensitivities until the next one
-static void invalidate_sens(cfnmpc_solver* s) { s->sens_src = 0; s->sens_valid = false; }
+static void invalidate_sens(cfnmpc_solver* s) { s->sens_src = 0; s->sens_valid = false; s->unc.current = false; }
+
+// The four blocks of the per-stage boxes (home lb / ub, compact lb / ub; cfnmpc_set_box_stages, cfnmpc_tighten_box).
+static int ensure_box_blocks(cfnmpc_solver* s) {
+    cfn::Params& P = s->P;
+    if (s->lbs_keep && P.clbs && P.cubs) return CFNMPC_OK;
+    // allocated and initialised as a whole before any pointer is committed: a failure half-way (ENOMEM, a failed copy)
+    // leaves the solver on the scalar box with nothing dangling (the blocks stay owned by s->allocs until cfnmpc_free)
+    const size_t cnt = ((size_t)P.NW + 1) * 4 * P.N * 4;
+    // (blocks a failed earlier attempt did get are kept in s->box_blk and reused: a retry allocates only what is missing)
+    int rc = CFNMPC_OK;
+    for (int q = 0; q < 4 && rc == CFNMPC_OK; q++)
+        if (!s->box_blk[q]) rc = dev_alloc(s, &s->box_blk[q], cnt);
+    if (rc != CFNMPC_OK) return rc;
+    double *lk = s->box_blk[0], *uk = s->box_blk[1], *cl = s->box_blk[2], *cu = s->box_blk[3];
+    // rows of the spare block (parked rows of compacted waves): a wide finite box
+    std::vector<double> lo(4 * (size_t)P.N * 4, -1e30), hi(4 * (size_t)P.N * 4, 1e30);
+    HIP_TRY(hipMemcpy(lk + (size_t)P.NW * 4 * P.N * 4, lo.data(), lo.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(uk + (size_t)P.NW * 4 * P.N * 4, hi.data(), hi.size() * 8, hipMemcpyHostToDevice));
+    s->lbs_keep = lk; s->ubs_keep = uk; P.clbs = cl; P.cubs = cu;
+    return CFNMPC_OK;
+}
+
+// A tightened box in force (cfnmpc_tighten_box) gives way to the nominal one, on `st`: per-stage nominal arrays are copied back
+// in place (captured step graphs keep replaying), a scalar nominal box switches the route back (and invalidates them).
+static int untighten(cfnmpc_solver* s, hipStream_t st) {
+    cfn::Params& P = s->P;
+    if (!s->unc.tight) return CFNMPC_OK;
+    if (s->unc.nom_stages) {
+        const size_t bytes = (size_t)P.NW * 4 * P.N * 4 * sizeof(double);
+        HIP_TRY(hipMemcpyAsync(P.lbs, s->unc.nom_lb, bytes, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(P.ubs, s->unc.nom_ub, bytes, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(P.clbs, s->unc.nom_lb, bytes, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(P.cubs, s->unc.nom_ub, bytes, hipMemcpyDeviceToDevice, st));
+    } else {
+        if (P.lbs) { s->lbs_keep = P.lbs; s->ubs_keep = P.ubs; }
+        P.lbs = P.ubs = nullptr;
+        invalidate_graphs(s);
+    }
+    s->unc.tight = false;
+    invalidate_sens(s);
+    return CFNMPC_OK;
+}
 
 // Per-instance weight table (Params.wtab, layout: cfnmpc_ws.hpp) from the rows in force, scaling applied: uploaded in place on
 // `st` and complete on return, so that a captured step graph (which holds the pointer) replays with the new values.
@@ -858,6 +938,14 @@ int cfnmpc_get_disturbance(cfnmpc_solver* s, double* d, int on_device, void* str
 
 int cfnmpc_set_box(cfnmpc_solver* s, double u_min, double u_max) {
     if (!s || !(u_max > u_min)) return CFNMPC_EINVAL;
+    if (s->unc.tight) {   // a tightened box in force: the nominal one comes back (cfnmpc_tighten_box)
+        // (no stream argument here: a tightening or a solve enqueued on a non-blocking stream -- fleet buckets, multi shards --
+        //  is not ordered before the null stream; wait for the device, then restore and complete)
+        DeviceGuard dg(s->device);
+        HIP_TRY(hipDeviceSynchronize());
+        RC_TRY(untighten(s, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+    }
     s->P.u_min = u_min;   // kernel arguments: take effect at the next cfnmpc_solve
     s->P.u_max = u_max;
     invalidate_sens(s);
@@ -872,6 +960,7 @@ int cfnmpc_set_box_stages(cfnmpc_solver* s, const double* lb, const double* ub, 
     if (!lb) {                       // back to the scalar box of cfnmpc_set_box
         if (P.lbs) { s->lbs_keep = P.lbs; s->ubs_keep = P.ubs; }
         P.lbs = P.ubs = nullptr;
+        s->unc.tight = false;        // (a tightened box goes with it: the scalar box is the nominal one from here on)
         invalidate_graphs(s);
         invalidate_sens(s);
         return CFNMPC_OK;
@@ -883,22 +972,7 @@ int cfnmpc_set_box_stages(cfnmpc_solver* s, const double* lb, const double* ub, 
     if (is_host(on_device))
         for (size_t i = 0; i < n; i++) if (!(lb[i] <= ub[i])) return CFNMPC_EINVAL;
     invalidate_sens(s);
-    if (!s->lbs_keep || !P.clbs || !P.cubs) {
-        // allocated and initialised as a whole before any pointer is committed: a failure half-way (ENOMEM, a failed copy)
-        // leaves the solver on the scalar box with nothing dangling (the blocks stay owned by s->allocs until cfnmpc_free)
-        const size_t cnt = ((size_t)P.NW + 1) * 4 * P.N * 4;
-        // (blocks a failed earlier attempt did get are kept in s->box_blk and reused: a retry allocates only what is missing)
-        int rc = CFNMPC_OK;
-        for (int q = 0; q < 4 && rc == CFNMPC_OK; q++)
-            if (!s->box_blk[q]) rc = dev_alloc(s, &s->box_blk[q], cnt);
-        if (rc != CFNMPC_OK) return rc;
-        double *lk = s->box_blk[0], *uk = s->box_blk[1], *cl = s->box_blk[2], *cu = s->box_blk[3];
-        // rows of the spare block (parked rows of compacted waves): a wide finite box
-        std::vector<double> lo(4 * (size_t)P.N * 4, -1e30), hi(4 * (size_t)P.N * 4, 1e30);
-        HIP_TRY(hipMemcpy(lk + (size_t)P.NW * 4 * P.N * 4, lo.data(), lo.size() * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(uk + (size_t)P.NW * 4 * P.N * 4, hi.data(), hi.size() * 8, hipMemcpyHostToDevice));
-        s->lbs_keep = lk; s->ubs_keep = uk; P.clbs = cl; P.cubs = cu;
-    }
+    RC_TRY(ensure_box_blocks(s));
     // the caller's AoS order [inst][stage][4] -> the layout of the home 4-vectors (Params.v4b).  Both arrays are STAGED first
     // (in the compact box buffers: scratch of the QP kernels, rewritten by every solve that uses them) and the home pair is
     // overwritten only after both puts succeeded -- a failure leaves the previous lb AND ub in force, never a mixed box.
@@ -911,6 +985,7 @@ int cfnmpc_set_box_stages(cfnmpc_solver* s, const double* lb, const double* ub, 
     HIP_TRY(hipMemcpyAsync(s->ubs_keep, P.cubs, bytes, hipMemcpyDeviceToDevice, st));
     if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));   // synchronous form: complete when the call returns
     P.lbs = s->lbs_keep; P.ubs = s->ubs_keep;
+    s->unc.tight = false;   // (the new arrays are the nominal box; a tightened one they replaced is gone)
     invalidate_graphs(s);
     return CFNMPC_OK;
 }
@@ -945,6 +1020,7 @@ int cfnmpc_init_iterate(cfnmpc_solver* s, int mode, void* stream) {
     if (s->P.as_warm) HIP_TRY(hipMemsetAsync(s->P.wvalid, 0, sizeof(int) * (size_t)s->P.B, (hipStream_t)stream));   // a new iterate: no set to start from
     s->lin_valid = false;
     invalidate_sens(s);
+    s->unc.beta_valid = false;
     return CFNMPC_OK;
 }
 
@@ -953,6 +1029,7 @@ int cfnmpc_set_iterate(cfnmpc_solver* s, const double* x, const double* u, int o
     DeviceGuard dg(s->device);
     s->lin_valid = false;
     invalidate_sens(s);
+    s->unc.beta_valid = false;
     if (s->P.as_warm) HIP_TRY(hipMemsetAsync(s->P.wvalid, 0, sizeof(int) * (size_t)s->P.B, (hipStream_t)stream));
     int rc = put_field(s, x, on_device, s->P.N + 1, 13, 1, s->P.xit, (hipStream_t)stream);
     if (rc != CFNMPC_OK) return rc;
@@ -984,6 +1061,7 @@ void launch_sqp_close(cfnmpc_solver* s, const cfn::SqpArgs& chk, hipStream_t st)
 
 int rti_step(cfnmpc_solver* s, hipStream_t st, bool reinit, const cfn::SqpArgs* chk) {
     invalidate_sens(s);   // (until the step is through)
+    s->unc.inputs_moved = false;
     hipEvent_t* e = nullptr;
     if (s->profiling && s->ev_used < EV_PER_STEP * MAX_PROFILED_STEPS) {   // bounded: later steps go untimed
         while (s->ev.size() < s->ev_used + EV_PER_STEP) {
@@ -1407,27 +1485,17 @@ int cfnmpc_get_sens_x0(cfnmpc_solver* s, int stage, int n_stages, double* du, do
         HIP_TRY(hipGetLastError());
         return CFNMPC_OK;
     }
-    // host arrays: rows in chunks of whole wavefronts through a staging buffer of at most 32 Mi doubles
-    const size_t per = nu + nx, cap_max = (size_t)1 << 25;
-    if (!s->sens_stage) {
-        const size_t want = std::min(B * (size_t)(N + 1) * 221, cap_max);
-        const int rc = dev_alloc(s, &s->sens_stage, want);
-        if (rc != CFNMPC_OK) return rc;
-        s->sens_stage_doubles = want;
-    }
-    size_t chunk = s->sens_stage_doubles / per;
-    chunk = chunk >= B ? B : (chunk & ~(size_t)3);   // (fewer than four rows: the buffer holds them all)
-    if (chunk == 0) return CFNMPC_ENOMEM;   // (unreachable: the buffer holds four rows of the longest range)
-    for (size_t b0 = 0; b0 < B; b0 += chunk) {
-        const size_t nb = std::min(chunk, B - b0);
+    // host arrays: rows in chunks of whole wavefronts through the staging buffer (host_row_chunks)
+    RC_TRY(host_row_chunks(s, nu + nx, [&](size_t b0, size_t nb, double* stage) {
         A.b0 = (int)b0; A.nb = (int)nb;
-        A.du = du ? s->sens_stage : nullptr;
-        A.dx = dx ? s->sens_stage + nb * nu : nullptr;
+        A.du = du ? stage : nullptr;
+        A.dx = dx ? stage + nb * nu : nullptr;
         cfn::launch_sens_fwd(s->P, A, st);
         HIP_TRY(hipGetLastError());
         if (du) HIP_TRY(hipMemcpyAsync(du + b0 * nu, A.du, nb * nu * sizeof(double), hipMemcpyDeviceToHost, st));
         if (dx) HIP_TRY(hipMemcpyAsync(dx + b0 * nx, A.dx, nb * nx * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
+        return (int)CFNMPC_OK;
+    }));
     if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
     return CFNMPC_OK;
 }
@@ -1436,6 +1504,183 @@ int cfnmpc_get_sens_active(cfnmpc_solver* s, signed char* act, int on_device, vo
     if (!s || !act || !s->sens_valid) return CFNMPC_EINVAL;
     DeviceGuard dg(s->device);
     return copy_out({{act, s->sens.mask, (size_t)s->P.B * s->P.N * 4}}, on_device, (hipStream_t)stream);
+}
+
+// ---- uncertainty propagation and robust input-bound tightening -----------------------------------
+namespace {
+// one table of cfnmpc_set_uncertainty: allocated at the first array, filled by one put kernel on `st`
+int unc_put_table(cfnmpc_solver* s, const double* src, bool host, size_t per, size_t blk, double** tab, hipStream_t st) {
+    const size_t B = s->P.B, n = B * per;
+    if (!*tab) RC_TRY(dev_alloc(s, tab, (size_t)s->P.NW * blk));   // (zero: the padding rows stay so)
+    const double* d = src;
+    if (host) {
+        if (!s->unc.stage) RC_TRY(dev_alloc(s, &s->unc.stage, B * 169));
+        HIP_TRY(hipMemcpyAsync(s->unc.stage, src, n * sizeof(double), hipMemcpyHostToDevice, st));
+        d = s->unc.stage;
+    }
+    if (per == 169) cfn::launch_unc_put_sym((int)B, d, *tab, st);
+    else cfn::launch_unc_put_gain((int)B, d, *tab, st);
+    HIP_TRY(hipGetLastError());
+    return CFNMPC_OK;
+}
+cfn::UncArgs unc_args(const cfnmpc_solver* s) {
+    cfn::UncArgs A{};
+    A.S0 = s->unc.has_S0 ? s->unc.S0 : nullptr;
+    A.W = s->unc.has_W ? s->unc.W : nullptr;
+    A.Ku = s->unc.gain_mode == CFNMPC_UNC_GAIN_USER ? s->unc.K : nullptr;
+    A.status = s->sens_src == 2 ? s->sqp.status : s->P.status;
+    return A;
+}
+}  // namespace
+
+}  // extern "C"
+namespace cfn {
+bool unc_backoff_valid(const cfnmpc_solver* s) { return s && s->unc.beta_valid; }
+}
+extern "C" {
+
+int cfnmpc_set_uncertainty(cfnmpc_solver* s, const double* Sigma0, const double* W, int on_device, void* stream) {
+    if (!s) return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t B = s->P.B;
+    const bool host = is_host(on_device);
+    // host arrays are validated as a whole before anything changes; device arrays are taken as they are
+    if (host && ((Sigma0 && !cfn::unc_sym_ok(Sigma0, B)) || (W && !cfn::unc_sym_ok(W, B)))) return CFNMPC_EINVAL;
+    // new inputs: the covariance getter would sweep with them while the stored beta is the old evaluation's -- it waits for the
+    // next cfnmpc_eval_uncertainty (the backoff itself stays valid: it is what cfnmpc_tighten_box applies)
+    s->unc.current = false;
+    // each table's flag follows its own put, so that a failure of the second put (allocation, copy) leaves tables and flags agreeing
+    s->unc.has_S0 = false;
+    if (Sigma0) {
+        RC_TRY(unc_put_table(s, Sigma0, host, 169, cfn::SZ_P, &s->unc.S0, st));
+        s->unc.has_S0 = true;
+        if (host && W) HIP_TRY(hipStreamSynchronize(st));   // (the staging buffer is reused)
+    }
+    s->unc.has_W = false;
+    if (W) {
+        RC_TRY(unc_put_table(s, W, host, 169, cfn::SZ_P, &s->unc.W, st));
+        s->unc.has_W = true;
+    }
+    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
+
+int cfnmpc_set_uncertainty_gain(cfnmpc_solver* s, int mode, const double* K, int on_device, void* stream) {
+    if (!s || (mode != CFNMPC_UNC_GAIN_RICCATI && mode != CFNMPC_UNC_GAIN_USER)) return CFNMPC_EINVAL;
+    if (mode == CFNMPC_UNC_GAIN_RICCATI) { s->unc.gain_mode = mode; s->unc.current = false; return CFNMPC_OK; }
+    if (!K) return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)s->P.B * 52;
+    const bool host = is_host(on_device);
+    if (host)
+        for (size_t i = 0; i < n; i++) if (!std::isfinite(K[i])) return CFNMPC_EINVAL;
+    s->unc.current = false;   // (as cfnmpc_set_uncertainty)
+    RC_TRY(unc_put_table(s, K, host, 52, cfn::SZ_K, &s->unc.K, st));
+    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
+    s->unc.gain_mode = mode;
+    return CFNMPC_OK;
+}
+
+int cfnmpc_eval_uncertainty(cfnmpc_solver* s, void* stream) {
+    if (!s) return CFNMPC_EINVAL;
+    // partial condensing and the fused start solve (start_solve = 2) write no home blocks / gains; the blocks must be the last
+    // QP's: a solve, and no change of its data since
+    if (s->P.cond_N2 || s->P.fused == 1 || s->sens_src == 0 || s->unc.inputs_moved) return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    if (!s->unc.beta) RC_TRY(dev_alloc(s, &s->unc.beta, (size_t)s->P.NW * 4 * s->P.N * 4));
+    cfn::UncArgs A = unc_args(s);
+    A.beta = s->unc.beta;
+    A.s0 = 0; A.ns = s->P.N; A.b0 = 0; A.nb = s->P.B;
+    s->unc.beta_valid = false;
+    cfn::launch_unc_prop(s->P, A, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    s->unc.beta_valid = true;
+    s->unc.current = true;
+    return CFNMPC_OK;
+}
+
+int cfnmpc_get_backoff(cfnmpc_solver* s, double* beta, int on_device, void* stream) {
+    if (!s || !beta || !s->unc.beta_valid) return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    return get_field(s, beta, on_device, s->P.N, 4, 0, 0, s->P.N, s->unc.beta, (hipStream_t)stream);
+}
+
+int cfnmpc_get_uncertainty(cfnmpc_solver* s, int stage, int n_stages, double* Sigma, double* std_x, int on_device, void* stream) {
+    if (!s || !s->unc.current) return CFNMPC_EINVAL;
+    const int N = s->P.N;
+    if (stage < 0 || n_stages < 1 || (long)stage + n_stages > N + 1 || (!Sigma && !std_x)) return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    hipStream_t st = (hipStream_t)stream;
+    cfn::UncArgs A = unc_args(s);
+    A.s0 = stage;
+    A.ns = n_stages;
+    const size_t B = s->P.B, ng = Sigma ? (size_t)n_stages * 169 : 0, nd = std_x ? (size_t)n_stages * 13 : 0;
+    if (!is_host(on_device)) {
+        A.Sig = Sigma; A.sd = std_x; A.b0 = 0; A.nb = (int)B;
+        cfn::launch_unc_prop(s->P, A, st);
+        HIP_TRY(hipGetLastError());
+        return CFNMPC_OK;
+    }
+    // host arrays: rows in chunks of whole wavefronts through the staging buffer of the sensitivities' host reads
+    RC_TRY(host_row_chunks(s, ng + nd, [&](size_t b0, size_t nb, double* stage) {
+        A.b0 = (int)b0; A.nb = (int)nb;
+        A.Sig = Sigma ? stage : nullptr;
+        A.sd = std_x ? stage + nb * ng : nullptr;
+        cfn::launch_unc_prop(s->P, A, st);
+        HIP_TRY(hipGetLastError());
+        if (Sigma) HIP_TRY(hipMemcpyAsync(Sigma + b0 * ng, A.Sig, nb * ng * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (std_x) HIP_TRY(hipMemcpyAsync(std_x + b0 * nd, A.sd, nb * nd * sizeof(double), hipMemcpyDeviceToHost, st));
+        return (int)CFNMPC_OK;
+    }));
+    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
+
+int cfnmpc_tighten_box(cfnmpc_solver* s, double gamma, double min_width, int* n_clamped, int on_device, void* stream) {
+    if (!s || !s->unc.beta_valid || !std::isfinite(gamma) || !(gamma >= 0.0) || !(min_width > 0.0) || !(min_width <= 1.0))
+        return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    cfn::Params& P = s->P;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t B = P.B;
+    if (!s->unc.ncl) RC_TRY(dev_alloc(s, &s->unc.ncl, B));
+    if (gamma == 0.0) {   // the nominal box back in force (the scalar route again if it is scalar)
+        RC_TRY(untighten(s, st));
+        HIP_TRY(hipMemsetAsync(s->unc.ncl, 0, B * sizeof(int), st));
+    } else {
+        RC_TRY(ensure_box_blocks(s));
+        const size_t cnt = (size_t)P.NW * 4 * P.N * 4;
+        if (!s->unc.tight) {   // the box in force is the nominal one: remember it
+            s->unc.nom_stages = P.lbs != nullptr;
+            if (s->unc.nom_stages) {
+                if (!s->unc.nom_lb) RC_TRY(dev_alloc(s, &s->unc.nom_lb, cnt));
+                if (!s->unc.nom_ub) RC_TRY(dev_alloc(s, &s->unc.nom_ub, cnt));
+                HIP_TRY(hipMemcpyAsync(s->unc.nom_lb, P.lbs, cnt * sizeof(double), hipMemcpyDeviceToDevice, st));
+                HIP_TRY(hipMemcpyAsync(s->unc.nom_ub, P.ubs, cnt * sizeof(double), hipMemcpyDeviceToDevice, st));
+            }
+        }
+        cfn::TightenArgs T{};
+        T.nlb = s->unc.nom_stages ? s->unc.nom_lb : nullptr;
+        T.nub = s->unc.nom_stages ? s->unc.nom_ub : nullptr;
+        T.u_min = P.u_min; T.u_max = P.u_max;
+        T.beta = s->unc.beta;
+        T.gamma = gamma; T.min_width = min_width;
+        T.lbs = P.lbs ? P.lbs : s->lbs_keep; T.ubs = P.ubs ? P.ubs : s->ubs_keep;
+        T.clbs = P.clbs; T.cubs = P.cubs;
+        T.ncl = s->unc.ncl;
+        cfn::launch_unc_tighten(P, T, st);
+        HIP_TRY(hipGetLastError());
+        // new values over old ones in place: captured step graphs keep replaying; only the switch from the scalar route
+        // invalidates them (as cfnmpc_set_box_stages does)
+        if (!P.lbs) { P.lbs = s->lbs_keep; P.ubs = s->ubs_keep; invalidate_graphs(s); }
+        s->unc.tight = true;
+        invalidate_sens(s);   // (the box is part of the QP's data)
+    }
+    if (n_clamped) return copy_out({{n_clamped, s->unc.ncl, B * sizeof(int)}}, on_device, st);
+    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
 }
 
 namespace {

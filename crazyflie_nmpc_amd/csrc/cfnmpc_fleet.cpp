@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <map>
 #include <vector>
 
@@ -451,4 +453,63 @@ int cfnmpc_fleet_get_sens_x0(cfnmpc_fleet* f, int stage, int n_stages, double* d
                       [&](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_get_sens_x0(b.s, stage, n_stages, p.d(0), p.d(1), mode, st); });
 }
 
+// ---- uncertainty propagation and bound tightening (include/cfnmpc.h: cfnmpc_eval_uncertainty) --------
+// host arrays are validated as a whole first: a bad matrix leaves every bucket unchanged
+int cfnmpc_fleet_set_uncertainty(cfnmpc_fleet* f, const double* Sigma0, const double* W, int on_device, void* stream) {
+    if (!f) return CFNMPC_EINVAL;
+    if (cfn::is_host(on_device) && ((Sigma0 && !cfn::unc_sym_ok(Sigma0, (size_t)f->B)) || (W && !cfn::unc_sym_ok(W, (size_t)f->B))))
+        return CFNMPC_EINVAL;
+    return fleet_write(f, on_device, stream, {col(Sigma0, 169), col(W, 169)},
+                       [](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_set_uncertainty(b.s, p.d(0), p.d(1), mode, st); });
+}
+
+int cfnmpc_fleet_set_uncertainty_gain(cfnmpc_fleet* f, int mode, const double* K, int on_device, void* stream) {
+    if (!f || (mode != CFNMPC_UNC_GAIN_RICCATI && mode != CFNMPC_UNC_GAIN_USER) || (mode == CFNMPC_UNC_GAIN_USER && !K)) return CFNMPC_EINVAL;
+    if (mode == CFNMPC_UNC_GAIN_RICCATI) K = nullptr;
+    if (K && cfn::is_host(on_device))
+        for (size_t i = 0; i < (size_t)f->B * 52; i++) if (!std::isfinite(K[i])) return CFNMPC_EINVAL;
+    return fleet_write(f, on_device, stream, {col(K, 52)},
+                       [&](Bucket& b, Staged p, int md, void* st) { return cfnmpc_set_uncertainty_gain(b.s, mode, p.d(0), md, st); });
+}
+
+int cfnmpc_fleet_eval_uncertainty(cfnmpc_fleet* f, void* stream) {
+    if (!f) return CFNMPC_EINVAL;
+    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) { return cfnmpc_eval_uncertainty(b.s, st); });
+}
+
+// beta [B][Nmax][4]: NaN behind a vehicle's own horizon (the whole array is filled first; all bits set is a NaN)
+int cfnmpc_fleet_get_backoff(cfnmpc_fleet* f, double* beta, int on_device, void* stream) {
+    if (!f || !beta || !cfn::fleet_backoff_valid(f)) return CFNMPC_EINVAL;   // (checked before the caller's array is touched)
+    const size_t bytes = (size_t)f->B * f->Nmax * 4 * sizeof(double);
+    if (cfn::is_host(on_device)) std::memset(beta, 0xff, bytes);
+    else {
+        cfn::DeviceGuard dg(f->device);
+        HIP_TRY(hipMemsetAsync(beta, 0xff, bytes, (hipStream_t)stream));
+    }
+    return fleet_read(f, on_device, stream, {col_stages(beta, 4)},
+                      [](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_get_backoff(b.s, p.d(0), mode, st); });
+}
+
+int cfnmpc_fleet_get_uncertainty(cfnmpc_fleet* f, int stage, int n_stages, double* Sigma, double* std_x, int on_device, void* stream) {
+    if (!f || stage < 0 || n_stages < 1 || (!Sigma && !std_x) || (long)stage + n_stages > f->Nmin + 1) return CFNMPC_EINVAL;
+    return fleet_read(f, on_device, stream, {col(Sigma, (size_t)n_stages * 169), col(std_x, (size_t)n_stages * 13)},
+                      [&](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_get_uncertainty(b.s, stage, n_stages, p.d(0), p.d(1), mode, st); });
+}
+
+int cfnmpc_fleet_tighten_box(cfnmpc_fleet* f, double gamma, double min_width, int* n_clamped, int on_device, void* stream) {
+    // (what a bucket would refuse is checked for all of them first: no bucket is tightened when another has no backoff)
+    if (!f || !cfn::fleet_backoff_valid(f) || !std::isfinite(gamma) || !(gamma >= 0.0) || !(min_width > 0.0) || !(min_width <= 1.0))
+        return CFNMPC_EINVAL;
+    return fleet_read(f, on_device, stream, {col(n_clamped, 1)},
+                      [&](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_tighten_box(b.s, gamma, min_width, p.i(0), mode, st); });
+}
+
 }  // extern "C"
+
+namespace cfn {
+bool fleet_backoff_valid(const cfnmpc_fleet* f) {
+    if (!f) return false;
+    for (const Bucket& b : f->bk) if (!unc_backoff_valid(b.s)) return false;
+    return true;
+}
+}  // namespace cfn

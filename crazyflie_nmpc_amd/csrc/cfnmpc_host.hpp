@@ -20,7 +20,13 @@
     } while (0)
 #define RC_TRY(x) do { int rc_ = (x); if (rc_ != CFNMPC_OK) return rc_; } while (0)
 
+struct cfnmpc_solver;
+struct cfnmpc_fleet;
 namespace cfn {
+// a stored backoff is there (cfnmpc_get_backoff / cfnmpc_tighten_box would accept): asked by the layers above BEFORE they touch
+// the caller's arrays
+bool unc_backoff_valid(const cfnmpc_solver* s);
+bool fleet_backoff_valid(const cfnmpc_fleet* f);
 
 // A solver, fleet or shard lives on the device that was current when it was created; every entry point that touches it makes
 // that device current for the duration of the call (a caller that drives several GPUs from one thread may have another one
@@ -38,6 +44,28 @@ struct DeviceGuard {
 
 // `on_device` argument: 0 host (synchronous), 2 host (enqueued only), anything else: device pointer
 inline bool is_host(int on_device) { return on_device == CFNMPC_ON_HOST || on_device == CFNMPC_ON_HOST_ASYNC; }
+
+// host arrays of cfnmpc_set_uncertainty, n matrices [13][13]: finite, symmetric to 1e-12 of the matrix' largest entry,
+// non-negative diagonal
+inline bool unc_sym_ok(const double* S, size_t n) {
+    for (size_t i = 0; i < n; i++) {
+        const double* m = S + i * 169;
+        double big = 0.0;
+        for (int e = 0; e < 169; e++) {
+            if (!(m[e] - m[e] == 0.0)) return false;   // (NaN, +-inf)
+            const double a = m[e] < 0.0 ? -m[e] : m[e];
+            if (a > big) big = a;
+        }
+        for (int r = 0; r < 13; r++) {
+            if (m[r * 14] < 0.0) return false;
+            for (int c = r + 1; c < 13; c++) {
+                const double d = m[r * 13 + c] - m[c * 13 + r];
+                if ((d < 0.0 ? -d : d) > 1e-12 * big) return false;
+            }
+        }
+    }
+    return true;
+}
 
 // the options of a creator: the caller's (ABI guard: the first field is the size the caller's filler saw -- read BEFORE the
 // struct is copied) or the defaults

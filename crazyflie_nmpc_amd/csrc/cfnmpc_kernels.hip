@@ -4451,3 +4451,4 @@ void launch_init_iterate(const Params& P, int mode, hipStream_t st) {
 }  // namespace cfn
 
 #include "cfnmpc_sens.hpp"
+#include "cfnmpc_unc.hpp"

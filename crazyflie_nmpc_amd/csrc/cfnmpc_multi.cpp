@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <numeric>
 #include <vector>
 
@@ -377,6 +379,51 @@ int cfnmpc_multi_get_sens_x0(cfnmpc_multi* m, int stage, int n_stages, double* d
     return multi_read(m, {col(du, (size_t)n_stages * 52), col(dx, (size_t)n_stages * 169)},
                       [&](Shard& s, Staged p, int mode) { return cfnmpc_get_sens_x0(s.s, stage, n_stages, p.d(0), p.d(1), mode, s.st); },
                       [&](Shard& s, Staged p, int mode) { return cfnmpc_fleet_get_sens_x0(s.f, stage, n_stages, p.d(0), p.d(1), mode, s.st); });
+}
+
+// ---- uncertainty propagation and bound tightening (host arrays over the whole fleet, caller's order; synchronous) ------------
+int cfnmpc_multi_set_uncertainty(cfnmpc_multi* m, const double* Sigma0, const double* W) {
+    if (!m) return CFNMPC_EINVAL;
+    if ((Sigma0 && !cfn::unc_sym_ok(Sigma0, (size_t)m->B)) || (W && !cfn::unc_sym_ok(W, (size_t)m->B))) return CFNMPC_EINVAL;   // (as a whole: no shard changes)
+    // (uniform shards: both arrays pass through ONE staging buffer per shard -- the solver orders the second put behind the first)
+    return multi_write(m, {col(Sigma0, 169), col(W, 169)},
+                       [](Shard& s, Staged p, int mode) { return cfnmpc_set_uncertainty(s.s, p.d(0), p.d(1), mode, s.st); },
+                       [](Shard& s, Staged p, int mode) { return cfnmpc_fleet_set_uncertainty(s.f, p.d(0), p.d(1), mode, s.st); });
+}
+
+int cfnmpc_multi_set_uncertainty_gain(cfnmpc_multi* m, int mode, const double* K) {
+    if (!m || (mode != CFNMPC_UNC_GAIN_RICCATI && mode != CFNMPC_UNC_GAIN_USER) || (mode == CFNMPC_UNC_GAIN_USER && !K)) return CFNMPC_EINVAL;
+    if (mode == CFNMPC_UNC_GAIN_RICCATI) K = nullptr;
+    if (K) for (size_t i = 0; i < (size_t)m->B * 52; i++) if (!std::isfinite(K[i])) return CFNMPC_EINVAL;
+    return multi_write(m, {col(K, 52)},
+                       [&](Shard& s, Staged p, int md) { return cfnmpc_set_uncertainty_gain(s.s, mode, p.d(0), md, s.st); },
+                       [&](Shard& s, Staged p, int md) { return cfnmpc_fleet_set_uncertainty_gain(s.f, mode, p.d(0), md, s.st); });
+}
+
+int cfnmpc_multi_eval_uncertainty(cfnmpc_multi* m) {
+    if (!m) return CFNMPC_EINVAL;
+    return for_shards(m, [](Shard& s) { return cfnmpc_eval_uncertainty(s.s, s.st); },
+                      [](Shard& s) { return cfnmpc_fleet_eval_uncertainty(s.f, s.st); }, true);
+}
+
+// beta [B][N][4] (N: the longest horizon): NaN behind a vehicle's own horizon (filled first; all bits set is a NaN)
+int cfnmpc_multi_get_backoff(cfnmpc_multi* m, double* beta) {
+    if (!m || !beta) return CFNMPC_EINVAL;
+    for (const Shard& s : m->sh)   // (checked before the caller's array is touched)
+        if (m->mixed ? !cfn::fleet_backoff_valid(s.f) : !cfn::unc_backoff_valid(s.s)) return CFNMPC_EINVAL;
+    if (m->mixed) std::memset(beta, 0xff, (size_t)m->B * m->N * 4 * sizeof(double));
+    return multi_read(m, {col_stages(beta, 4)},
+                      [](Shard& s, Staged p, int mode) { return cfnmpc_get_backoff(s.s, p.d(0), mode, s.st); },
+                      [](Shard& s, Staged p, int mode) { return cfnmpc_fleet_get_backoff(s.f, p.d(0), mode, s.st); });
+}
+
+int cfnmpc_multi_tighten_box(cfnmpc_multi* m, double gamma, double min_width, int* n_clamped) {
+    if (!m) return CFNMPC_EINVAL;
+    for (const Shard& s : m->sh)   // (no shard is tightened when another has no backoff)
+        if (m->mixed ? !cfn::fleet_backoff_valid(s.f) : !cfn::unc_backoff_valid(s.s)) return CFNMPC_EINVAL;
+    return multi_read(m, {col(n_clamped, 1)},
+                      [&](Shard& s, Staged p, int mode) { return cfnmpc_tighten_box(s.s, gamma, min_width, p.i(0), mode, s.st); },
+                      [&](Shard& s, Staged p, int mode) { return cfnmpc_fleet_tighten_box(s.f, gamma, min_width, p.i(0), mode, s.st); });
 }
 
 }  // extern "C"

@@ -308,6 +308,29 @@ struct SensArgs {
 void launch_sens_eval(const Params& P, const SensArgs& A, hipStream_t st);
 // forward propagation for the rows [A.b0, A.b0 + A.nb) into A.du / A.dx
 void launch_sens_fwd(const Params& P, const SensArgs& A, hipStream_t st);
+// uncertainty propagation and robust input-bound tightening (cfnmpc_eval_uncertainty / cfnmpc_tighten_box; kernels:
+// cfnmpc_unc.hpp): buffers owned by the solver, allocated at the first call that needs them
+struct UncArgs {
+    const double *S0, *W;   // Sigma_0 / W tables, a row-distributed 13 x 13 per instance (SZ_P per block, internal order); NULL: zero
+    double* Ku;             // user gain in KR's block layout with one stage per block (SZ_K per block); NULL: the home gains KR
+    double* beta;           // backoffs in the home 4-vector layout (Params.v4b), N stages; NULL: not written (the getter's sweep)
+    const int* status;      // [B] status of the last solve (4: NaN outputs)
+    double *Sig, *sd;       // [nb][ns][13][13], [nb][ns][13] (either may be NULL): rows [b0, b0 + nb), stages [s0, s0 + ns)
+    int s0, ns, b0, nb;
+};
+void launch_unc_prop(const Params& P, const UncArgs& A, hipStream_t st);
+// the caller's [B][13][13] / [B][4][13] arrays (public order) -> the tables of UncArgs
+void launch_unc_put_sym(int B, const double* src, double* tab, hipStream_t st);
+void launch_unc_put_gain(int B, const double* src, double* tab, hipStream_t st);
+struct TightenArgs {
+    const double *nlb, *nub;   // nominal per-stage box in the home 4-vector layout; NULL: the scalar box u_min / u_max below
+    double u_min, u_max;
+    const double* beta;        // UncArgs.beta
+    double gamma, min_width;
+    double *lbs, *ubs, *clbs, *cubs;   // the per-stage box arrays in force and their compact copies (all in the home layout)
+    int* ncl;                  // [B] clamped entries per instance (cleared by the launch)
+};
+void launch_unc_tighten(const Params& P, const TightenArgs& A, hipStream_t st);
 // output stage of the reference node for the fleet (cmd_vel [B][4] doubles, motvel [B][4] int32 or NULL)
 void launch_postproc(const Params& P, double* cmd_vel, int* motvel, hipStream_t st);
 

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import NU, NX, NY
-from .solver import SQP_MODES, _arg, _check, _sqp_mode, default_opts, _launch_stream, _torch_device
+from .solver import SQP_MODES, UncertaintyCalls, _arg, _check, _sqp_mode, default_opts, _launch_stream, _torch_device
 from .synthetic import regulation_row
 
 
@@ -31,7 +31,10 @@ def _weight_rows(B, W, WN):
     return out
 
 
-class MixedHorizonFleet:
+class MixedHorizonFleet(UncertaintyCalls):
+    _unc_pre = "cfnmpc_fleet_"
+    _unc_N = property(lambda self: self.Nmax)
+
     def __init__(self, horizons, **opt_kw):
         self._L = _lib.lib()
         self.horizons = np.ascontiguousarray(horizons, dtype=np.int32)

@@ -217,6 +217,34 @@ class MultiGpuFleet:
                                                      dx.ctypes.data_as(C.c_void_p)), "cfnmpc_multi_get_sens_x0")
         return du, dx
 
+    # ---- uncertainty propagation and bound tightening (BatchSolver.set_uncertainty ...; host arrays over the whole fleet, synchronous;
+    # the full covariance is read through the shards' own solvers)
+    def set_uncertainty(self, Sigma0=None, W=None):
+        vp = self._C.c_void_p
+        a = None if Sigma0 is None else self._p(Sigma0, (self.B, 13, 13))
+        b = None if W is None else self._p(W, (self.B, 13, 13))
+        self._check(self._L.cfnmpc_multi_set_uncertainty(self._h, a[1] if a else vp(0), b[1] if b else vp(0)), "cfnmpc_multi_set_uncertainty")
+
+    def set_uncertainty_gain(self, mode="riccati", K=None):
+        m = {"riccati": 0, "user": 1}.get(mode, mode)
+        a = None if K is None else self._p(K, (self.B, 4, 13))
+        self._check(self._L.cfnmpc_multi_set_uncertainty_gain(self._h, int(m), a[1] if a else self._C.c_void_p(0)), "cfnmpc_multi_set_uncertainty_gain")
+
+    def eval_uncertainty(self):
+        self._check(self._L.cfnmpc_multi_eval_uncertainty(self._h), "cfnmpc_multi_eval_uncertainty")
+
+    def backoff(self):
+        """-> beta [B][N][4] (mixed horizons: N the longest one, NaN behind a vehicle's own)"""
+        beta = np.empty((self.B, self.N, 4))
+        self._check(self._L.cfnmpc_multi_get_backoff(self._h, beta.ctypes.data_as(self._C.c_void_p)), "cfnmpc_multi_get_backoff")
+        return beta
+
+    def tighten_box(self, gamma, min_width=0.1):
+        """-> n_clamped [B] (int32)"""
+        n = np.empty(self.B, dtype=np.int32)
+        self._check(self._L.cfnmpc_multi_tighten_box(self._h, float(gamma), float(min_width), n.ctypes.data_as(self._C.c_void_p)), "cfnmpc_multi_tighten_box")
+        return n
+
     def get_u(self, stage):
         u = np.empty((self.B, 4))
         self._check(self._L.cfnmpc_multi_get_u(self._h, int(stage), u.ctypes.data_as(self._C.c_void_p)), "cfnmpc_multi_get_u")

@@ -144,7 +144,88 @@ def sens_x0_call(obj, N, fn, what, stage, n_stages, out_u, out_x):
     _check(fn(obj._h, stage, ns, pu, px, dev, st), what)
     return out_u, out_x
 
-class BatchSolver:
+UNC_GAIN_RICCATI, UNC_GAIN_USER = 0, 1
+
+
+class UncertaintyCalls:
+    """Uncertainty propagation and robust input-bound tightening (include/cfnmpc.h: cfnmpc_set_uncertainty ...; DESIGN.md section
+    5.21), shared by BatchSolver and MixedHorizonFleet: _unc_pre is the C prefix, _unc_N the stage stride of beta (N, or the
+    fleet's longest horizon; the covariance getter of a fleet reaches the shortest horizon, checked by the library)."""
+
+    def _unc_fn(self, name):
+        return getattr(self._L, self._unc_pre + name), self._unc_pre + name
+
+    def set_uncertainty(self, Sigma0=None, W=None, stream=None):
+        """Sigma0 [B][13][13]: covariance of the state estimate at stage 0; W [B][13][13]: covariance added per shooting
+        interval (public state order; numpy or device tensors; None: zero).  Host arrays must be finite, symmetric and have a
+        non-negative diagonal."""
+        fn, what = self._unc_fn("set_uncertainty")
+        if Sigma0 is not None and W is not None and _is_torch(Sigma0) != _is_torch(W):
+            raise ValueError("Sigma0 and W must both be host arrays or both device tensors")
+        ps, pw, dev, st, keep = None, None, 0, _launch_stream(stream, self._device), []
+        if Sigma0 is not None:
+            ps, dev, st, k = _arg(Sigma0, (self.B, NX, NX), device=self._device); keep.append(k)
+        if W is not None:
+            pw, dev, st, k = _arg(W, (self.B, NX, NX), device=self._device); keep.append(k)
+        if stream:
+            st = C.c_void_p(stream)
+        _check(fn(self._h, ps, pw, dev, st), what)
+
+    def set_uncertainty_gain(self, mode="riccati", K=None, stream=None):
+        """Feedback gain of the propagation, in du = -K dx: "riccati" (the gains of the last solve's start solve) or "user"
+        with one constant K [B][4][13] per instance (acados zoRO's fdbk_K_mat)."""
+        fn, what = self._unc_fn("set_uncertainty_gain")
+        m = {"riccati": UNC_GAIN_RICCATI, "user": UNC_GAIN_USER}.get(mode, mode)
+        pk, dev, st = None, 0, _launch_stream(stream, self._device)
+        if K is not None:
+            pk, dev, st, _k = _arg(K, (self.B, NU, NX), device=self._device)
+            if stream:
+                st = C.c_void_p(stream)
+        _check(fn(self._h, int(m), pk, dev, st), what)
+
+    def eval_uncertainty(self, stream=None):
+        """Propagates the covariance through the closed-loop linearisation of the last QP and keeps the backoffs (backoff())."""
+        fn, what = self._unc_fn("eval_uncertainty")
+        _check(fn(self._h, _launch_stream(stream, self._device)), what)
+
+    def backoff(self, out=None):
+        """-> beta [B][N][4]: 1-sigma standard deviation of the feedback's input correction (a fleet: [B][Nmax][4], NaN behind
+        a vehicle's own horizon)"""
+        fn, what = self._unc_fn("get_backoff")
+        shape = (self.B, self._unc_N, NU)
+        if out is None:
+            out = np.empty(shape)
+        p, dev, st, _k = _arg(out, shape, device=self._device)
+        _check(fn(self._h, p, dev, st), what)
+        return out
+
+    def uncertainty(self, stage=0, n_stages=None, want_sigma=True, want_std=True):
+        """-> (Sigma, std_x): the covariance [B][n][13][13] and the square roots of its diagonal [B][n][13] for the stages
+        [stage, stage + n_stages) (n_stages = None: that one stage, without the stage axis); host arrays, None where not wanted"""
+        fn, what = self._unc_fn("get_uncertainty")
+        ns = 1 if n_stages is None else int(n_stages)
+        sg = np.empty((self.B, ns, NX, NX)) if want_sigma else None
+        sd = np.empty((self.B, ns, NX)) if want_std else None
+        _check(fn(self._h, int(stage), ns, None if sg is None else sg.ctypes.data_as(C.c_void_p),
+                  None if sd is None else sd.ctypes.data_as(C.c_void_p), 0, _launch_stream(None, self._device)), what)
+        if n_stages is None:
+            sg = None if sg is None else sg[:, 0]
+            sd = None if sd is None else sd[:, 0]
+        return sg, sd
+
+    def tighten_box(self, gamma, min_width=0.1, stream=None):
+        """lb' = lb + t, ub' = ub - t with t = min(gamma beta, (1 - min_width)(ub - lb) / 2) on the nominal box, in force from
+        the next solve on; gamma = 0 puts the nominal box back.  -> n_clamped [B] (int32)"""
+        fn, what = self._unc_fn("tighten_box")
+        n = np.empty(self.B, dtype=np.int32)
+        _check(fn(self._h, float(gamma), float(min_width), n.ctypes.data_as(C.c_void_p), 0, _launch_stream(stream, self._device)), what)
+        return n
+
+
+class BatchSolver(UncertaintyCalls):
+    _unc_pre = "cfnmpc_"
+    _unc_N = property(lambda self: self.N)
+
     def __init__(self, batch: int, opts: Opts | None = None, **kw):
         self._L = _lib.lib()
         self.opts = opts if opts is not None else default_opts(**kw)

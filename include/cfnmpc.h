@@ -438,6 +438,52 @@ int cfnmpc_get_sens_x0(cfnmpc_solver *s, int stage, int n_stages, double *du /*[
                        double *dx /*[B][n_stages][13][13] or NULL*/, int on_device, void *stream);
 int cfnmpc_get_sens_active(cfnmpc_solver *s, signed char *act /*[B][N][4]*/, int on_device, void *stream);
 
+/* Uncertainty propagation and robust input-bound tightening (zero-order robust optimisation, acados' zoRO custom update;
+ * DESIGN.md section 5.21).  A state covariance is carried along the horizon through the closed-loop linearisation of the LAST QP
+ * (the "last QP" rule of cfnmpc_eval_sens_x0: its stored blocks A_k, B_k), and every input bound is backed off by a multiple of
+ * the standard deviation of the feedback's input correction.  All arrays are in the public state order.
+ *   Inputs per instance: Sigma_0 [13][13], symmetric, the covariance of the state estimate at stage 0; W [13][13], symmetric,
+ *     the covariance added per shooting interval.  NULL means zero.
+ *   Feedback gain K_k in du = -K_k dx (sign and layout of cfnmpc_debug_get_factor's K [B][N][4][13]):
+ *     CFNMPC_UNC_GAIN_RICCATI (default): the gains of the last solve's start solve (the feedback law of the unconstrained tail);
+ *     CFNMPC_UNC_GAIN_USER: one constant [4][13] per instance, K [B][4][13] (acados zoRO's fdbk_K_mat).
+ *   Recursion, with M_k = A_k - B_k K_k:   Sigma_{k+1} = M_k Sigma_k M_k' + W,  k = 0 .. N-1;
+ *     backoff beta_{k,a} = sqrt((K_k Sigma_k K_k')_aa), k = 0 .. N-1, a = 0 .. 3 (1 sigma; the tightening applies the multiple).
+ *     A row whose status is 4 gets NaN in Sigma, std_x and beta; the tightening leaves its box nominal.
+ *   Tightening: lb'_{k,a} = lb_{k,a} + t, ub'_{k,a} = ub_{k,a} - t with t = min(gamma beta_{k,a}, (1 - min_width)(ub - lb) / 2):
+ *     the tightened box keeps at least min_width of its nominal width and never inverts.  An equality entry (lb == ub) is left
+ *     untouched.  n_clamped [B]: per instance, the entries the clamp limited.
+ *   Nominal box: what cfnmpc_set_box or cfnmpc_set_box_stages last set; it is remembered, and every tightening starts from it,
+ *     never from a tightened one.  Tightened boxes are in force from the next solve on, as per-stage boxes (the kernels of
+ *     cfnmpc_set_box_stages).  gamma = 0, or a later cfnmpc_set_box / cfnmpc_set_box_stages, puts the then-current nominal box
+ *     back in force (the scalar route again if it is scalar).  New tightened values are written over old ones in place: captured
+ *     step graphs keep replaying; only a switch between the scalar and the per-stage route invalidates them.
+ *   cfnmpc_set_uncertainty / cfnmpc_set_uncertainty_gain: HOST arrays are validated (finite; Sigma_0 and W symmetric to 1e-12
+ *     of their largest entry with a non-negative diagonal; CFNMPC_EINVAL changes nothing); DEVICE arrays are taken as they are,
+ *     one put kernel on `stream` (the rule of cfnmpc_set_disturbance).
+ *   cfnmpc_eval_uncertainty: one sweep over [0, N) on `stream`, keeps beta.  Writes nothing that a solve reads.  CFNMPC_EINVAL:
+ *     no solve yet; any change of the QP's data since the last solve (whatever invalidates cfnmpc_eval_sens_x0, and set_x0 /
+ *     set_yref / set_yref_windows); cond_N2 > 0 or start_solve = 2 (no stored blocks).
+ *   cfnmpc_get_backoff: beta [B][N][4].  The stored beta stays valid until the next cfnmpc_eval_uncertainty,
+ *     cfnmpc_init_iterate or cfnmpc_set_iterate, so cfnmpc_tighten_box may come before or after the set_x0 of the next step.
+ *   cfnmpc_get_uncertainty: one sweep over [0, stage + n_stages) writes Sigma [B][n_stages][13][13] and std_x [B][n_stages][13]
+ *     (the square roots of its diagonal; either may be NULL, not both; stage + n_stages <= N + 1).  Nothing of Sigma is kept
+ *     between calls.  CFNMPC_EINVAL without an evaluation since the last solve or data change.  Host arrays go through the
+ *     staging buffer of cfnmpc_get_sens_x0, in chunks of rows.
+ *   cfnmpc_tighten_box: CFNMPC_EINVAL without a valid beta, for gamma < 0 and for min_width outside (0, 1].
+ * The buffers (tables, beta, nominal-box copy) are allocated at the first call that needs them; cfnmpc_workspace_bytes counts
+ * them from then on. */
+#define CFNMPC_UNC_GAIN_RICCATI 0
+#define CFNMPC_UNC_GAIN_USER 1
+int cfnmpc_set_uncertainty(cfnmpc_solver *s, const double *Sigma0 /*[B][13][13] or NULL*/, const double *W /*[B][13][13] or NULL*/,
+                           int on_device, void *stream);
+int cfnmpc_set_uncertainty_gain(cfnmpc_solver *s, int mode, const double *K /*[B][4][13], mode 1*/, int on_device, void *stream);
+int cfnmpc_eval_uncertainty(cfnmpc_solver *s, void *stream);
+int cfnmpc_get_backoff(cfnmpc_solver *s, double *beta /*[B][N][4]*/, int on_device, void *stream);
+int cfnmpc_get_uncertainty(cfnmpc_solver *s, int stage, int n_stages, double *Sigma /*[B][n_stages][13][13] or NULL*/,
+                           double *std_x /*[B][n_stages][13] or NULL*/, int on_device, void *stream);
+int cfnmpc_tighten_box(cfnmpc_solver *s, double gamma, double min_width, int *n_clamped /*[B] or NULL*/, int on_device, void *stream);
+
 /* NLP cost, KKT residuals, costates and reduced gradient at the CURRENT iterate w = (x_0..x_N, u_0..u_{N-1}) (DESIGN.md section
  * 5.16), from the data in force now and nothing else: x0, yref / yref_e, the uniform or per-instance weights times the cost
  * scaling (s, s_e), the scalar or per-stage box, the nominal or per-instance model parameters, erk_steps (Phi = that many RK4
@@ -613,6 +659,15 @@ int cfnmpc_fleet_get_sqp_ls_stats(cfnmpc_fleet *f, double *alpha, double *mu, in
 int cfnmpc_fleet_eval_sens_x0(cfnmpc_fleet *f, double act_tol, void *stream);
 int cfnmpc_fleet_get_sens_x0(cfnmpc_fleet *f, int stage, int n_stages, double *du /*[B][n_stages][4][13] or NULL*/,
                              double *dx /*[B][n_stages][13][13] or NULL*/, int on_device, void *stream);
+/* Uncertainty propagation and bound tightening on every bucket (cfnmpc_set_uncertainty ...), rows in the fleet's vehicle order.
+ * Host arrays are validated as a whole first.  beta has [B][Nmax][4] with NaN behind a vehicle's own horizon;
+ * cfnmpc_fleet_get_uncertainty's range is limited by the shortest horizon (stage + n_stages <= Nmin + 1). */
+int cfnmpc_fleet_set_uncertainty(cfnmpc_fleet *f, const double *Sigma0, const double *W, int on_device, void *stream);
+int cfnmpc_fleet_set_uncertainty_gain(cfnmpc_fleet *f, int mode, const double *K, int on_device, void *stream);
+int cfnmpc_fleet_eval_uncertainty(cfnmpc_fleet *f, void *stream);
+int cfnmpc_fleet_get_backoff(cfnmpc_fleet *f, double *beta /*[B][Nmax][4]*/, int on_device, void *stream);
+int cfnmpc_fleet_get_uncertainty(cfnmpc_fleet *f, int stage, int n_stages, double *Sigma, double *std_x, int on_device, void *stream);
+int cfnmpc_fleet_tighten_box(cfnmpc_fleet *f, double gamma, double min_width, int *n_clamped /*[B] or NULL*/, int on_device, void *stream);
 /* cfnmpc_eval_nlp (keep_multipliers = 0) on every bucket, cfnmpc_get_nlp_stats in the fleet's vehicle order: cost [B], res [B][3]
  * (host arrays, on_device 0 or 2, are filled synchronously).  The multipliers have one shape per horizon: evaluate and read them
  * through the bucket's solver (cfnmpc_fleet_bucket). */
@@ -676,6 +731,14 @@ int cfnmpc_multi_set_weights_batch(cfnmpc_multi *m, const double *W, const doubl
  * synchronous; for cfnmpc_multi_create_horizons the range is limited by the shortest horizon, as for a fleet. */
 int cfnmpc_multi_eval_sens_x0(cfnmpc_multi *m, double act_tol);
 int cfnmpc_multi_get_sens_x0(cfnmpc_multi *m, int stage, int n_stages, double *du /*host or NULL*/, double *dx /*host or NULL*/);
+/* Uncertainty propagation and bound tightening per shard (both create variants): host arrays of the whole fleet in the caller's
+ * order, synchronous, validated as a whole first; beta [B][N][4] (N: the longest horizon; NaN behind a vehicle's own).  The full
+ * covariance is read through the shards' solvers (cfnmpc_multi_shard / cfnmpc_multi_shard_fleet). */
+int cfnmpc_multi_set_uncertainty(cfnmpc_multi *m, const double *Sigma0, const double *W);
+int cfnmpc_multi_set_uncertainty_gain(cfnmpc_multi *m, int mode, const double *K);
+int cfnmpc_multi_eval_uncertainty(cfnmpc_multi *m);
+int cfnmpc_multi_get_backoff(cfnmpc_multi *m, double *beta /*[B][N][4] host*/);
+int cfnmpc_multi_tighten_box(cfnmpc_multi *m, double gamma, double min_width, int *n_clamped /*[B] host or NULL*/);
 /* cfnmpc_eval_nlp (keep_multipliers = 0) per shard and its results over the whole fleet (both create variants): host arrays in
  * the caller's order, synchronous */
 int cfnmpc_multi_eval_nlp(cfnmpc_multi *m);
