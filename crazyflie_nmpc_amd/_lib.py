@@ -39,6 +39,9 @@ SYMBOLS = [
     "cfnmpc_tighten_box", "cfnmpc_fleet_set_uncertainty", "cfnmpc_fleet_set_uncertainty_gain", "cfnmpc_fleet_eval_uncertainty",
     "cfnmpc_fleet_get_backoff", "cfnmpc_fleet_get_uncertainty", "cfnmpc_fleet_tighten_box", "cfnmpc_multi_set_uncertainty",
     "cfnmpc_multi_set_uncertainty_gain", "cfnmpc_multi_eval_uncertainty", "cfnmpc_multi_get_backoff", "cfnmpc_multi_tighten_box",
+    "cfnmpc_get_yref", "cfnmpc_set_poly_library", "cfnmpc_set_poly_assignment", "cfnmpc_set_yref_poly", "cfnmpc_eval_poly",
+    "cfnmpc_fleet_set_poly_library", "cfnmpc_fleet_set_poly_assignment", "cfnmpc_fleet_set_yref_poly", "cfnmpc_fleet_eval_poly",
+    "cfnmpc_multi_set_poly_library", "cfnmpc_multi_set_poly_assignment", "cfnmpc_multi_set_yref_poly",
 ]
 ABI_VERSION = 9   # CFNMPC_ABI_VERSION of the include/cfnmpc.h this binding was written against
 
@@ -128,6 +131,16 @@ def lib():
     L.cfnmpc_multi_eval_uncertainty.argtypes = [vp]
     L.cfnmpc_multi_get_backoff.argtypes = [vp, vp]
     L.cfnmpc_multi_tighten_box.argtypes = [vp, dbl, dbl, vp]
+    L.cfnmpc_get_yref.argtypes = [vp, vp, vp, i32, vp]
+    for pre in ("cfnmpc_", "cfnmpc_fleet_"):
+        getattr(L, pre + "set_poly_library").argtypes = [vp, vp, vp, i32, vp]
+        getattr(L, pre + "set_poly_assignment").argtypes = [vp, vp, vp, i32, vp]
+        getattr(L, pre + "set_yref_poly").argtypes = [vp, dbl, i32, vp]
+    L.cfnmpc_eval_poly.argtypes = [vp, dbl, i32, i32, vp, vp, i32, vp]
+    L.cfnmpc_fleet_eval_poly.argtypes = [vp, dbl, i32, vp, vp, i32, vp]
+    L.cfnmpc_multi_set_poly_library.argtypes = [vp, vp, vp, i32]
+    L.cfnmpc_multi_set_poly_assignment.argtypes = [vp, vp, vp]
+    L.cfnmpc_multi_set_yref_poly.argtypes = [vp, dbl, i32]
     L.cfnmpc_eval_nlp.argtypes = [vp, i32, vp]
     L.cfnmpc_get_nlp_stats.argtypes = [vp, vp, vp, i32, vp]
     L.cfnmpc_get_nlp_multipliers.argtypes = [vp, vp, vp, i32, vp]

@@ -113,6 +113,16 @@ struct cfnmpc_solver {
         double *nom_lb = nullptr, *nom_ub = nullptr;
         bool tight = false, nom_stages = false;
     } unc;
+    // device-side polynomial trajectory references (cfnmpc_set_poly_library / cfnmpc_set_yref_poly): the
+    // library tables (at their limits), the assignment [B] and the placement rows [B][6], allocated together at the first call
+    struct Poly {
+        double* pieces = nullptr;
+        int* first = nullptr;
+        int n_traj = 0;
+        int* traj = nullptr;
+        double* place = nullptr;
+        bool has_place = false;   // (NULL given: the identity placement for everybody)
+    } poly;
 };
 
 namespace {
@@ -223,10 +233,16 @@ int copy_out(std::initializer_list<Out> outs, int on_device, hipStream_t st) {
 template <typename F>
 int host_row_chunks(cfnmpc_solver* s, size_t per, F chunk) {
     const size_t B = s->P.B, cap_max = (size_t)1 << 25;
-    if (!s->sens_stage) {
-        const size_t want = std::min(B * (size_t)(s->P.N + 1) * 221, cap_max);
-        const int rc = dev_alloc(s, &s->sens_stage, want);
+    // (rows longer than the ranges the buffer was sized for -- cfnmpc_eval_poly over many stages: a buffer for 64 of them replaces
+    //  it; the old one stays with the solver until cfnmpc_free, a transfer in flight may still read it)
+    const size_t floor = per * std::min(B, (size_t)4);
+    if (!s->sens_stage || s->sens_stage_doubles < floor) {
+        const size_t want = std::max(std::min(B * (size_t)(s->P.N + 1) * 221, cap_max), std::min(per * std::min(B, (size_t)64), cap_max));
+        if (want < floor) return CFNMPC_ENOMEM;
+        double* buf = nullptr;
+        const int rc = dev_alloc(s, &buf, want);
         if (rc != CFNMPC_OK) return rc;
+        s->sens_stage = buf;
         s->sens_stage_doubles = want;
     }
     size_t rows = s->sens_stage_doubles / per;
@@ -617,6 +633,115 @@ int cfnmpc_set_yref_windows(cfnmpc_solver* s, const double* traj, int n_rows, in
     s->unc.inputs_moved = true;
     cfn::launch_windows(s->P, traj, n_rows > 0 ? n_rows : 0, mode, iter, des_xyz, uss, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
+    return CFNMPC_OK;
+}
+
+int cfnmpc_get_yref(cfnmpc_solver* s, double* yref, double* yref_e, int on_device, void* stream) {
+    if (!s || (!yref && !yref_e)) return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    hipStream_t st = (hipStream_t)stream;
+    // (two arrays through one staging buffer: the second layout kernel is ordered behind the first copy on the stream)
+    if (yref) RC_TRY(get_field(s, yref, is_host(on_device) && yref_e ? (int)CFNMPC_ON_HOST_ASYNC : on_device, s->P.N, 17, 1, 0, s->P.N, s->P.yref, st));
+    if (yref_e) RC_TRY(get_field(s, yref_e, on_device, 1, 13, 1, 0, 1, s->P.yref_e, st));
+    return CFNMPC_OK;
+}
+
+// ---- device-side polynomial trajectory references ----------------------------------------------------
+static_assert(CFNMPC_POLY_NC == 33 && CFNMPC_NPLACE == 6 && CFNMPC_NFLAT == 13, "polynomial reference rows");
+// the tables, the assignment (-1 everywhere) and the placement rows, allocated together at the first call of the feature
+static int ensure_poly(cfnmpc_solver* s) {
+    if (s->poly.traj) return CFNMPC_OK;
+    const size_t B = s->P.B;
+    RC_TRY(dev_alloc(s, &s->poly.pieces, (size_t)CFNMPC_POLY_MAX_PIECES * CFNMPC_POLY_NC));
+    RC_TRY(dev_alloc(s, &s->poly.first, (size_t)CFNMPC_POLY_MAX_TRAJ + 1));
+    RC_TRY(dev_alloc(s, &s->poly.place, B * CFNMPC_NPLACE));
+    int* t = nullptr;
+    RC_TRY(dev_alloc(s, &t, B));
+    HIP_TRY(hipMemset(t, 0xff, B * sizeof(int)));   // (-1)
+    HIP_TRY(hipStreamSynchronize(nullptr));          // (as in dev_alloc: the fill is complete before a stream writes)
+    s->poly.traj = t;
+    return CFNMPC_OK;
+}
+static cfn::PolyArgs poly_args(const cfnmpc_solver* s, double t, int flags) {
+    cfn::PolyArgs A{};
+    A.pieces = s->poly.pieces; A.first = s->poly.first; A.n_traj = s->poly.n_traj;
+    A.traj = s->poly.traj; A.place = s->poly.has_place ? s->poly.place : nullptr;
+    A.t = t; A.flags = flags;
+    return A;
+}
+
+int cfnmpc_set_poly_library(cfnmpc_solver* s, const double* pieces, const int* first, int n_traj, void* stream) {
+    if (!s || n_traj < 0) return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_traj == 0 || !pieces || !first) {   // clears the library: every vehicle is without a trajectory
+        s->poly.n_traj = 0;
+        if (s->poly.traj) { cfn::launch_poly_clamp_ids(s->P.B, 0, s->poly.traj, st); HIP_TRY(hipGetLastError()); }
+        return CFNMPC_OK;
+    }
+    if (!cfn::poly_library_ok(pieces, first, n_traj)) return CFNMPC_EINVAL;
+    RC_TRY(ensure_poly(s));
+    HIP_TRY(hipMemcpyAsync(s->poly.pieces, pieces, (size_t)first[n_traj] * CFNMPC_POLY_NC * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->poly.first, first, ((size_t)n_traj + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    cfn::launch_poly_clamp_ids(s->P.B, n_traj, s->poly.traj, st);   // (a smaller library: ids it no longer has -> -1)
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));   // (the caller's arrays may be temporaries)
+    s->poly.n_traj = n_traj;
+    return CFNMPC_OK;
+}
+
+int cfnmpc_set_poly_assignment(cfnmpc_solver* s, const int* traj, const double* place, int on_device, void* stream) {
+    if (!s || !traj) return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t B = s->P.B;
+    const bool host = is_host(on_device);
+    if (host && !cfn::poly_assignment_ok(traj, place, B, s->poly.n_traj)) return CFNMPC_EINVAL;
+    RC_TRY(ensure_poly(s));
+    const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    HIP_TRY(hipMemcpyAsync(s->poly.traj, traj, B * sizeof(int), kind, st));
+    if (place) HIP_TRY(hipMemcpyAsync(s->poly.place, place, B * CFNMPC_NPLACE * sizeof(double), kind, st));
+    s->poly.has_place = place != nullptr;
+    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
+
+int cfnmpc_set_yref_poly(cfnmpc_solver* s, double t, int flags, void* stream) {
+    if (!s || s->poly.n_traj == 0 || !std::isfinite(t) || (flags & ~(CFNMPC_POLY_LOOP | CFNMPC_POLY_KINEMATIC))) return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    s->unc.inputs_moved = true;
+    cfn::launch_poly_rows(s->P, poly_args(s, t, flags), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return CFNMPC_OK;
+}
+
+int cfnmpc_eval_poly(cfnmpc_solver* s, double t, int n_stages, int flags, double* flat, double* rows, int on_device, void* stream) {
+    if (!s || s->poly.n_traj == 0 || !std::isfinite(t) || (flags & ~(CFNMPC_POLY_LOOP | CFNMPC_POLY_KINEMATIC)) || n_stages < 1 ||
+        n_stages > (1 << 20) || (!flat && !rows))
+        return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    hipStream_t st = (hipStream_t)stream;
+    cfn::PolyArgs A = poly_args(s, t, flags);
+    A.ns = n_stages;
+    const size_t B = s->P.B, nf = flat ? (size_t)n_stages * CFNMPC_NFLAT : 0, nr = rows ? (size_t)n_stages * 17 : 0;
+    if (!is_host(on_device)) {
+        A.flat = flat; A.rows = rows; A.b0 = 0; A.nb = (int)B;
+        cfn::launch_poly_eval(s->P, A, st);
+        HIP_TRY(hipGetLastError());
+        return CFNMPC_OK;
+    }
+    // host arrays: rows in chunks through the staging buffer (host_row_chunks)
+    RC_TRY(host_row_chunks(s, nf + nr, [&](size_t b0, size_t nb, double* stage) {
+        A.b0 = (int)b0; A.nb = (int)nb;
+        A.flat = flat ? stage : nullptr;
+        A.rows = rows ? stage + nb * nf : nullptr;
+        cfn::launch_poly_eval(s->P, A, st);
+        HIP_TRY(hipGetLastError());
+        if (flat) HIP_TRY(hipMemcpyAsync(flat + b0 * nf, A.flat, nb * nf * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (rows) HIP_TRY(hipMemcpyAsync(rows + b0 * nr, A.rows, nb * nr * sizeof(double), hipMemcpyDeviceToHost, st));
+        return (int)CFNMPC_OK;
+    }));
+    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));
     return CFNMPC_OK;
 }
 
@@ -1536,6 +1661,7 @@ cfn::UncArgs unc_args(const cfnmpc_solver* s) {
 }  // extern "C"
 namespace cfn {
 bool unc_backoff_valid(const cfnmpc_solver* s) { return s && s->unc.beta_valid; }
+int poly_n_traj(const cfnmpc_solver* s) { return s ? s->poly.n_traj : 0; }
 }
 extern "C" {
 

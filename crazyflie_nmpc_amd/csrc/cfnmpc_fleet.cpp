@@ -504,9 +504,49 @@ int cfnmpc_fleet_tighten_box(cfnmpc_fleet* f, double gamma, double min_width, in
                       [&](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_tighten_box(b.s, gamma, min_width, p.i(0), mode, st); });
 }
 
+// ---- device-side polynomial trajectory references (include/cfnmpc.h: cfnmpc_set_yref_poly) ------------
+// the library to every bucket (validated first: a bad table leaves every bucket unchanged)
+int cfnmpc_fleet_set_poly_library(cfnmpc_fleet* f, const double* pieces, const int* first, int n_traj, void* stream) {
+    if (!f || n_traj < 0) return CFNMPC_EINVAL;
+    if (n_traj > 0 && pieces && first && !cfn::poly_library_ok(pieces, first, n_traj)) return CFNMPC_EINVAL;
+    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) { return cfnmpc_set_poly_library(b.s, pieces, first, n_traj, st); });
+}
+
+// traj [B], place [B][6] or NULL in the fleet's vehicle order; host arrays are validated as a whole first
+int cfnmpc_fleet_set_poly_assignment(cfnmpc_fleet* f, const int* traj, const double* place, int on_device, void* stream) {
+    if (!f || !traj) return CFNMPC_EINVAL;
+    if (cfn::is_host(on_device) && !cfn::poly_assignment_ok(traj, place, (size_t)f->B, cfn::fleet_poly_n_traj(f))) return CFNMPC_EINVAL;
+    return fleet_write(f, on_device, stream, {col(traj, 1), col(place, CFNMPC_NPLACE)},
+                       [](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_set_poly_assignment(b.s, p.i(0), p.d(1), mode, st); });
+}
+
+// every bucket writes its own N + 1 rows at the shared t and dt
+int cfnmpc_fleet_set_yref_poly(cfnmpc_fleet* f, double t, int flags, void* stream) {
+    if (!f || cfn::fleet_poly_n_traj(f) == 0) return CFNMPC_EINVAL;   // (no bucket has written when the call is refused)
+    return on_buckets(f, (hipStream_t)stream, [&](Bucket& b, hipStream_t st) { return cfnmpc_set_yref_poly(b.s, t, flags, st); });
+}
+
+// flat [B][Nmax][13], rows [B][Nmax][17]: every vehicle's own N stage rows, NaN behind its horizon (the arrays are filled first;
+// all bits set is a NaN)
+int cfnmpc_fleet_eval_poly(cfnmpc_fleet* f, double t, int flags, double* flat, double* rows, int on_device, void* stream) {
+    if (!f || cfn::fleet_poly_n_traj(f) == 0 || (!flat && !rows)) return CFNMPC_EINVAL;
+    const size_t nf = (size_t)f->B * f->Nmax * CFNMPC_NFLAT * sizeof(double), nr = (size_t)f->B * f->Nmax * 17 * sizeof(double);
+    if (cfn::is_host(on_device)) {
+        if (flat) std::memset(flat, 0xff, nf);
+        if (rows) std::memset(rows, 0xff, nr);
+    } else {
+        cfn::DeviceGuard dg(f->device);
+        if (flat) HIP_TRY(hipMemsetAsync(flat, 0xff, nf, (hipStream_t)stream));
+        if (rows) HIP_TRY(hipMemsetAsync(rows, 0xff, nr, (hipStream_t)stream));
+    }
+    return fleet_read(f, on_device, stream, {col_stages(flat, CFNMPC_NFLAT), col_stages(rows, 17)},
+                      [&](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_eval_poly(b.s, t, b.N, flags, p.d(0), p.d(1), mode, st); });
+}
+
 }  // extern "C"
 
 namespace cfn {
+int fleet_poly_n_traj(const cfnmpc_fleet* f) { return f && !f->bk.empty() ? poly_n_traj(f->bk[0].s) : 0; }
 bool fleet_backoff_valid(const cfnmpc_fleet* f) {
     if (!f) return false;
     for (const Bucket& b : f->bk) if (!unc_backoff_valid(b.s)) return false;

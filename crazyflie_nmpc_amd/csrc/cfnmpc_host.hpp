@@ -67,6 +67,32 @@ inline bool unc_sym_ok(const double* S, size_t n) {
     return true;
 }
 
+// host arrays of cfnmpc_set_poly_library: every number finite, every duration > 0, first[0] = 0 and strictly increasing, within
+// the limits of include/cfnmpc.h
+inline bool poly_library_ok(const double* pieces, const int* first, int n_traj) {
+    if (n_traj < 1 || n_traj > CFNMPC_POLY_MAX_TRAJ || first[0] != 0) return false;
+    for (int j = 0; j < n_traj; j++) if (first[j + 1] <= first[j] || first[j + 1] > CFNMPC_POLY_MAX_PIECES) return false;
+    const size_t n = (size_t)first[n_traj] * CFNMPC_POLY_NC;
+    for (size_t i = 0; i < n; i++) {
+        if (!(pieces[i] - pieces[i] == 0.0)) return false;   // (NaN, +-inf)
+        if (i % CFNMPC_POLY_NC == 0 && !(pieces[i] > 0.0)) return false;
+    }
+    return true;
+}
+// host arrays of cfnmpc_set_poly_assignment for n vehicles: id in [-1, n_traj), time_scale finite and > 0, the rest finite
+inline bool poly_assignment_ok(const int* traj, const double* place, size_t n, int n_traj) {
+    for (size_t i = 0; i < n; i++) if (traj[i] < -1 || traj[i] >= n_traj) return false;
+    if (place)
+        for (size_t i = 0; i < n * CFNMPC_NPLACE; i++) {
+            if (!(place[i] - place[i] == 0.0)) return false;
+            if (i % CFNMPC_NPLACE == 1 && !(place[i] > 0.0)) return false;
+        }
+    return true;
+}
+// trajectories in the solver's library (0: none); a fleet's buckets all hold the same one
+int poly_n_traj(const cfnmpc_solver* s);
+int fleet_poly_n_traj(const cfnmpc_fleet* f);
+
 // the options of a creator: the caller's (ABI guard: the first field is the size the caller's filler saw -- read BEFORE the
 // struct is copied) or the defaults
 inline int take_opts(const cfnmpc_opts* opts, cfnmpc_opts* o) {

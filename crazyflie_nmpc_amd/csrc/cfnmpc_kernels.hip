@@ -4452,3 +4452,4 @@ void launch_init_iterate(const Params& P, int mode, hipStream_t st) {
 
 #include "cfnmpc_sens.hpp"
 #include "cfnmpc_unc.hpp"
+#include "cfnmpc_poly.hpp"

@@ -426,4 +426,29 @@ int cfnmpc_multi_tighten_box(cfnmpc_multi* m, double gamma, double min_width, in
                       [&](Shard& s, Staged p, int mode) { return cfnmpc_fleet_tighten_box(s.f, gamma, min_width, p.i(0), mode, s.st); });
 }
 
+// ---- device-side polynomial trajectory references (per shard; host arrays over the whole fleet, caller's order) ----------------
+int cfnmpc_multi_set_poly_library(cfnmpc_multi* m, const double* pieces, const int* first, int n_traj) {
+    if (!m || n_traj < 0) return CFNMPC_EINVAL;
+    if (n_traj > 0 && pieces && first && !cfn::poly_library_ok(pieces, first, n_traj)) return CFNMPC_EINVAL;   // (as a whole: no shard changes)
+    return for_shards(m, [&](Shard& s) { return cfnmpc_set_poly_library(s.s, pieces, first, n_traj, s.st); },
+                      [&](Shard& s) { return cfnmpc_fleet_set_poly_library(s.f, pieces, first, n_traj, s.st); }, true);
+}
+
+int cfnmpc_multi_set_poly_assignment(cfnmpc_multi* m, const int* traj, const double* place) {
+    if (!m || !traj || m->sh.empty()) return CFNMPC_EINVAL;
+    const int n_traj = m->mixed ? cfn::fleet_poly_n_traj(m->sh[0].f) : cfn::poly_n_traj(m->sh[0].s);
+    if (!cfn::poly_assignment_ok(traj, place, (size_t)m->B, n_traj)) return CFNMPC_EINVAL;   // (as a whole: no shard changes)
+    return multi_write(m, {col(traj, 1), col(place, CFNMPC_NPLACE)},
+                       [](Shard& s, Staged p, int mode) { return cfnmpc_set_poly_assignment(s.s, p.i(0), p.d(1), mode, s.st); },
+                       [](Shard& s, Staged p, int mode) { return cfnmpc_fleet_set_poly_assignment(s.f, p.i(0), p.d(1), mode, s.st); });
+}
+
+// asynchronous on every shard's stream, like cfnmpc_multi_solve
+int cfnmpc_multi_set_yref_poly(cfnmpc_multi* m, double t, int flags) {
+    if (!m || m->sh.empty()) return CFNMPC_EINVAL;
+    if ((m->mixed ? cfn::fleet_poly_n_traj(m->sh[0].f) : cfn::poly_n_traj(m->sh[0].s)) == 0) return CFNMPC_EINVAL;
+    return for_shards(m, [&](Shard& s) { return cfnmpc_set_yref_poly(s.s, t, flags, s.st); },
+                      [&](Shard& s) { return cfnmpc_fleet_set_yref_poly(s.f, t, flags, s.st); });
+}
+
 }  // extern "C"

@@ -331,6 +331,24 @@ struct TightenArgs {
     int* ncl;                  // [B] clamped entries per instance (cleared by the launch)
 };
 void launch_unc_tighten(const Params& P, const TightenArgs& A, hipStream_t st);
+// device-side polynomial trajectory references (cfnmpc_set_yref_poly / cfnmpc_eval_poly; kernels: cfnmpc_poly.hpp, DESIGN.md
+// section 5.22): the library, the assignment and the placement rows are owned by the solver, allocated at the first call of the
+// feature (not part of Params: no RTI kernel sees them)
+struct PolyArgs {
+    const double* pieces;   // [pieces][33]: duration, x^0..x^7, y^0..y^7, z^0..z^7, yaw^0..yaw^7
+    const int* first;       // [n_traj + 1]: trajectory j owns the pieces [first[j], first[j + 1])
+    int n_traj;
+    const int* traj;        // [B] trajectory of every instance; outside [0, n_traj): none
+    const double* place;    // [B][6] t_start, time_scale, ox, oy, oz, yaw0; NULL: [0, 1, 0, 0, 0, 0] for everybody
+    double t;               // fleet time of row 0; row k is at t + k dt
+    int flags;              // CFNMPC_POLY_LOOP | CFNMPC_POLY_KINEMATIC
+    int ns, kchunk;         // rows per instance (N + 1 for the windows), rows per workgroup (set by the launch)
+    double *flat, *rows;    // cfnmpc_eval_poly: [nb][ns][13], [nb][ns][17] (either may be NULL) for the instances [b0, b0 + nb)
+    int b0, nb;
+};
+void launch_poly_rows(const Params& P, PolyArgs A, hipStream_t st);   // every assigned instance's window -> P.yref, P.yref_e
+void launch_poly_eval(const Params& P, PolyArgs A, hipStream_t st);   // -> A.flat / A.rows
+void launch_poly_clamp_ids(int B, int n_traj, int* traj, hipStream_t st);   // ids outside [0, n_traj) -> -1
 // output stage of the reference node for the fleet (cmd_vel [B][4] doubles, motvel [B][4] int32 or NULL)
 void launch_postproc(const Params& P, double* cmd_vel, int* motvel, hipStream_t st);
 

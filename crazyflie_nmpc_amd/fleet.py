@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import NU, NX, NY
-from .solver import SQP_MODES, UncertaintyCalls, _arg, _check, _sqp_mode, default_opts, _launch_stream, _torch_device
+from .solver import NFLAT, SQP_MODES, PolyCalls, UncertaintyCalls, _arg, _check, _sqp_mode, default_opts, _launch_stream, _torch_device
 from .synthetic import regulation_row
 
 
@@ -31,7 +31,7 @@ def _weight_rows(B, W, WN):
     return out
 
 
-class MixedHorizonFleet(UncertaintyCalls):
+class MixedHorizonFleet(UncertaintyCalls, PolyCalls):
     _unc_pre = "cfnmpc_fleet_"
     _unc_N = property(lambda self: self.Nmax)
 
@@ -101,6 +101,16 @@ class MixedHorizonFleet(UncertaintyCalls):
         if dev != deve:
             raise ValueError("yref and yref_e must live on the same side")
         _check(self._L.cfnmpc_fleet_set_yref(self._h, p, pe, dev, st), "cfnmpc_fleet_set_yref")
+
+    def eval_poly(self, t, flags=0, want_flat=True, want_rows=True):
+        """-> (flat [B][Nmax][13], rows [B][Nmax][17]): every vehicle's own N stage rows of set_yref_poly, NaN behind its
+        horizon and for vehicles without a trajectory; host arrays, None where not wanted"""
+        fl = np.empty((self.B, self.Nmax, NFLAT)) if want_flat else None
+        rw = np.empty((self.B, self.Nmax, NY)) if want_rows else None
+        _check(self._L.cfnmpc_fleet_eval_poly(self._h, float(t), int(flags), None if fl is None else fl.ctypes.data_as(C.c_void_p),
+                                              None if rw is None else rw.ctypes.data_as(C.c_void_p), 0, _launch_stream(None, self._device)),
+               "cfnmpc_fleet_eval_poly")
+        return fl, rw
 
     def set_x0(self, x0):
         p, dev, st, _k = _arg(x0, (self.B, NX), device=self._device)

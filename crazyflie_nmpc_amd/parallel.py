@@ -158,6 +158,30 @@ class MultiGpuFleet:
         if rc != 0:
             raise ValueError(f"cfnmpc_multi_set_disturbance failed with code {rc}")
 
+    def set_poly_library(self, tables):
+        """polynomial trajectory library for every shard (BatchSolver.set_poly_library); None or an empty list clears it"""
+        from .solver import CfnmpcError, _poly_library_args
+        pp, pf, n, _keep = _poly_library_args(tables)
+        rc = self._L.cfnmpc_multi_set_poly_library(self._h, pp, pf, n)
+        if rc != 0:
+            raise CfnmpcError(f"cfnmpc_multi_set_poly_library failed with code {rc}")
+
+    def set_poly_assignment(self, traj, place=None):
+        """host arrays of the whole fleet: traj [B] int32 (-1 = none), place [B][6] or None"""
+        from .solver import CfnmpcError
+        _t, pt = self._p(traj, (self.B,), dtype=np.int32)
+        _pl, pl = (None, None) if place is None else self._p(place, (self.B, 6))
+        rc = self._L.cfnmpc_multi_set_poly_assignment(self._h, pt, pl)
+        if rc != 0:
+            raise CfnmpcError(f"cfnmpc_multi_set_poly_assignment failed with code {rc}")
+
+    def set_yref_poly(self, t, flags=0):
+        """every shard writes its vehicles' reference windows on the device (asynchronous, like solve)"""
+        from .solver import CfnmpcError
+        rc = self._L.cfnmpc_multi_set_yref_poly(self._h, float(t), int(flags))
+        if rc != 0:
+            raise CfnmpcError(f"cfnmpc_multi_set_yref_poly failed with code {rc}")
+
     def set_weights_batch(self, W=None, WN=None):
         """per-vehicle cost weights, host arrays W [B][17] / WN [B][13] of the whole fleet; None, None: uniform"""
         from .fleet import _weight_rows

@@ -222,7 +222,52 @@ class UncertaintyCalls:
         return n
 
 
-class BatchSolver(UncertaintyCalls):
+POLY_NC, NPLACE, NFLAT = 33, 6, 13
+POLY_LOOP, POLY_KINEMATIC = 1, 2
+
+
+def _poly_library_args(tables):
+    """list of [n_i][33] tables (or None / empty: clear) -> (pieces pointer, first pointer, n_traj, keepalive)"""
+    from .trajectories import poly_library
+    if not tables:
+        return None, None, 0, None
+    pieces, first = poly_library(tables)
+    return pieces.ctypes.data_as(C.c_void_p), first.ctypes.data_as(C.c_void_p), len(first) - 1, (pieces, first)
+
+
+class PolyCalls:
+    """Device-side polynomial trajectory references (include/cfnmpc.h: cfnmpc_set_poly_library ...), shared
+    by BatchSolver and MixedHorizonFleet (_unc_pre is the C prefix).  The host twin of the kernel is trajectories.poly_rows."""
+
+    def set_poly_library(self, tables, stream=None):
+        """tables: list of [n_i][33] coefficient tables in the crazyflie_demo CSV format (trajectories.load_poly_csv); the id of
+        a trajectory is its place in the list.  None or an empty list clears the library."""
+        pp, pf, n, _keep = _poly_library_args(tables)
+        _check(getattr(self._L, self._unc_pre + "set_poly_library")(self._h, pp, pf, n, _launch_stream(stream, self._device)),
+               self._unc_pre + "set_poly_library")
+
+    def set_poly_assignment(self, traj, place=None, stream=None):
+        """traj [B] int32: trajectory id of every vehicle, -1 = none (its reference rows are left alone); place [B][6] =
+        t_start [s], time_scale, ox, oy, oz [m], yaw0 [rad], None: [0, 1, 0, 0, 0, 0] everywhere.  numpy arrays are validated
+        by the library; torch device tensors are taken as they are."""
+        if place is not None and _is_torch(traj) != _is_torch(place):
+            raise ValueError("traj and place must both be host arrays or both device tensors")
+        pt, dev, st, _k = _arg(traj, (self.B,), dtype=np.int32, device=self._device)
+        pl, _k2 = None, None
+        if place is not None:
+            pl, _d, _s, _k2 = _arg(place, (self.B, NPLACE), device=self._device)
+        if stream:
+            st = C.c_void_p(stream)
+        _check(getattr(self._L, self._unc_pre + "set_poly_assignment")(self._h, pt, pl, dev, st), self._unc_pre + "set_poly_assignment")
+
+    def set_yref_poly(self, t, flags=0, stream=None):
+        """Writes the reference window of every vehicle with a trajectory, rows k = 0 .. N at the fleet times t + k dt, on the
+        device; flags: POLY_LOOP | POLY_KINEMATIC.  Asynchronous."""
+        _check(getattr(self._L, self._unc_pre + "set_yref_poly")(self._h, float(t), int(flags), _launch_stream(stream, self._device)),
+               self._unc_pre + "set_yref_poly")
+
+
+class BatchSolver(UncertaintyCalls, PolyCalls):
     _unc_pre = "cfnmpc_"
     _unc_N = property(lambda self: self.N)
 
@@ -262,6 +307,24 @@ class BatchSolver(UncertaintyCalls):
         if dev != deve:
             raise ValueError("yref and yref_e must live on the same side")
         _check(self._L.cfnmpc_set_yref(self._h, p, pe, dev, st), "cfnmpc_set_yref")
+
+    def yref(self):
+        """-> (yref [B][N][17], yref_e [B][13]): the reference windows in force, public order (cfnmpc_get_yref)"""
+        y = np.empty((self.B, self.N, NY)); ye = np.empty((self.B, NX))
+        _check(self._L.cfnmpc_get_yref(self._h, y.ctypes.data_as(C.c_void_p), ye.ctypes.data_as(C.c_void_p), 0,
+                                       _launch_stream(None, self._device)), "cfnmpc_get_yref")
+        return y, ye
+
+    def eval_poly(self, t, n_stages, flags=0, want_flat=True, want_rows=True):
+        """The evaluation of set_yref_poly for rows k = 0 .. n_stages - 1 without touching the references -> (flat
+        [B][n_stages][13] = pos, vel, acc, yaw, omega as the reference's evaluator returns them, rows [B][n_stages][17]); host
+        arrays, None where not wanted; NaN for vehicles without a trajectory."""
+        fl = np.empty((self.B, int(n_stages), NFLAT)) if want_flat else None
+        rw = np.empty((self.B, int(n_stages), NY)) if want_rows else None
+        _check(self._L.cfnmpc_eval_poly(self._h, float(t), int(n_stages), int(flags), None if fl is None else fl.ctypes.data_as(C.c_void_p),
+                                        None if rw is None else rw.ctypes.data_as(C.c_void_p), 0, _launch_stream(None, self._device)),
+               "cfnmpc_eval_poly")
+        return fl, rw
 
     def set_yref_windows(self, traj, mode, it, des_xyz, uss):
         """Device-side reference windows (NMPC::iteration state machine); all arguments are torch

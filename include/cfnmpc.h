@@ -234,6 +234,72 @@ int cfnmpc_set_yref(cfnmpc_solver *s, const double *yref, const double *yref_e, 
  * tracks), mode [B] / iter [B] (int, updated in place), des_xyz [B][3]. */
 int cfnmpc_set_yref_windows(cfnmpc_solver *s, const double *traj, int n_rows, int *mode, int *iter,
                             const double *des_xyz, double uss, void *stream);
+/* The windows in force, in the public order (the sibling of cfnmpc_set_yref): yref [B][N][17], yref_e [B][13]; either pointer may be
+ * NULL, not both. */
+int cfnmpc_get_yref(cfnmpc_solver *s, double *yref /*[B][N][17] or NULL*/, double *yref_e /*[B][13] or NULL*/, int on_device, void *stream);
+/* Device-side polynomial trajectory references, one per vehicle.  A small LIBRARY of piecewise 7th-order
+ * polynomial trajectories in the format of crazyflie_demo/scripts/ (figure8.csv; uav_trajectory.py evaluates it), a trajectory id
+ * and a PLACEMENT row per vehicle, and one kernel that writes every vehicle's reference window straight into yref / yref_e: the
+ * polynomial and its first three derivatives at each stage time, mapped through the flatness relations of this model.  No RTI
+ * kernel, launch, option or default changes: a solver that never calls these runs the same step bit for bit.
+ *   cfnmpc_set_poly_library: HOST arrays, validated as a whole before anything changes (every number finite, every duration > 0,
+ *     first[0] = 0 and strictly increasing: CFNMPC_EINVAL otherwise).  Limits: CFNMPC_POLY_MAX_TRAJ trajectories and
+ *     CFNMPC_POLY_MAX_PIECES pieces in total, refused beyond (CFNMPC_EINVAL).  n_traj = 0 or a NULL pointer clears the library.
+ *     Replacing the library resets the assigned ids outside [0, n_traj) to -1.  The tables and the assignment are allocated at the
+ *     first call of the feature (cfnmpc_workspace_bytes counts them from then on); the copy is complete on return.
+ *   cfnmpc_set_poly_assignment: traj [B], id of every vehicle's trajectory or -1 = none; place [B][CFNMPC_NPLACE] or NULL =
+ *     [0, 1, 0, 0, 0, 0] for every vehicle.  Host arrays are validated (id in [-1, n_traj), time_scale finite and > 0, the rest
+ *     finite; CFNMPC_EINVAL changes nothing); device arrays are taken as they are: the kernel treats an id outside [0, n_traj) as -1
+ *     and a time_scale that is not a positive finite number as 1, and never indexes the library with an unchecked value.
+ *   cfnmpc_set_yref_poly: for every vehicle with an id >= 0 the stage rows k = 0 .. N-1 and the terminal row k = N (first 13
+ *     columns) at the fleet times t + k dt (cfnmpc_opts.dt).  Vehicles with id -1 keep what cfnmpc_set_yref /
+ *     cfnmpc_set_yref_windows gave them bit for bit: the three sources can be mixed in one fleet.  Its effect on solver state is
+ *     that of cfnmpc_set_yref_windows; the values are written in place (captured step graphs keep replaying); asynchronous on
+ *     `stream`.  CFNMPC_EINVAL without a library, for t not finite and for unknown flags.
+ *   cfnmpc_eval_poly: the same evaluation into the caller's arrays for rows k = 0 .. n_stages-1 (all of them stage rows), without
+ *     touching yref: flat [B][n_stages][CFNMPC_NFLAT] = pos, vel, acc, yaw, omega after placement -- the fields of
+ *     uav_trajectory.py's TrajectoryOutput, with its own omega_z = z_b[2] dyaw --, rows [B][n_stages][17] in the public order
+ *     (either may be NULL, not both).  Rows of vehicles with id -1 are NaN.  Host arrays go through the staging buffer of
+ *     cfnmpc_get_sens_x0, in chunks of rows.
+ * Rules (crazyflie_nmpc_amd/trajectories.py: poly_rows follows them operation for operation; every operation is rounded on its
+ * own, so the host twin and the kernel choose the same piece bit for bit):
+ *   local time    tau = ((t + k dt) - t_start) / time_scale; D = the trajectory's duration, accumulated piece by piece in table order.
+ *   piece         uav_trajectory.py:97-105: the first piece with tau < cum + duration (the last one otherwise), piece time tau - cum.
+ *   outside       tau < 0: held at the start.  tau >= D with CFNMPC_POLY_LOOP: tau -= D floor(tau / D) (a negative result: 0), then
+ *                 the lookup; without the flag: held at the end, the last piece at its own duration.  A held row has position and yaw
+ *                 of that point, zero derivatives, attitude qz(yaw), zero velocities and rates, the vehicle's hover speed.
+ *   derivatives   pos / yaw, vel / dyaw, acc, jerk by Horner's rule on the coefficient lists (i + 1) p[i + 1], taken one to three
+ *                 times (Polynomial.derivative); the d-th derivative is divided by time_scale^d.
+ *   placement     pos, vel, acc and jerk are rotated by Rz(yaw0); yaw += yaw0; pos += (ox, oy, oz).
+ *   flatness      with g0 and Ct / mq of the vehicle's parameter row (cfnmpc_set_model_params; the nominal constants otherwise):
+ *                 thr = acc + (0, 0, g0), z_b = thr / |thr|, x_w = (cos yaw, sin yaw, 0), c = z_b x x_w, y_b = c / |c|, x_b = y_b x z_b,
+ *                 h_w = (jerk - (jerk . z_b) z_b) / |thr|, omega = (-h_w . y_b, h_w . x_b, omega_z).  The evaluator's omega_z =
+ *                 z_b[2] dyaw is an approximation (figure8.csv, yaw = 0: up to 0.11 rad/s from the attitude's body rate); flat
+ *                 returns it, the rows carry the exact one, omega_z = -x_b . (h_w x x_w + z_b x dx_w) / |c| with
+ *                 dx_w = dyaw (-sin yaw, cos yaw, 0): the quaternion rows of this model's ODE are then the reference's own qdot.
+ *   attitude      [x_b y_b z_b] = Rz(yaw) Rx(phi) Ry(theta) with zl = Rz(-yaw) z_b, theta = asin(zl_x), phi = atan2(-zl_y, zl_z);
+ *                 q = qz(yaw) qx(phi) qy(theta) (w, x, y, z): continuous in yaw, no division, no sign choice.
+ *   the rest      v_b = [x_b y_b z_b]' vel; four equal speeds sqrt(|thr| / (4 Ct / mq)) = sqrt(mq |thr| / (4 Ct)).  Torque-consistent
+ *                 rotor speeds need the snap and the yaw acceleration and are out of scope.
+ *   guard         a stage with thr_z <= 0.1 g0 or |c| < 1e-3 is a LEVEL row: attitude qz(yaw), v_b = Rz(yaw)' vel, omega = (0, 0, dyaw)
+ *                 (in flat too), hover speed.  A reference never contains NaN or Inf.
+ *   CFNMPC_POLY_KINEMATIC   the helix-style row [pos, 1, 0, 0, 0, 0 x 6, hover speed x 4] from the same lookup and placement (flat is
+ *                 unchanged): the two references through one call.
+ * Disturbance rows are ignored: the reference is that of the undisturbed vehicle, as with cfnmpc_init_iterate's hover mode. */
+#define CFNMPC_POLY_NC 33      /* one piece: duration, x^0..x^7, y^0..y^7, z^0..z^7, yaw^0..yaw^7 (ascending powers; figure8.csv) */
+#define CFNMPC_NPLACE 6        /* placement row: t_start [s], time_scale (> 0), ox, oy, oz [m], yaw0 [rad] */
+#define CFNMPC_NFLAT 13        /* pos[3], vel[3], acc[3], yaw, omega[3]: the fields of uav_trajectory.py's TrajectoryOutput */
+#define CFNMPC_POLY_LOOP 1      /* flags */
+#define CFNMPC_POLY_KINEMATIC 2
+#define CFNMPC_POLY_MAX_TRAJ 1024
+#define CFNMPC_POLY_MAX_PIECES 8192
+int cfnmpc_set_poly_library(cfnmpc_solver *s, const double *pieces /*[first[n_traj]][33], HOST*/, const int *first /*[n_traj+1], HOST*/,
+                            int n_traj, void *stream);
+int cfnmpc_set_poly_assignment(cfnmpc_solver *s, const int *traj /*[B], -1 = none*/, const double *place /*[B][6] or NULL*/,
+                               int on_device, void *stream);
+int cfnmpc_set_yref_poly(cfnmpc_solver *s, double t, int flags, void *stream);
+int cfnmpc_eval_poly(cfnmpc_solver *s, double t, int n_stages, int flags, double *flat /*[B][n_stages][13] or NULL*/,
+                     double *rows /*[B][n_stages][17] or NULL*/, int on_device, void *stream);
 /* ocp_nlp_cost_model_set(.., k, "W", ..) equivalent (acados_mpc.cpp:596-602, compiled out by
  * SET_WEIGHTS 0 in the reference): diagonal stage / terminal weights for ALL instances and
  * stages; either pointer may be NULL (unchanged).  State weights must be >= 0 (the reference's
@@ -463,7 +529,7 @@ int cfnmpc_get_sens_active(cfnmpc_solver *s, signed char *act /*[B][N][4]*/, int
  *     one put kernel on `stream` (the rule of cfnmpc_set_disturbance).
  *   cfnmpc_eval_uncertainty: one sweep over [0, N) on `stream`, keeps beta.  Writes nothing that a solve reads.  CFNMPC_EINVAL:
  *     no solve yet; any change of the QP's data since the last solve (whatever invalidates cfnmpc_eval_sens_x0, and set_x0 /
- *     set_yref / set_yref_windows); cond_N2 > 0 or start_solve = 2 (no stored blocks).
+ *     set_yref / set_yref_windows / set_yref_poly); cond_N2 > 0 or start_solve = 2 (no stored blocks).
  *   cfnmpc_get_backoff: beta [B][N][4].  The stored beta stays valid until the next cfnmpc_eval_uncertainty,
  *     cfnmpc_init_iterate or cfnmpc_set_iterate, so cfnmpc_tighten_box may come before or after the set_x0 of the next step.
  *   cfnmpc_get_uncertainty: one sweep over [0, stage + n_stages) writes Sigma [B][n_stages][13][13] and std_x [B][n_stages][13]
@@ -668,6 +734,15 @@ int cfnmpc_fleet_eval_uncertainty(cfnmpc_fleet *f, void *stream);
 int cfnmpc_fleet_get_backoff(cfnmpc_fleet *f, double *beta /*[B][Nmax][4]*/, int on_device, void *stream);
 int cfnmpc_fleet_get_uncertainty(cfnmpc_fleet *f, int stage, int n_stages, double *Sigma, double *std_x, int on_device, void *stream);
 int cfnmpc_fleet_tighten_box(cfnmpc_fleet *f, double gamma, double min_width, int *n_clamped /*[B] or NULL*/, int on_device, void *stream);
+/* The polynomial references for a fleet (cfnmpc_set_poly_library ...): the library goes to every bucket; traj [B] and place [B][6]
+ * in the fleet's vehicle order (host arrays are validated as a whole first); every bucket writes its own N + 1 rows at the shared
+ * t and dt.  cfnmpc_fleet_eval_poly evaluates every vehicle's own N stage rows: flat [B][Nmax][13], rows [B][Nmax][17], NaN behind a
+ * vehicle's own horizon. */
+int cfnmpc_fleet_set_poly_library(cfnmpc_fleet *f, const double *pieces, const int *first, int n_traj, void *stream);
+int cfnmpc_fleet_set_poly_assignment(cfnmpc_fleet *f, const int *traj, const double *place, int on_device, void *stream);
+int cfnmpc_fleet_set_yref_poly(cfnmpc_fleet *f, double t, int flags, void *stream);
+int cfnmpc_fleet_eval_poly(cfnmpc_fleet *f, double t, int flags, double *flat /*[B][Nmax][13] or NULL*/,
+                           double *rows /*[B][Nmax][17] or NULL*/, int on_device, void *stream);
 /* cfnmpc_eval_nlp (keep_multipliers = 0) on every bucket, cfnmpc_get_nlp_stats in the fleet's vehicle order: cost [B], res [B][3]
  * (host arrays, on_device 0 or 2, are filled synchronously).  The multipliers have one shape per horizon: evaluate and read them
  * through the bucket's solver (cfnmpc_fleet_bucket). */
@@ -743,6 +818,13 @@ int cfnmpc_multi_tighten_box(cfnmpc_multi *m, double gamma, double min_width, in
  * the caller's order, synchronous */
 int cfnmpc_multi_eval_nlp(cfnmpc_multi *m);
 int cfnmpc_multi_get_nlp_stats(cfnmpc_multi *m, double *cost /*[B] host or NULL*/, double *res /*[B][3] host or NULL*/);
+
+/* The polynomial references per shard (both create variants): the library to every shard; host arrays traj [B], place [B][6] or NULL
+ * of the whole fleet in the caller's order, validated as a whole first; cfnmpc_multi_set_yref_poly is asynchronous on every shard's
+ * stream, like cfnmpc_multi_solve. */
+int cfnmpc_multi_set_poly_library(cfnmpc_multi *m, const double *pieces, const int *first, int n_traj);
+int cfnmpc_multi_set_poly_assignment(cfnmpc_multi *m, const int *traj, const double *place);
+int cfnmpc_multi_set_yref_poly(cfnmpc_multi *m, double t, int flags);
 
 const char *cfnmpc_version(void);
 
