@@ -486,44 +486,51 @@ __device__ __forceinline__ void linearise_body(const Params& P, double* sx, doub
 //  per stage (run-time unit vectors and tile indices, rebuilt rotation matrices) and ran 1.69 - 1.75 ms against 1.19 ms at 65 536
 //  instances (2048 workgroups of 25 stages), 2.05 ms with one workgroup per 64 instances: the second wave did not raise the VALU
 //  occupancy (~54 % either way).  Removed; profiles/r04_linearise_variants.md.)
-KALIGN __global__ __launch_bounds__(64) void k_linearise(Params P) {
-    __shared__ double sx[2 * 64 * 13];   // two tiles of one 13-vector per instance (internal order): x_k, x_{k+1}
-    __shared__ __attribute__((aligned(16))) double sc[4][64 * 13];    // the tile of a group of up to four sensitivity columns
-    __shared__ int sinst[64];
-    linearise_body<false>(P, sx, sc, sinst);
+// ---------------------------------------------------------------------------------------------
+// Kernel variants.  Every family of entry points that differ only in the template arguments of one
+// shared body is ONE list: a row names the kernel, the cell of the family's table it fills and its template arguments.  The
+// list is expanded twice -- by the family's wrapper macro(s) into the __global__ entry points and into the table its launcher
+// indexes with the axes below -- so a variant cannot be defined without being reachable, or chosen by two ladders that differ.
+// ---------------------------------------------------------------------------------------------
+typedef void (*Kernel)(Params);
+enum Model { M_NOM, M_PAR, M_DST, N_MODEL };   // folded constants | rows of P.mpar | + rows of P.dist
+static inline int model_of(const Params& P) { return P.dist ? M_DST : P.mpar ? M_PAR : M_NOM; }
+static inline int erk_of(const Params& P) { return P.erk_steps > 1 ? 1 : 0; }
+static inline int wtab_of(const Params& P) { return P.wtab ? 1 : 0; }
+// true when no cell of a table (an array of kernel pointers of any rank) is empty
+template <class F> constexpr bool filled(F* const& k) { return k != nullptr; }
+template <class T, size_t N> constexpr bool filled(const T (&a)[N]) {
+    for (size_t i = 0; i < N; i++) if (!filled(a[i])) return false;
+    return true;
 }
-KALIGN __global__ __launch_bounds__(64) void k_linearise_erk(Params P) {   // the same with P.erk_steps > 1 RK4 sub-steps per interval
-    __shared__ double sx[2 * 64 * 13];
-    __shared__ __attribute__((aligned(16))) double sc[4][64 * 13];
-    __shared__ int sinst[64];
-    linearise_body<false, false, true>(P, sx, sc, sinst);
+// a cell without a kernel is a combination the setters refuse: one line, no launch (as launch_factor_only for !P.v4b)
+static void launch_variant(Kernel k, const char* family, dim3 grid, hipStream_t st, const Params& P) {
+    if (!k) { std::fprintf(stderr, "cfnmpc: no %s kernel for this combination of options\n", family); return; }
+    hipLaunchKernelGGL(k, grid, dim3(64), 0, st, P);
 }
-// the same two with per-instance model constants (cfnmpc_set_model_params)
-KALIGN __global__ __launch_bounds__(64) void k_linearise_par(Params P) {
-    __shared__ double sx[2 * 64 * 13];
-    __shared__ __attribute__((aligned(16))) double sc[4][64 * 13];
-    __shared__ int sinst[64];
-    linearise_body<false, false, false, true>(P, sx, sc, sinst);
-}
-KALIGN __global__ __launch_bounds__(64) void k_linearise_erk_par(Params P) {
-    __shared__ double sx[2 * 64 * 13];
-    __shared__ __attribute__((aligned(16))) double sc[4][64 * 13];
-    __shared__ int sinst[64];
-    linearise_body<false, false, true, true>(P, sx, sc, sinst);
-}
-// ... and with per-instance disturbance rows on top (cfnmpc_set_disturbance)
-KALIGN __global__ __launch_bounds__(64) void k_linearise_dst(Params P) {
-    __shared__ double sx[2 * 64 * 13];
-    __shared__ __attribute__((aligned(16))) double sc[4][64 * 13];
-    __shared__ int sinst[64];
-    linearise_body<false, false, false, true, true>(P, sx, sc, sinst);
-}
-KALIGN __global__ __launch_bounds__(64) void k_linearise_erk_dst(Params P) {
-    __shared__ double sx[2 * 64 * 13];
-    __shared__ __attribute__((aligned(16))) double sc[4][64 * 13];
-    __shared__ int sinst[64];
-    linearise_body<false, false, true, true, true>(P, sx, sc, sinst);
-}
+
+// Linearisation: model x erk.  Row: name, model, erk, template arguments of linearise_body.
+#define CFN_LINEARISE_KERNELS(X)                                                                        \
+    X(k_linearise,         M_NOM, 0, false)                                                             \
+    X(k_linearise_erk,     M_NOM, 1, false, false, true)                 /* P.erk_steps > 1 RK4 sub-steps per interval */ \
+    X(k_linearise_par,     M_PAR, 0, false, false, false, true)          /* per-instance model constants (cfnmpc_set_model_params) */ \
+    X(k_linearise_erk_par, M_PAR, 1, false, false, true, true)                                          \
+    X(k_linearise_dst,     M_DST, 0, false, false, false, true, true)    /* + disturbance rows (cfnmpc_set_disturbance) */ \
+    X(k_linearise_erk_dst, M_DST, 1, false, false, true, true, true)
+#define CFN_LINEARISE_KERNEL(name, model, erk, ...)                                                     \
+    KALIGN __global__ __launch_bounds__(64) void name(Params P) {                                       \
+        __shared__ double sx[2 * 64 * 13];   /* two tiles of one 13-vector per instance (internal order): x_k, x_{k+1} */ \
+        __shared__ __attribute__((aligned(16))) double sc[4][64 * 13];   /* the tile of a group of up to four sensitivity columns */ \
+        __shared__ int sinst[64];                                                                       \
+        linearise_body<__VA_ARGS__>(P, sx, sc, sinst);                                                  \
+    }
+CFN_LINEARISE_KERNELS(CFN_LINEARISE_KERNEL)
+#undef CFN_LINEARISE_KERNEL
+struct LineariseTab { Kernel k[N_MODEL][2]; };
+#define CFN_CELL(name, model, erk, ...) t.k[model][erk] = name;
+static constexpr LineariseTab linearise_tab = [] { LineariseTab t{}; CFN_LINEARISE_KERNELS(CFN_CELL) return t; }();
+#undef CFN_CELL
+static_assert(filled(linearise_tab.k), "a linearisation variant has no kernel");
 #ifdef CFN_DEV   // (overlapped preparation: development builds only)
 __global__ __launch_bounds__(64) void k_linearise_list(Params P) {
     __shared__ double sx[2 * 64 * 13];
@@ -1141,6 +1148,17 @@ __device__ __forceinline__ void forward_body(const Params& P, double* xs, double
     using FwdK = typename std::conditional<DST, DstK, typename std::conditional<PAR, typename std::conditional<LAZY, ParKG, ParK>::type, NomK>::type>::type;
     FwdK mk{};
     if constexpr (PAR && !LAZY) mk = model_k<PAR, DST>(P, inst);
+    if constexpr (SPLIT == 1 && ERK && DST) {
+        // k_forward_p1_erk_dst only.  As built before, the compiler split one of these constants when it spilled it ahead of
+        // the stage loop -- low half through scratch into one accumulation register, high half into another -- and read the
+        // high half back in the loop from a third that nothing ever wrote: the w_z row of every sub-step was multiplied by a
+        // constant with a garbage high word (every row of a split, disturbed, sub-stepped sweep off by ~1e-2 from stage 1
+        // on; tests/test_gpu_variants.py, cell start-dst-2:forward_split=1).  Opaque copies of the fourteen constants change
+        // the allocation: no register of the kernel is read unwritten any more (scratch 68 -> 52 B), every other kernel of
+        // the unit keeps its instruction stream.
+        _Pragma("unroll") for (int j = 0; j < 8; j++) asm volatile("" : "+v"(mk.c[j]));
+        _Pragma("unroll") for (int j = 0; j < ND; j++) asm volatile("" : "+v"(mk.d[j]));
+    }
     if constexpr (LAZY) mk = FwdK{gm(P.mpar) + inst, (unsigned)(P.NW + 1) * 4u};
     const double margin = P.ah_margin * (P.u_max - P.u_min);
     const gdouble* kp = gm(P.KR) + w * N * SZ_K + q * 4;
@@ -1439,11 +1457,52 @@ __device__ __forceinline__ void forward_body(const Params& P, double* xs, double
     }
 }
 
-KALIGN __global__ __launch_bounds__(64) void k_forward(Params P) {   // matrix-free forward sweep of the start solve
-    __shared__ double xs[64 * 13], cs[64 * 13];
-    __shared__ int sflag[64];
-    forward_body<false, true>(P, xs, cs, sflag);
-}
+// Matrix-free forward sweeps of the start solve: sweep x model x erk.  Row: name, alignment, sweep, model, erk, template
+// arguments of forward_body; HOLE rows are the cells without a kernel.
+enum Sweep { S_WHOLE, S_P1, S_P2, S_COND, N_SWEEP };   // all stages | split sweep: stages [0, H) + classification | stages [H, N), late rows | cond_N2
+#define CFN_UNALIGNED
+#define CFN_FORWARD_KERNELS(X, HOLE)                                                                    \
+    X(k_forward,            KALIGN,        S_WHOLE, M_NOM, 0, false, true)                              \
+    X(k_forward_p1,         KALIGN,        S_P1,    M_NOM, 0, false, true, 1)                           \
+    X(k_forward_p2,         KALIGN,        S_P2,    M_NOM, 0, false, true, 2)                           \
+    X(k_cforward,           CFN_UNALIGNED, S_COND,  M_NOM, 0, true)                                     \
+    X(k_forward_erk,        KALIGN,        S_WHOLE, M_NOM, 1, false, true, 0, true)                     \
+    X(k_forward_p1_erk,     KALIGN,        S_P1,    M_NOM, 1, false, true, 1, true)                     \
+    X(k_forward_p2_erk,     KALIGN,        S_P2,    M_NOM, 1, false, true, 2, true)                     \
+    X(k_cforward_erk,       CFN_UNALIGNED, S_COND,  M_NOM, 1, true, false, 0, true)                     \
+    X(k_forward_par,        KALIGN,        S_WHOLE, M_PAR, 0, false, true, 0, false, true)              \
+    X(k_forward_p1_par,     KALIGN,        S_P1,    M_PAR, 0, false, true, 1, false, true)              \
+    X(k_forward_p2_par,     KALIGN,        S_P2,    M_PAR, 0, false, true, 2, false, true)              \
+    X(k_cforward_par,       KALIGN,        S_COND,  M_PAR, 0, true, false, 0, false, true)              \
+    X(k_forward_erk_par,    KALIGN,        S_WHOLE, M_PAR, 1, false, true, 0, true, true)               \
+    X(k_forward_p1_erk_par, KALIGN,        S_P1,    M_PAR, 1, false, true, 1, true, true)               \
+    X(k_forward_p2_erk_par, KALIGN,        S_P2,    M_PAR, 1, false, true, 2, true, true)               \
+    X(k_cforward_erk_par,   KALIGN,        S_COND,  M_PAR, 1, true, false, 0, true, true)               \
+    X(k_forward_dst,        KALIGN,        S_WHOLE, M_DST, 0, false, true, 0, false, true, true)        \
+    X(k_forward_p1_dst,     KALIGN,        S_P1,    M_DST, 0, false, true, 1, false, true, true)        \
+    X(k_forward_p2_dst,     KALIGN,        S_P2,    M_DST, 0, false, true, 2, false, true, true)        \
+    HOLE(S_COND, M_DST, 0)                                 /* cfnmpc_set_disturbance refuses cond_N2 */ \
+    X(k_forward_erk_dst,    KALIGN,        S_WHOLE, M_DST, 1, false, true, 0, true, true, true)         \
+    X(k_forward_p1_erk_dst, KALIGN,        S_P1,    M_DST, 1, false, true, 1, true, true, true)         \
+    X(k_forward_p2_erk_dst, KALIGN,        S_P2,    M_DST, 1, false, true, 2, true, true, true)         \
+    HOLE(S_COND, M_DST, 1)                                 /* cfnmpc_set_disturbance refuses cond_N2 */
+#define CFN_FORWARD_KERNEL(name, align, sweep, model, erk, ...)                                         \
+    align __global__ __launch_bounds__(64) void name(Params P) {                                        \
+        __shared__ double xs[64 * 13], cs[64 * 13];                                                     \
+        __shared__ int sflag[64];                                                                       \
+        forward_body<__VA_ARGS__>(P, xs, cs, sflag);                                                    \
+    }
+#define CFN_NO_KERNEL(...)
+CFN_FORWARD_KERNELS(CFN_FORWARD_KERNEL, CFN_NO_KERNEL)
+#undef CFN_FORWARD_KERNEL
+struct ForwardTab { Kernel k[N_SWEEP][N_MODEL][2]; int rows; };
+#define CFN_CELL(name, align, sweep, model, erk, ...) t.k[sweep][model][erk] = name; t.rows++;
+#define CFN_HOLE(sweep, model, erk) t.k[sweep][model][erk] = nullptr; t.rows++;
+static constexpr ForwardTab forward_tab = [] { ForwardTab t{}; CFN_FORWARD_KERNELS(CFN_CELL, CFN_HOLE) return t; }();
+#undef CFN_CELL
+#undef CFN_HOLE
+static_assert(forward_tab.rows == N_SWEEP * N_MODEL * 2, "every forward-sweep variant is a kernel or a named hole");
+static_assert(filled(forward_tab.k[S_WHOLE]) && filled(forward_tab.k[S_P1]) && filled(forward_tab.k[S_P2]), "a matrix-free sweep has no kernel");
 #ifdef CFN_DEV
 // the same at two waves per SIMD (<= 256 registers, a few spills): beside the fused start solve of ANOTHER sub-fleet, whose
 // waves leave half a SIMD's register file each (cfnmpc_opts.sub_fleets)
@@ -1453,65 +1512,6 @@ __global__ __launch_bounds__(64, 2) void k_forward_half(Params P) {
     forward_body<false, true>(P, xs, cs, sflag);
 }
 #endif
-KALIGN __global__ __launch_bounds__(64) void k_forward_p1(Params P) {   // split sweep, stages [0, H) + classification
-    __shared__ double xs[64 * 13], cs[64 * 13];
-    __shared__ int sflag[64];
-    forward_body<false, true, 1>(P, xs, cs, sflag);
-}
-KALIGN __global__ __launch_bounds__(64) void k_forward_p2(Params P) {   // split sweep, stages [H, N), late rows
-    __shared__ double xs[64 * 13], cs[64 * 13];
-    __shared__ int sflag[64];
-    forward_body<false, true, 2>(P, xs, cs, sflag);
-}
-__global__ __launch_bounds__(64) void k_cforward(Params P) {
-    __shared__ double xs[64 * 13], cs[64 * 13];
-    __shared__ int sflag[64];
-    forward_body<true>(P, xs, cs, sflag);
-}
-// the same sweeps with P.erk_steps > 1 RK4 sub-steps per interval
-KALIGN __global__ __launch_bounds__(64) void k_forward_erk(Params P) {
-    __shared__ double xs[64 * 13], cs[64 * 13];
-    __shared__ int sflag[64];
-    forward_body<false, true, 0, true>(P, xs, cs, sflag);
-}
-KALIGN __global__ __launch_bounds__(64) void k_forward_p1_erk(Params P) {
-    __shared__ double xs[64 * 13], cs[64 * 13];
-    __shared__ int sflag[64];
-    forward_body<false, true, 1, true>(P, xs, cs, sflag);
-}
-KALIGN __global__ __launch_bounds__(64) void k_forward_p2_erk(Params P) {
-    __shared__ double xs[64 * 13], cs[64 * 13];
-    __shared__ int sflag[64];
-    forward_body<false, true, 2, true>(P, xs, cs, sflag);
-}
-__global__ __launch_bounds__(64) void k_cforward_erk(Params P) {
-    __shared__ double xs[64 * 13], cs[64 * 13];
-    __shared__ int sflag[64];
-    forward_body<true, false, 0, true>(P, xs, cs, sflag);
-}
-// the eight sweeps with per-instance model constants (cfnmpc_set_model_params)
-#define CFN_FWD_PAR(name, ...)                                                                          \
-    KALIGN __global__ __launch_bounds__(64) void name(Params P) {                                       \
-        __shared__ double xs[64 * 13], cs[64 * 13];                                                     \
-        __shared__ int sflag[64];                                                                       \
-        forward_body<__VA_ARGS__>(P, xs, cs, sflag);                                                    \
-    }
-CFN_FWD_PAR(k_forward_par, false, true, 0, false, true)
-CFN_FWD_PAR(k_forward_p1_par, false, true, 1, false, true)
-CFN_FWD_PAR(k_forward_p2_par, false, true, 2, false, true)
-CFN_FWD_PAR(k_cforward_par, true, false, 0, false, true)
-CFN_FWD_PAR(k_forward_erk_par, false, true, 0, true, true)
-CFN_FWD_PAR(k_forward_p1_erk_par, false, true, 1, true, true)
-CFN_FWD_PAR(k_forward_p2_erk_par, false, true, 2, true, true)
-CFN_FWD_PAR(k_cforward_erk_par, true, false, 0, true, true)
-// the six matrix-free sweeps with per-instance disturbance rows on top (cfnmpc_set_disturbance)
-CFN_FWD_PAR(k_forward_dst, false, true, 0, false, true, true)
-CFN_FWD_PAR(k_forward_p1_dst, false, true, 1, false, true, true)
-CFN_FWD_PAR(k_forward_p2_dst, false, true, 2, false, true, true)
-CFN_FWD_PAR(k_forward_erk_dst, false, true, 0, true, true, true)
-CFN_FWD_PAR(k_forward_p1_erk_dst, false, true, 1, true, true, true)
-CFN_FWD_PAR(k_forward_p2_erk_dst, false, true, 2, true, true, true)
-#undef CFN_FWD_PAR
 
 // ---------------------------------------------------------------------------------------------
 // Start solve, forward sweep on the STORED stage blocks -- row groups, four instances per wave.
@@ -2543,120 +2543,87 @@ __global__ __launch_bounds__(1024) void k_ipm_list(Params P) {
 __device__ __forceinline__ int ipm_rest_rows(const Params& P) {
     return P.ipm_listed ? gm(P.nipm)[NI_LISTED] : gm(P.nipm)[0] + (P.fwd_split ? gm(P.nipm)[NI_LATE] : 0);
 }
-__global__ __launch_bounds__(64) void k_ipm(Params P) {       // MODE 0: used when active_set = 0
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    qp_wave<0, false, false, false, WR_ARGS>(P, wtile, btile, blockIdx.x);
-}
-KALIGN __global__ __launch_bounds__(64) void k_as(Params P) {        // active-set solves
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    __shared__ __attribute__((aligned(16))) double qtab[16 * QT_ROW];
-    qtab_fill(P, qtab);
-    __syncthreads();
-    qp_wave<1, false, false, true, WR_ARGS>(P, wtile, btile, blockIdx.x, qtab);
-}
-__global__ __launch_bounds__(64) void k_ipm_rest(Params P) {  // interior point for what k_as left
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    for (int vb = blockIdx.x; vb * 4 < ipm_rest_rows(P); vb += gridDim.x) qp_wave<2, false, false, false, WR_ARGS>(P, wtile, btile, vb);
-}
-// the same three for per-stage input boxes (cfnmpc_set_box_stages)
-__global__ __launch_bounds__(64) void k_ipm_sbox(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    qp_wave<0, true, false, false, WR_ARGS>(P, wtile, btile, blockIdx.x);
-}
-__global__ __launch_bounds__(64) void k_as_sbox(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    qp_wave<1, true, false, false, WR_ARGS>(P, wtile, btile, blockIdx.x);
-}
-__global__ __launch_bounds__(64) void k_ipm_rest_sbox(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    for (int vb = blockIdx.x; vb * 4 < ipm_rest_rows(P); vb += gridDim.x) qp_wave<2, true, false, false, WR_ARGS>(P, wtile, btile, vb);
-}
-// the three for the fused start solve (Params.fused = 1: stage blocks only in the compact store)
-__global__ __launch_bounds__(64) void k_ipm_cst(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    qp_wave<0, false, true, false, WR_ARGS>(P, wtile, btile, blockIdx.x);
-}
-KALIGN __global__ __launch_bounds__(64) void k_as_cst(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    qp_wave<1, false, true, false, WR_ARGS>(P, wtile, btile, blockIdx.x);
-}
-__global__ __launch_bounds__(64) void k_ipm_rest_cst(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    for (int vb = blockIdx.x; vb * 4 < ipm_rest_rows(P); vb += gridDim.x) qp_wave<2, false, true, false, WR_ARGS>(P, wtile, btile, vb);
-}
-__global__ __launch_bounds__(64) void k_as_solves(Params P) {  // MODE 4: active-set solves, no roll-out
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    __shared__ __attribute__((aligned(16))) double qtab[16 * QT_ROW];
-    qtab_fill(P, qtab);
-    __syncthreads();
-    qp_wave<4, false, false, true, WR_ARGS>(P, wtile, btile, blockIdx.x, qtab);
-}
-// The twins for per-instance cost weights (Params.wtab).  k_as / k_as_solves: without the LDS weight
-// table, which the four rows of a wavefront share.  The interior-point kernels: with the run-time test of P.wtab inside they
-// exceed their scratch ceilings (tests/test_resource_budget.py), so the kernels above read the kernel arguments and these the table.
-KALIGN __global__ __launch_bounds__(64) void k_as_w(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    __shared__ double wrows_lds[4][WT_STRIDE];
-    qp_wave<1, false, false, false, WR_TABLE>(P, wtile, btile, blockIdx.x, &wrows_lds[0][0]);
-}
-__global__ __launch_bounds__(64) void k_as_solves_w(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    __shared__ double wrows_lds[4][WT_STRIDE];
-    qp_wave<4, false, false, false, WR_TABLE>(P, wtile, btile, blockIdx.x, &wrows_lds[0][0]);
-}
-__global__ __launch_bounds__(64) void k_as_sbox_w(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    __shared__ double wrows_lds[4][WT_STRIDE];
-    qp_wave<1, true, false, false, WR_TABLE>(P, wtile, btile, blockIdx.x, &wrows_lds[0][0]);
-}
-__global__ __launch_bounds__(64) void k_as_retry_w(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    __shared__ double wrows_lds[4][WT_STRIDE];
-    qp_wave<3, false, false, false, WR_TABLE>(P, wtile, btile, blockIdx.x, &wrows_lds[0][0]);
-}
-__global__ __launch_bounds__(64) void k_ipm_w(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    __shared__ double wrows_lds[4][WT_STRIDE];
-    qp_wave<0, false, false, false, WR_TABLE>(P, wtile, btile, blockIdx.x, &wrows_lds[0][0]);
-}
-__global__ __launch_bounds__(64) void k_ipm_rest_w(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    __shared__ double wrows_lds[4][WT_STRIDE];
-    for (int vb = blockIdx.x; vb * 4 < ipm_rest_rows(P); vb += gridDim.x) qp_wave<2, false, false, false, WR_TABLE>(P, wtile, btile, vb, &wrows_lds[0][0]);
-}
-__global__ __launch_bounds__(64) void k_ipm_sbox_w(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    __shared__ double wrows_lds[4][WT_STRIDE];
-    qp_wave<0, true, false, false, WR_TABLE>(P, wtile, btile, blockIdx.x, &wrows_lds[0][0]);
-}
-__global__ __launch_bounds__(64) void k_ipm_rest_sbox_w(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    __shared__ double wrows_lds[4][WT_STRIDE];
-    for (int vb = blockIdx.x; vb * 4 < ipm_rest_rows(P); vb += gridDim.x) qp_wave<2, true, false, false, WR_TABLE>(P, wtile, btile, vb, &wrows_lds[0][0]);
-}
-__global__ __launch_bounds__(64) void k_as_retry(Params P) {  // MODE 3: rows the commit kernel sent back
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    qp_wave<3, false, false, false, WR_ARGS>(P, wtile, btile, blockIdx.x);
-}
+// The constrained-QP kernels: kind x box x weights.  Row: name, alignment, kind, box, weights, call shape, template arguments of qp_wave;
+// the macro that heads a row is its LDS shape.  HOLE rows are the cells without a kernel.
+//   The _w twins (per-instance cost weights, Params.wtab) of k_as / k_as_solves go without the LDS weight
+//   table, which the four rows of a wavefront share.  The interior-point kernels: with the run-time test of P.wtab inside they
+//   exceed their scratch ceilings (tests/test_resource_budget.py), so the plain kernels read the kernel arguments and the twins the table.
+enum QpKind { Q_IPM, Q_AS, Q_REST, Q_RETRY, Q_SOLVES, N_QP };
+//   Q_IPM (MODE 0): interior point, used when active_set = 0 | Q_AS (1): active-set solves | Q_REST (2): interior point for what
+//   the active-set kernels left | Q_RETRY (3): rows the commit kernel sent back | Q_SOLVES (4): active-set solves, no roll-out
+enum Box { B_PLAIN, B_SBOX, B_CST, N_BOX };
+//   B_SBOX: per-stage input boxes (cfnmpc_set_box_stages) | B_CST: the fused start solve (Params.fused = 1: stage blocks only in
+//   the compact store); per-stage boxes take the stored path (launch_qp_start)
+static inline int box_of(const Params& P) { return P.lbs ? B_SBOX : P.fused == 1 ? B_CST : B_PLAIN; }
+#define CFN_QP_KERNELS(PLAIN, QTAB, WROWS, HOLE)                                                        \
+    PLAIN(k_ipm,             CFN_UNALIGNED, Q_IPM,    B_PLAIN, 0, ONCE, 0, false, false, false, WR_ARGS)    \
+    WROWS(k_ipm_w,           CFN_UNALIGNED, Q_IPM,    B_PLAIN, 1, ONCE, 0, false, false, false, WR_TABLE)   \
+    PLAIN(k_ipm_sbox,        CFN_UNALIGNED, Q_IPM,    B_SBOX,  0, ONCE, 0, true, false, false, WR_ARGS)     \
+    WROWS(k_ipm_sbox_w,      CFN_UNALIGNED, Q_IPM,    B_SBOX,  1, ONCE, 0, true, false, false, WR_TABLE)    \
+    PLAIN(k_ipm_cst,         CFN_UNALIGNED, Q_IPM,    B_CST,   0, ONCE, 0, false, true, false, WR_ARGS)     \
+    HOLE(Q_IPM, B_CST, 1)                              /* cfnmpc_set_weights_batch refuses the fused start solve */ \
+    QTAB(k_as,               KALIGN,        Q_AS,     B_PLAIN, 0, ONCE, 1, false, false, true, WR_ARGS)     \
+    WROWS(k_as_w,            KALIGN,        Q_AS,     B_PLAIN, 1, ONCE, 1, false, false, false, WR_TABLE)   \
+    PLAIN(k_as_sbox,         CFN_UNALIGNED, Q_AS,     B_SBOX,  0, ONCE, 1, true, false, false, WR_ARGS)     \
+    WROWS(k_as_sbox_w,       CFN_UNALIGNED, Q_AS,     B_SBOX,  1, ONCE, 1, true, false, false, WR_TABLE)    \
+    PLAIN(k_as_cst,          KALIGN,        Q_AS,     B_CST,   0, ONCE, 1, false, true, false, WR_ARGS)     \
+    HOLE(Q_AS, B_CST, 1)                               /* cfnmpc_set_weights_batch refuses the fused start solve */ \
+    PLAIN(k_ipm_rest,        CFN_UNALIGNED, Q_REST,   B_PLAIN, 0, LOOP, 2, false, false, false, WR_ARGS)    \
+    WROWS(k_ipm_rest_w,      CFN_UNALIGNED, Q_REST,   B_PLAIN, 1, LOOP, 2, false, false, false, WR_TABLE)   \
+    PLAIN(k_ipm_rest_sbox,   CFN_UNALIGNED, Q_REST,   B_SBOX,  0, LOOP, 2, true, false, false, WR_ARGS)     \
+    WROWS(k_ipm_rest_sbox_w, CFN_UNALIGNED, Q_REST,   B_SBOX,  1, LOOP, 2, true, false, false, WR_TABLE)    \
+    PLAIN(k_ipm_rest_cst,    CFN_UNALIGNED, Q_REST,   B_CST,   0, LOOP, 2, false, true, false, WR_ARGS)     \
+    HOLE(Q_REST, B_CST, 1)                             /* cfnmpc_set_weights_batch refuses the fused start solve */ \
+    PLAIN(k_as_retry,        CFN_UNALIGNED, Q_RETRY,  B_PLAIN, 0, ONCE, 3, false, false, false, WR_ARGS)    \
+    WROWS(k_as_retry_w,      CFN_UNALIGNED, Q_RETRY,  B_PLAIN, 1, ONCE, 3, false, false, false, WR_TABLE)   \
+    QTAB(k_as_solves,        CFN_UNALIGNED, Q_SOLVES, B_PLAIN, 0, ONCE, 4, false, false, true, WR_ARGS)     \
+    WROWS(k_as_solves_w,     CFN_UNALIGNED, Q_SOLVES, B_PLAIN, 1, ONCE, 4, false, false, false, WR_TABLE)   \
+    /* the staged structure (as_passes != 0: solves, commit, retries) exists over stored blocks and the scalar box only: */ \
+    /* cfnmpc_create refuses start_solve = 2 beside as_passes != 0, and launch_qp_ipm gives per-stage boxes */ \
+    /* (cfnmpc_set_box_stages) the monolithic kernels whatever as_passes says */                        \
+    HOLE(Q_RETRY, B_SBOX, 0) HOLE(Q_RETRY, B_SBOX, 1) HOLE(Q_RETRY, B_CST, 0) HOLE(Q_RETRY, B_CST, 1)   \
+    HOLE(Q_SOLVES, B_SBOX, 0) HOLE(Q_SOLVES, B_SBOX, 1) HOLE(Q_SOLVES, B_CST, 0) HOLE(Q_SOLVES, B_CST, 1)
+// the call shapes: one block per wave of rows | the grid-stride loop of the fall-back kernels over ipm_rest_rows
+#define CFN_QP_ONCE(tab, ...) qp_wave<__VA_ARGS__>(P, wtile, btile, blockIdx.x, tab);
+#define CFN_QP_LOOP(tab, ...) for (int vb = blockIdx.x; vb * 4 < ipm_rest_rows(P); vb += gridDim.x) qp_wave<__VA_ARGS__>(P, wtile, btile, vb, tab);
+#define CFN_QP_PLAIN(name, align, kind, box, w, call, ...)                                              \
+    align __global__ __launch_bounds__(64) void name(Params P) {                                        \
+        __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];                               \
+        __shared__ double btile[4][64];                                                                 \
+        CFN_QP_##call(nullptr, __VA_ARGS__)                                                             \
+    }
+#define CFN_QP_QTAB(name, align, kind, box, w, call, ...)                                               \
+    align __global__ __launch_bounds__(64) void name(Params P) {                                        \
+        __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];                               \
+        __shared__ double btile[4][64];                                                                 \
+        __shared__ __attribute__((aligned(16))) double qtab[16 * QT_ROW];                               \
+        qtab_fill(P, qtab);                                                                             \
+        __syncthreads();                                                                                \
+        CFN_QP_##call(qtab, __VA_ARGS__)                                                                \
+    }
+#define CFN_QP_WROWS(name, align, kind, box, w, call, ...)                                              \
+    align __global__ __launch_bounds__(64) void name(Params P) {                                        \
+        __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];                               \
+        __shared__ double btile[4][64];                                                                 \
+        __shared__ double wrows_lds[4][WT_STRIDE];                                                      \
+        CFN_QP_##call(&wrows_lds[0][0], __VA_ARGS__)                                                    \
+    }
+CFN_QP_KERNELS(CFN_QP_PLAIN, CFN_QP_QTAB, CFN_QP_WROWS, CFN_NO_KERNEL)
+#undef CFN_QP_PLAIN
+#undef CFN_QP_QTAB
+#undef CFN_QP_WROWS
+#undef CFN_QP_ONCE
+#undef CFN_QP_LOOP
+#undef CFN_NO_KERNEL
+struct QpTab { Kernel k[N_QP][N_BOX][2]; int rows; };
+#define CFN_CELL(name, align, kind, box, w, call, ...) t.k[kind][box][w] = name; t.rows++;
+#define CFN_HOLE(kind, box, w) t.k[kind][box][w] = nullptr; t.rows++;
+static constexpr QpTab qp_tab = [] { QpTab t{}; CFN_QP_KERNELS(CFN_CELL, CFN_CELL, CFN_CELL, CFN_HOLE) return t; }();
+#undef CFN_CELL
+#undef CFN_HOLE
+static_assert(qp_tab.rows == N_QP * N_BOX * 2, "every constrained-QP variant is a kernel or a named hole");
+static_assert(filled(qp_tab.k[Q_IPM][B_PLAIN]) && filled(qp_tab.k[Q_AS][B_PLAIN]) && filled(qp_tab.k[Q_REST][B_PLAIN]) &&
+              filled(qp_tab.k[Q_RETRY][B_PLAIN]) && filled(qp_tab.k[Q_SOLVES][B_PLAIN]), "a stored-block, scalar-box QP kernel is missing");
 #ifdef CFN_DEV   // round 3's scheduling experiments (as_passes -2 / 1..12): development builds only since round 6 (measured slower at every fleet size)
 // =============================================================================================
 // Level-synchronous active-set passes (cfnmpc_opts.as_pipeline)
@@ -3529,32 +3496,25 @@ __global__ void k_postproc(Params P, double* __restrict__ cmd_vel, int* __restri
     }
 }
 
-__global__ void k_init_iterate(Params P, int mode) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= P.B) return;
-    // generate_c_code.py:58,135 / SURVEY App. D-3
-    const double hov = sqrt((MQ * G0) / (4 * CT));
-    for (int k = 0; k <= P.N; k++)
-        for (int e = 0; e < 13; e++) {
-            const double x0e = P.x0[blk_index(i, 0, int_of(e), 1, 13)];
-            P.xit[blk_index(i, k, int_of(e), P.N + 1, 13)] = (mode == 1) ? x0e : (e == 3 ? 1.0 : 0.0);
-        }
-    for (int k = 0; k < P.N; k++)
-        for (int e = 0; e < 4; e++) P.uit[blk_index(i, k, e, P.N, 4, P.v4b)] = (mode == 1) ? hov : 0.0;
-}
-// the same with each instance's own hover speed (row NK - 1 of P.mpar, cfnmpc_set_model_params)
-__global__ void k_init_iterate_par(Params P, int mode) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= P.B) return;
-    const double hov = P.mpar[(size_t)(NK - 1) * ((size_t)P.NW + 1) * 4 + i];
-    for (int k = 0; k <= P.N; k++)
-        for (int e = 0; e < 13; e++) {
-            const double x0e = P.x0[blk_index(i, 0, int_of(e), 1, 13)];
-            P.xit[blk_index(i, k, int_of(e), P.N + 1, 13)] = (mode == 1) ? x0e : (e == 3 ? 1.0 : 0.0);
-        }
-    for (int k = 0; k < P.N; k++)
-        for (int e = 0; e < 4; e++) P.uit[blk_index(i, k, e, P.N, 4, P.v4b)] = (mode == 1) ? hov : 0.0;
-}
+// One body for both: HOV is the hover speed of instance i.  (A macro, not an inlined template: behind any inlined call the compiler
+// addresses the thirteen stores of a stage from another base and the kernels lose one instruction.)
+#define CFN_INIT_ITERATE_KERNEL(name, HOV)                                                              \
+    __global__ void name(Params P, int mode) {                                                          \
+        const int i = blockIdx.x * blockDim.x + threadIdx.x;                                            \
+        if (i >= P.B) return;                                                                           \
+        const double hov = HOV;                                                                         \
+        for (int k = 0; k <= P.N; k++)                                                                  \
+            for (int e = 0; e < 13; e++) {                                                              \
+                const double x0e = P.x0[blk_index(i, 0, int_of(e), 1, 13)];                             \
+                P.xit[blk_index(i, k, int_of(e), P.N + 1, 13)] = (mode == 1) ? x0e : (e == 3 ? 1.0 : 0.0); \
+            }                                                                                           \
+        for (int k = 0; k < P.N; k++)                                                                   \
+            for (int e = 0; e < 4; e++) P.uit[blk_index(i, k, e, P.N, 4, P.v4b)] = (mode == 1) ? hov : 0.0; \
+    }
+CFN_INIT_ITERATE_KERNEL(k_init_iterate, sqrt((MQ * G0) / (4 * CT)))   // generate_c_code.py:58,135 / SURVEY App. D-3
+// each instance's own hover speed (row NK - 1 of P.mpar, cfnmpc_set_model_params)
+CFN_INIT_ITERATE_KERNEL(k_init_iterate_par, P.mpar[(size_t)(NK - 1) * ((size_t)P.NW + 1) * 4 + i])
+#undef CFN_INIT_ITERATE_KERNEL
 
 // cfnmpc_opts.reinit_failed: an instance whose last step ended in status 4 (factorisation not positive definite / not
 // finite: its iterate has left the region where the Gauss-Newton QP is solvable, and re-linearising around the same iterate
@@ -3691,9 +3651,6 @@ __device__ __forceinline__ void sqp_check_body(const Params& P, const SqpArgs& A
         if (blockIdx.x == 0) A.cnt[(A.j + 1) & 1] = 0u;
     }
 }
-__global__ __launch_bounds__(64) void k_sqp_check(Params P, SqpArgs A) { sqp_check_body<false>(P, A); }
-__global__ __launch_bounds__(64) void k_sqp_check_par(Params P, SqpArgs A) { sqp_check_body<true>(P, A); }
-__global__ __launch_bounds__(64) void k_sqp_check_dst(Params P, SqpArgs A) { sqp_check_body<true, true>(P, A); }
 
 // =============================================================================================
 // globalised SQP solve (cfnmpc_set_sqp_globalization): l1 merit backtracking behind SQP iteration j
@@ -3969,9 +3926,6 @@ __device__ __forceinline__ void sqp_ls_body(const Params& P, const SqpArgs& A, c
         if (blockIdx.x == 0) A.cnt[(A.j + 1) & 1] = 0u;
     }
 }
-__global__ __launch_bounds__(64) void k_sqp_ls(Params P, SqpArgs A, LsArgs G) { sqp_ls_body<false>(P, A, G); }
-__global__ __launch_bounds__(64) void k_sqp_ls_par(Params P, SqpArgs A, LsArgs G) { sqp_ls_body<true>(P, A, G); }
-__global__ __launch_bounds__(64) void k_sqp_ls_dst(Params P, SqpArgs A, LsArgs G) { sqp_ls_body<true, true>(P, A, G); }
 
 // =============================================================================================
 // NLP evaluation at the current iterate (cfnmpc_eval_nlp)
@@ -4186,9 +4140,38 @@ __device__ __forceinline__ void nlp_eval_body(const Params& P, const NlpArgs& A)
         gm(A.res)[(size_t)raw * 3 + 2] = r_ineq;
     }
 }
-__global__ __launch_bounds__(64) void k_nlp_eval(Params P, NlpArgs A) { nlp_eval_body<false>(P, A); }
-__global__ __launch_bounds__(64) void k_nlp_eval_par(Params P, NlpArgs A) { nlp_eval_body<true>(P, A); }
-__global__ __launch_bounds__(64) void k_nlp_eval_dst(Params P, NlpArgs A) { nlp_eval_body<true, true>(P, A); }
+
+// The lane-per-instance NLP sweeps that take arguments beside Params (full SQP solve, line search, NLP evaluation): family x model.
+// Row: name, family (its body is <family>_body, its arguments CFN_PARAMS_ / CFN_PASS_<family>), model, template arguments.
+#define CFN_ARGS_KERNELS(X)                                                                             \
+    X(k_sqp_check,     sqp_check, M_NOM, false)                                                         \
+    X(k_sqp_check_par, sqp_check, M_PAR, true)                                                          \
+    X(k_sqp_check_dst, sqp_check, M_DST, true, true)                                                    \
+    X(k_sqp_ls,        sqp_ls,    M_NOM, false)                                                         \
+    X(k_sqp_ls_par,    sqp_ls,    M_PAR, true)                                                          \
+    X(k_sqp_ls_dst,    sqp_ls,    M_DST, true, true)                                                    \
+    X(k_nlp_eval,      nlp_eval,  M_NOM, false)                                                         \
+    X(k_nlp_eval_par,  nlp_eval,  M_PAR, true)                                                          \
+    X(k_nlp_eval_dst,  nlp_eval,  M_DST, true, true)
+#define CFN_PARAMS_sqp_check Params P, SqpArgs A
+#define CFN_PASS_sqp_check P, A
+#define CFN_PARAMS_sqp_ls Params P, SqpArgs A, LsArgs G
+#define CFN_PASS_sqp_ls P, A, G
+#define CFN_PARAMS_nlp_eval Params P, NlpArgs A
+#define CFN_PASS_nlp_eval P, A
+#define CFN_ARGS_KERNEL(name, family, model, ...)                                                       \
+    __global__ __launch_bounds__(64) void name(CFN_PARAMS_##family) { family##_body<__VA_ARGS__>(CFN_PASS_##family); }
+CFN_ARGS_KERNELS(CFN_ARGS_KERNEL)
+#undef CFN_ARGS_KERNEL
+struct ArgsTab {
+    void (*sqp_check[N_MODEL])(CFN_PARAMS_sqp_check);
+    void (*sqp_ls[N_MODEL])(CFN_PARAMS_sqp_ls);
+    void (*nlp_eval[N_MODEL])(CFN_PARAMS_nlp_eval);
+};
+#define CFN_CELL(name, family, model, ...) t.family[model] = name;
+static constexpr ArgsTab args_tab = [] { ArgsTab t{}; CFN_ARGS_KERNELS(CFN_CELL) return t; }();
+#undef CFN_CELL
+static_assert(filled(args_tab.sqp_check) && filled(args_tab.sqp_ls) && filled(args_tab.nlp_eval), "an NLP sweep variant has no kernel");
 
 // ---------------------------------------------------------------------------------------------
 // launchers
@@ -4196,12 +4179,7 @@ __global__ __launch_bounds__(64) void k_nlp_eval_dst(Params P, NlpArgs A) { nlp_
 static inline int imin_h(int a, int b) { return a < b ? a : b; }
 static inline int imax_h(int a, int b) { return a > b ? a : b; }
 void launch_linearise(const Params& P, int chunks, hipStream_t st) {
-    if (P.dist && P.erk_steps > 1) hipLaunchKernelGGL(k_linearise_erk_dst, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
-    else if (P.dist) hipLaunchKernelGGL(k_linearise_dst, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
-    else if (P.mpar && P.erk_steps > 1) hipLaunchKernelGGL(k_linearise_erk_par, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
-    else if (P.mpar) hipLaunchKernelGGL(k_linearise_par, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
-    else if (P.erk_steps > 1) hipLaunchKernelGGL(k_linearise_erk, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
-    else hipLaunchKernelGGL(k_linearise, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P);
+    launch_variant(linearise_tab.k[model_of(P)][erk_of(P)], "linearisation", dim3((P.NW + 15) / 16, chunks), st, P);
 }
 #ifdef CFN_DEV
 void launch_linearise_list(const Params& P, int chunks, hipStream_t st) {
@@ -4210,6 +4188,9 @@ void launch_linearise_list(const Params& P, int chunks, hipStream_t st) {
 #endif
 void launch_linearise_clist(const Params& P, int chunks, int which, hipStream_t st) {
     hipLaunchKernelGGL(k_linearise_clist, dim3((P.NW + 15) / 16, chunks), dim3(64), 0, st, P, which);
+}
+static void launch_forward(const Params& P, int sweep, hipStream_t st) {   // matrix-free sweeps, 64 instances per wave
+    launch_variant(forward_tab.k[sweep][model_of(P)][erk_of(P)], "forward sweep", dim3((P.B + 63) / 64), st, P);
 }
 // ev (optional, cfnmpc_set_profiling): events recorded after k_factor, after the forward sweep, after the compaction
 void launch_factor_only(const Params& P, hipStream_t st);
@@ -4228,18 +4209,7 @@ void launch_qp_start(const Params& P, hipStream_t st, hipEvent_t* ev, bool skip_
 #ifdef CFN_DEV
         if (P.forward_half) { hipLaunchKernelGGL(k_forward_half, dim3((P.B + 63) / 64), dim3(64), 0, st, P); } else
 #endif
-        if (P.dist) {   // (per-instance disturbance rows: the same choice among the _dst twins)
-            if (P.fwd_split) { if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p1_erk_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_forward_p1_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
-            else { if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_erk_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_forward_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
-        } else
-        if (P.mpar) {   // (per-instance model constants: the same choice among the _par twins)
-            if (P.fwd_split) { if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p1_erk_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_forward_p1_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
-            else { if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_erk_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_forward_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
-        } else
-        if (P.fwd_split && P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p1_erk, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
-        else if (P.fwd_split) hipLaunchKernelGGL(k_forward_p1, dim3((P.B + 63) / 64), dim3(64), 0, st, P);   // part two: launch_qp_ipm
-        else if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_erk, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
-        else hipLaunchKernelGGL(k_forward, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
+        launch_forward(P, P.fwd_split ? S_P1 : S_WHOLE, st);   // (S_P1: part two in launch_qp_ipm)
     }
     if (ev) (void)hipEventRecord(ev[1], st);
     hipLaunchKernelGGL(k_compact, dim3(N_BIN), dim3(256), 0, st, P);
@@ -4257,45 +4227,22 @@ void launch_factor_only(const Params& P, hipStream_t st) {
     if (!P.v4b) { std::fprintf(stderr, "cfnmpc: k_factor needs the wave-blocked 4-vector layout (not a cond_N2 solver)\n"); return; }
     hipLaunchKernelGGL(P.wtab ? k_factor_w : k_factor, dim3(P.NW), dim3(64), 0, st, P);
 }
-void launch_cforward(const Params& P, hipStream_t st) {
-    if (P.mpar) { if (P.erk_steps > 1) hipLaunchKernelGGL(k_cforward_erk_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_cforward_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
-    else if (P.erk_steps > 1) hipLaunchKernelGGL(k_cforward_erk, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
-    else hipLaunchKernelGGL(k_cforward, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
-}
-static void launch_forward_p2(const Params& P, hipStream_t st) {   // second part of the split sweep
-    if (P.dist) { if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p2_erk_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_forward_p2_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
-    else
-    if (P.mpar) { if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p2_erk_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); else hipLaunchKernelGGL(k_forward_p2_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P); }
-    else if (P.erk_steps > 1) hipLaunchKernelGGL(k_forward_p2_erk, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
-    else hipLaunchKernelGGL(k_forward_p2, dim3((P.B + 63) / 64), dim3(64), 0, st, P);
-}
+void launch_cforward(const Params& P, hipStream_t st) { launch_forward(P, S_COND, st); }
 // ev (optional): event recorded after the active-set kernels (before the interior-point launch for what they left)
 void launch_qp_ipm(const Params& P, hipStream_t st, hipEvent_t* ev) {
-    if (P.fused == 1 && !P.lbs) {
-        // fused start solve: no stored stage blocks -- the constrained instances are re-linearised into their compact
-        // store first (and the interior-point fall-back rows once more after k_ipm_list has moved them to new slots)
-        launch_linearise_clist(P, P.clist_chunks, 0, st);
-        if (P.active_set) {
-            hipLaunchKernelGGL(k_as_cst, dim3(P.NW), dim3(64), 0, st, P);   // (lists its fall-back rows itself)
-            if (ev) (void)hipEventRecord(ev[0], st);
-            if (P.ipm_listed) launch_linearise_clist(P, P.clist_chunks, 1, st);
-            hipLaunchKernelGGL(k_ipm_rest_cst, dim3(imax_h(1, imin_h(P.NW, P.as_grid / 2))), dim3(64), 0, st, P);
-        } else {
-            if (ev) (void)hipEventRecord(ev[0], st);
-            hipLaunchKernelGGL(k_ipm_cst, dim3(P.NW), dim3(64), 0, st, P);
-        }
+    const int box = box_of(P);
+    const auto qp = [&](int kind, hipStream_t on, const Params& Q) { launch_variant(qp_tab.k[kind][box][wtab_of(P)], "constrained-QP", dim3(P.NW), on, Q); };
+    // fused start solve: no stored stage blocks -- the constrained instances are re-linearised into their compact
+    // store first (and the interior-point fall-back rows once more after k_as_cst has listed them in new slots)
+    if (box == B_CST) launch_linearise_clist(P, P.clist_chunks, 0, st);
+    if (!P.active_set) {
+        if (ev) (void)hipEventRecord(ev[0], st);
+        qp(Q_IPM, st, P);
         return;
     }
-    if (P.lbs) {   // per-stage boxes: monolithic kernels instantiated for them
-        if (P.active_set) {
-            hipLaunchKernelGGL(P.wtab ? k_as_sbox_w : k_as_sbox, dim3(P.NW), dim3(64), 0, st, P);   // (lists its fall-back rows itself)
-            if (ev) (void)hipEventRecord(ev[0], st);
-            hipLaunchKernelGGL(P.wtab ? k_ipm_rest_sbox_w : k_ipm_rest_sbox, dim3(imax_h(1, imin_h(P.NW, P.as_grid / 2))), dim3(64), 0, st, P);
-        } else {
-            if (ev) (void)hipEventRecord(ev[0], st);
-            hipLaunchKernelGGL(P.wtab ? k_ipm_sbox_w : k_ipm_sbox, dim3(P.NW), dim3(64), 0, st, P);
-        }
-    } else if (P.active_set && P.as_passes != 0) {
+    // per-stage boxes and the fused start solve: the monolithic kernel instantiated for them, whatever as_passes says
+    const bool staged = box == B_PLAIN && P.as_passes != 0;
+    if (staged) {
         // as_passes > 0: level-synchronous active-set passes -- pairs (factor, forward) of one solve each, one
         // launch loops over the remaining solves in-wave; as_passes < 0: every solve in one launch.  Then commit,
         // retries over a longer head, interior point for the rest.
@@ -4316,34 +4263,25 @@ void launch_qp_ipm(const Params& P, hipStream_t st, hipEvent_t* ev) {
             const bool split = p1_ran && side && side2;
             if (side) (void)hipEventRecord((hipEvent_t)P.as_fork, st);
             if (split) {
-                Params PA = P;
-                PA.as_range = 1;
                 (void)hipStreamWaitEvent(side2, (hipEvent_t)P.as_fork, 0);
-                launch_forward_p2(P, side2);
+                launch_forward(P, S_P2, side2);
                 // (the rows with heads behind the split point -- PB's range: rare -- are left to k_as_retry below: a launch behind
                 //  part two, which is the longest chain of this group, cost 5 + 8 us per step whether it had work or not)
                 (void)hipEventRecord((hipEvent_t)P.as_join2, side2);
-                (void)hipStreamWaitEvent(side, (hipEvent_t)P.as_fork, 0);
-                hipLaunchKernelGGL(P.wtab ? k_as_solves_w : k_as_solves, dim3(P.NW), dim3(64), 0, side, PA);
-                (void)hipEventRecord((hipEvent_t)P.as_join, side);
-            } else {
-                if (p1_ran) launch_forward_p2(P, st);   // no side streams: in order
-                if (side && !p1_ran) {
-                    (void)hipStreamWaitEvent(side, (hipEvent_t)P.as_fork, 0);
-                    hipLaunchKernelGGL(P.wtab ? k_as_solves_w : k_as_solves, dim3(P.NW), dim3(64), 0, side, P);
-                    (void)hipEventRecord((hipEvent_t)P.as_join, side);
-                } else {
-                    side = nullptr;
-                    Params PA = P;
-                    PA.as_range = p1_ran ? 1 : 0;   // (behind a split sweep the same rows as with the side streams: bit-identical steps)
-                    hipLaunchKernelGGL(P.wtab ? k_as_solves_w : k_as_solves, dim3(P.NW), dim3(64), 0, st, PA);
-                }
+            } else if (p1_ran) {
+                launch_forward(P, S_P2, st);   // no side streams: in order, k_as_solves behind it
+                side = nullptr;
             }
+            Params PA = P;
+            PA.as_range = p1_ran ? 1 : 0;   // (behind a split sweep the same rows with and without the side streams: bit-identical steps)
+            if (side) (void)hipStreamWaitEvent(side, (hipEvent_t)P.as_fork, 0);
+            qp(Q_SOLVES, side ? side : st, PA);
+            if (side) (void)hipEventRecord((hipEvent_t)P.as_join, side);
             launch_as_dense(P, imax_h(1, imin_h(P.as_grid / 2, P.NW * 4)), st);
             if (side) (void)hipStreamWaitEvent(st, (hipEvent_t)P.as_join, 0);
             if (split) (void)hipStreamWaitEvent(st, (hipEvent_t)P.as_join2, 0);
         } else if (P.as_passes == -2) {
-            hipLaunchKernelGGL(P.wtab ? k_as_solves_w : k_as_solves, dim3(P.NW), dim3(64), 0, st, P);
+            qp(Q_SOLVES, st, P);
         }
 #ifdef CFN_DEV
         else if (P.as_passes < 0) {
@@ -4364,18 +4302,14 @@ void launch_qp_ipm(const Params& P, hipStream_t st, hipEvent_t* ev) {
         // (late rows of a split forward sweep: k_as_retry and k_ipm_rest count them in, P.nipm[0] + P.nipm[NI_LATE].  Tried: both modes in
         //  ONE launch for small fleets, where each normally finds nothing to do and an empty launch costs 5 - 7 us -- either half
         //  alone runs, the combined kernel aborts on the device; not pursued)
-        hipLaunchKernelGGL(P.wtab ? k_as_retry_w : k_as_retry, dim3(P.NW), dim3(64), 0, st, P);
-        if (ev) (void)hipEventRecord(ev[0], st);
-        if (P.ipm_listed) hipLaunchKernelGGL(k_ipm_list, dim3(1), dim3(1024), 0, st, P);
-        hipLaunchKernelGGL(P.wtab ? k_ipm_rest_w : k_ipm_rest, dim3(imax_h(1, imin_h(P.NW, P.as_grid / 2))), dim3(64), 0, st, P);
-    } else if (P.active_set) {
-        hipLaunchKernelGGL(P.wtab ? k_as_w : k_as, dim3(P.NW), dim3(64), 0, st, P);   // (lists its fall-back rows itself)
-        if (ev) (void)hipEventRecord(ev[0], st);
-        hipLaunchKernelGGL(P.wtab ? k_ipm_rest_w : k_ipm_rest, dim3(imax_h(1, imin_h(P.NW, P.as_grid / 2))), dim3(64), 0, st, P);
+        qp(Q_RETRY, st, P);
     } else {
-        if (ev) (void)hipEventRecord(ev[0], st);
-        hipLaunchKernelGGL(P.wtab ? k_ipm_w : k_ipm, dim3(P.NW), dim3(64), 0, st, P);
+        qp(Q_AS, st, P);   // (lists its fall-back rows itself)
     }
+    if (ev) (void)hipEventRecord(ev[0], st);
+    if (staged && P.ipm_listed) hipLaunchKernelGGL(k_ipm_list, dim3(1), dim3(1024), 0, st, P);
+    if (box == B_CST && P.ipm_listed) launch_linearise_clist(P, P.clist_chunks, 1, st);
+    launch_variant(qp_tab.k[Q_REST][box][wtab_of(P)], "constrained-QP", dim3(imax_h(1, imin_h(P.NW, P.as_grid / 2))), st, P);
 }
 void launch_qp(const Params& P, hipStream_t st, hipEvent_t* ev) {
     launch_qp_start(P, st, ev);
@@ -4429,23 +4363,16 @@ void launch_reinit_failed(const Params& P, hipStream_t st) {
     hipLaunchKernelGGL(k_reinit_failed, dim3((P.B + 255) / 256), dim3(256), 0, st, P);
 }
 void launch_sqp_check(const Params& P, const SqpArgs& A, hipStream_t st) {
-    if (P.dist) hipLaunchKernelGGL(k_sqp_check_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
-    else if (P.mpar) hipLaunchKernelGGL(k_sqp_check_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
-    else hipLaunchKernelGGL(k_sqp_check, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
+    hipLaunchKernelGGL(args_tab.sqp_check[model_of(P)], dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
 }
 void launch_sqp_ls(const Params& P, const SqpArgs& A, const LsArgs& G, hipStream_t st) {
-    if (P.dist) hipLaunchKernelGGL(k_sqp_ls_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A, G);
-    else if (P.mpar) hipLaunchKernelGGL(k_sqp_ls_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A, G);
-    else hipLaunchKernelGGL(k_sqp_ls, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A, G);
+    hipLaunchKernelGGL(args_tab.sqp_ls[model_of(P)], dim3((P.B + 63) / 64), dim3(64), 0, st, P, A, G);
 }
 void launch_nlp_eval(const Params& P, const NlpArgs& A, hipStream_t st) {
-    if (P.dist) hipLaunchKernelGGL(k_nlp_eval_dst, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
-    else if (P.mpar) hipLaunchKernelGGL(k_nlp_eval_par, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
-    else hipLaunchKernelGGL(k_nlp_eval, dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
+    hipLaunchKernelGGL(args_tab.nlp_eval[model_of(P)], dim3((P.B + 63) / 64), dim3(64), 0, st, P, A);
 }
 void launch_init_iterate(const Params& P, int mode, hipStream_t st) {
-    if (P.mpar) hipLaunchKernelGGL(k_init_iterate_par, dim3((P.B + 255) / 256), dim3(256), 0, st, P, mode);
-    else hipLaunchKernelGGL(k_init_iterate, dim3((P.B + 255) / 256), dim3(256), 0, st, P, mode);
+    hipLaunchKernelGGL(P.mpar ? k_init_iterate_par : k_init_iterate, dim3((P.B + 255) / 256), dim3(256), 0, st, P, mode);
 }
 
 }  // namespace cfn
