@@ -33,6 +33,8 @@ SYMBOLS = [
     "cfnmpc_set_weights_batch", "cfnmpc_get_weights_batch", "cfnmpc_fleet_set_weights_batch", "cfnmpc_multi_set_weights_batch",
     "cfnmpc_eval_sens_x0", "cfnmpc_get_sens_x0", "cfnmpc_get_sens_active", "cfnmpc_fleet_eval_sens_x0", "cfnmpc_fleet_get_sens_x0",
     "cfnmpc_multi_eval_sens_x0", "cfnmpc_multi_get_sens_x0",
+    "cfnmpc_eval_adjoint", "cfnmpc_get_adjoint", "cfnmpc_get_adjoint_cost", "cfnmpc_fleet_eval_adjoint", "cfnmpc_fleet_get_adjoint",
+    "cfnmpc_multi_eval_adjoint", "cfnmpc_multi_get_adjoint",
     "cfnmpc_eval_nlp", "cfnmpc_get_nlp_stats", "cfnmpc_get_nlp_multipliers", "cfnmpc_fleet_eval_nlp", "cfnmpc_fleet_get_nlp_stats",
     "cfnmpc_multi_eval_nlp", "cfnmpc_multi_get_nlp_stats",
     "cfnmpc_set_uncertainty", "cfnmpc_set_uncertainty_gain", "cfnmpc_eval_uncertainty", "cfnmpc_get_backoff", "cfnmpc_get_uncertainty",
@@ -115,6 +117,13 @@ def lib():
     L.cfnmpc_eval_sens_x0.argtypes = [vp, dbl, vp]
     L.cfnmpc_get_sens_x0.argtypes = [vp, i32, i32, vp, vp, i32, vp]
     L.cfnmpc_get_sens_active.argtypes = [vp, vp, i32, vp]
+    L.cfnmpc_eval_adjoint.argtypes = [vp, vp, i32, vp, i32, i32, vp]
+    L.cfnmpc_get_adjoint.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp]
+    L.cfnmpc_get_adjoint_cost.argtypes = [vp, vp, vp, vp, vp, i32, vp]
+    L.cfnmpc_fleet_eval_adjoint.argtypes = [vp, vp, vp, i32, i32, vp]
+    L.cfnmpc_fleet_get_adjoint.argtypes = [vp, vp, vp, vp, i32, vp]
+    L.cfnmpc_multi_eval_adjoint.argtypes = [vp, vp, vp, i32]
+    L.cfnmpc_multi_get_adjoint.argtypes = [vp, vp, vp, vp]
     L.cfnmpc_fleet_eval_sens_x0.argtypes = [vp, dbl, vp]
     L.cfnmpc_fleet_get_sens_x0.argtypes = [vp, i32, i32, vp, vp, i32, vp]
     L.cfnmpc_multi_eval_sens_x0.argtypes = [vp, dbl]

@@ -92,6 +92,11 @@ struct cfnmpc_solver {
     cfn::SensArgs sens;
     double* sens_stage;
     size_t sens_stage_doubles;
+    // adjoint sensitivities (cfnmpc_eval_adjoint): the buffers (allocated at the first evaluation; adj_gx / adj_gu hold the
+    // gradients a caller hands over as host arrays) and whether an evaluation belongs to the sensitivity evaluation in force
+    cfn::AdjArgs adj;
+    double *adj_gx, *adj_gu;
+    bool adj_valid;
     // NLP evaluation (cfnmpc_eval_nlp): cost [B] and residuals [B][3] (allocated with the solver), costates and reduced gradient
     // (allocated at the first evaluation that keeps them), and what the last evaluation left (0: none yet, 1: cost and residuals,
     // 2: the multipliers too)
@@ -748,7 +753,7 @@ int cfnmpc_eval_poly(cfnmpc_solver* s, double t, int n_stages, int flags, double
 // kernel arguments changed (weights, box): the captured steps hold the old ones
 static void invalidate_graphs(cfnmpc_solver* s) { s->gvalid[0] = s->gvalid[1] = false; }
 // the QP's data changed since the last solve: no sensitivities until the next one
-static void invalidate_sens(cfnmpc_solver* s) { s->sens_src = 0; s->sens_valid = false; s->unc.current = false; }
+static void invalidate_sens(cfnmpc_solver* s) { s->sens_src = 0; s->sens_valid = false; s->adj_valid = false; s->unc.current = false; }
 
 // The four blocks of the per-stage boxes (home lb / ub, compact lb / ub; cfnmpc_set_box_stages, cfnmpc_tighten_box).
 static int ensure_box_blocks(cfnmpc_solver* s) {
@@ -1585,6 +1590,7 @@ int cfnmpc_eval_sens_x0(cfnmpc_solver* s, double act_tol, void* stream) {
         A = a;
     }
     s->sens_valid = false;
+    s->adj_valid = false;
     A.tol = act_tol;
     cfn::launch_sens_eval(s->P, A, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
@@ -1629,6 +1635,76 @@ int cfnmpc_get_sens_active(cfnmpc_solver* s, signed char* act, int on_device, vo
     if (!s || !act || !s->sens_valid) return CFNMPC_EINVAL;
     DeviceGuard dg(s->device);
     return copy_out({{act, s->sens.mask, (size_t)s->P.B * s->P.N * 4}}, on_device, (hipStream_t)stream);
+}
+
+// ---- adjoint solution sensitivities --------------------------------------------------------------
+int cfnmpc_eval_adjoint(cfnmpc_solver* s, const double* gx, int n_gx, const double* gu, int n_gu, int on_device, void* stream) {
+    // the sensitivity evaluation is the one source of the active set: whatever refuses or invalidates it refuses this call
+    if (!s || !s->sens_valid) return CFNMPC_EINVAL;
+    const size_t N = s->P.N, B = s->P.B;
+    if ((gx && (n_gx < 1 || (size_t)n_gx > N + 1)) || (gu && (n_gu < 1 || (size_t)n_gu > N))) return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    hipStream_t st = (hipStream_t)stream;
+    cfn::AdjArgs& A = s->adj;
+    if (!A.kap) {
+        cfn::AdjArgs a{};
+        int rc = dev_alloc(s, &a.kap, B * N * 4);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &a.wuni, 32);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &a.dq, B * (N + 1) * 13);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &a.dr, B * N * 4);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &a.dx0, B * 13);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &a.db, B * N * 13);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &a.dbox, B * N * 4);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &a.dW, B * 17);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &a.dWN, B * 13);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &a.dyref, B * N * 17);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &a.dyref_e, B * 13);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->adj_gx, B * (N + 1) * 13);
+        if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->adj_gu, B * N * 4);
+        if (rc != CFNMPC_OK) return rc;   // (what was allocated stays with the solver; the next call allocates again)
+        A = a;
+    }
+    s->adj_valid = false;
+    A.gx = gx; A.gu = gu;
+    A.n_gx = gx ? n_gx : 0; A.n_gu = gu ? n_gu : 0;
+    if (is_host(on_device)) {   // (the solver's own copies: the sweeps read them after this call has returned)
+        if (gx) {
+            HIP_TRY(hipMemcpyAsync(s->adj_gx, gx, B * n_gx * 13 * sizeof(double), hipMemcpyHostToDevice, st));
+            A.gx = s->adj_gx;
+        }
+        if (gu) {
+            HIP_TRY(hipMemcpyAsync(s->adj_gu, gu, B * n_gu * 4 * sizeof(double), hipMemcpyHostToDevice, st));
+            A.gu = s->adj_gu;
+        }
+    }
+    A.mask = s->sens.mask; A.kst = s->sens.kst; A.K = s->sens.K;
+    A.status = s->sens_src == 2 ? s->sqp.status : s->P.status;
+    A.stage_scale = s->stage_scale; A.terminal_scale = s->terminal_scale;
+    cfn::launch_adjoint(s->P, A, st);
+    HIP_TRY(hipGetLastError());
+    if (on_device == CFNMPC_ON_HOST) HIP_TRY(hipStreamSynchronize(st));   // (the caller's arrays are free again)
+    s->adj_valid = true;
+    return CFNMPC_OK;
+}
+
+int cfnmpc_get_adjoint(cfnmpc_solver* s, double* dl_dx0, double* dl_dq, double* dl_dr, double* dl_db, double* dl_dbox, int on_device,
+                       void* stream) {
+    if (!s || !s->adj_valid) return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    const size_t N = s->P.N, B = s->P.B, d = sizeof(double);
+    const cfn::AdjArgs& A = s->adj;
+    return copy_out({{dl_dx0, A.dx0, B * 13 * d}, {dl_dq, A.dq, B * (N + 1) * 13 * d}, {dl_dr, A.dr, B * N * 4 * d},
+                     {dl_db, A.db, B * N * 13 * d}, {dl_dbox, A.dbox, B * N * 4 * d}}, on_device, (hipStream_t)stream);
+}
+
+int cfnmpc_get_adjoint_cost(cfnmpc_solver* s, double* dl_dW, double* dl_dWN, double* dl_dyref, double* dl_dyref_e, int on_device,
+                            void* stream) {
+    if (!s || !s->adj_valid) return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    const size_t N = s->P.N, B = s->P.B, d = sizeof(double);
+    const cfn::AdjArgs& A = s->adj;
+    return copy_out({{dl_dW, A.dW, B * 17 * d}, {dl_dWN, A.dWN, B * 13 * d}, {dl_dyref, A.dyref, B * N * 17 * d},
+                     {dl_dyref_e, A.dyref_e, B * 13 * d}}, on_device, (hipStream_t)stream);
 }
 
 // ---- uncertainty propagation and robust input-bound tightening -----------------------------------

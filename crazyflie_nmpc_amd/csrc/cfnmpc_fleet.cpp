@@ -453,6 +453,23 @@ int cfnmpc_fleet_get_sens_x0(cfnmpc_fleet* f, int stage, int n_stages, double* d
                       [&](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_get_sens_x0(b.s, stage, n_stages, p.d(0), p.d(1), mode, st); });
 }
 
+// ---- adjoint sensitivities (include/cfnmpc.h: cfnmpc_eval_adjoint) -----------------------------------
+int cfnmpc_fleet_eval_adjoint(cfnmpc_fleet* f, const double* gx, const double* gu, int n_g, int on_device, void* stream) {
+    // (stages [0, n_g) below the shortest horizon: a terminal gradient would sit at another stage in every bucket)
+    if (!f || (!gx && !gu) || n_g < 1 || n_g > f->Nmin) return CFNMPC_EINVAL;
+    return fleet_write(f, on_device, stream, {col(gx, (size_t)n_g * 13), col(gu, (size_t)n_g * 4)},
+                       [&](Bucket& b, Staged p, int mode, void* st) { return cfnmpc_eval_adjoint(b.s, p.d(0), n_g, p.d(1), n_g, mode, st); });
+}
+
+int cfnmpc_fleet_get_adjoint(cfnmpc_fleet* f, double* dl_dx0, double* dl_dW, double* dl_dWN, int on_device, void* stream) {
+    if (!f || (!dl_dx0 && !dl_dW && !dl_dWN)) return CFNMPC_EINVAL;
+    return fleet_read(f, on_device, stream, {col(dl_dx0, 13), col(dl_dW, 17), col(dl_dWN, 13)},
+                      [](Bucket& b, Staged p, int mode, void* st) {
+                          RC_TRY(cfnmpc_get_adjoint(b.s, p.d(0), nullptr, nullptr, nullptr, nullptr, mode, st));
+                          return cfnmpc_get_adjoint_cost(b.s, p.d(1), p.d(2), nullptr, nullptr, mode, st);
+                      });
+}
+
 // ---- uncertainty propagation and bound tightening (include/cfnmpc.h: cfnmpc_eval_uncertainty) --------
 // host arrays are validated as a whole first: a bad matrix leaves every bucket unchanged
 int cfnmpc_fleet_set_uncertainty(cfnmpc_fleet* f, const double* Sigma0, const double* W, int on_device, void* stream) {

@@ -4378,5 +4378,6 @@ void launch_init_iterate(const Params& P, int mode, hipStream_t st) {
 }  // namespace cfn
 
 #include "cfnmpc_sens.hpp"
+#include "cfnmpc_adj.hpp"
 #include "cfnmpc_unc.hpp"
 #include "cfnmpc_poly.hpp"

@@ -381,6 +381,25 @@ int cfnmpc_multi_get_sens_x0(cfnmpc_multi* m, int stage, int n_stages, double* d
                       [&](Shard& s, Staged p, int mode) { return cfnmpc_fleet_get_sens_x0(s.f, stage, n_stages, p.d(0), p.d(1), mode, s.st); });
 }
 
+// ---- adjoint sensitivities (host arrays over the whole fleet, caller's order; synchronous) -----------------------------------
+int cfnmpc_multi_eval_adjoint(cfnmpc_multi* m, const double* gx, const double* gu, int n_g) {
+    const int Nlim = m ? (m->mixed ? m->Nmin : m->N) : 0;
+    if (!m || (!gx && !gu) || n_g < 1 || n_g > Nlim) return CFNMPC_EINVAL;
+    return multi_write(m, {col(gx, (size_t)n_g * 13), col(gu, (size_t)n_g * 4)},
+                       [&](Shard& s, Staged p, int mode) { return cfnmpc_eval_adjoint(s.s, p.d(0), n_g, p.d(1), n_g, mode, s.st); },
+                       [&](Shard& s, Staged p, int mode) { return cfnmpc_fleet_eval_adjoint(s.f, p.d(0), p.d(1), n_g, mode, s.st); });
+}
+
+int cfnmpc_multi_get_adjoint(cfnmpc_multi* m, double* dl_dx0, double* dl_dW, double* dl_dWN) {
+    if (!m || (!dl_dx0 && !dl_dW && !dl_dWN)) return CFNMPC_EINVAL;
+    return multi_read(m, {col(dl_dx0, 13), col(dl_dW, 17), col(dl_dWN, 13)},
+                      [](Shard& s, Staged p, int mode) {
+                          RC_TRY(cfnmpc_get_adjoint(s.s, p.d(0), nullptr, nullptr, nullptr, nullptr, mode, s.st));
+                          return cfnmpc_get_adjoint_cost(s.s, p.d(1), p.d(2), nullptr, nullptr, mode, s.st);
+                      },
+                      [](Shard& s, Staged p, int mode) { return cfnmpc_fleet_get_adjoint(s.f, p.d(0), p.d(1), p.d(2), mode, s.st); });
+}
+
 // ---- uncertainty propagation and bound tightening (host arrays over the whole fleet, caller's order; synchronous) ------------
 int cfnmpc_multi_set_uncertainty(cfnmpc_multi* m, const double* Sigma0, const double* W) {
     if (!m) return CFNMPC_EINVAL;

@@ -74,9 +74,13 @@ __device__ __forceinline__ int chk_index(int k) {
 // One stage of the masked homogeneous recursion (factor_stage's arithmetic without the affine row).  Pa: lanes 0..12 row i
 // of P_{k+1} -> P_k; fa[a]: input a of this row's instance is active (row-uniform); rh: R_a in lanes a < 4.  Returns the
 // transposed gain in Kp (lane l < 13: K[a][l]), exact zeros for the active inputs.
+// AFF (cfnmpc_adj.hpp): lane 13 carries an affine row p' as factor_stage's does -- qv: its linear state term in lanes j < 13,
+// g: its linear input term in lanes a < 4; on exit lane 13 of Pa holds p_k' and lane 13 of Kp the feed-forward S_FF^{-1} rho_F
+// (exact zeros on the active inputs).  Lanes 0..12 see the same instructions either way.
+template <bool AFF = false>
 __device__ __forceinline__ void sens_stage(const Lane& t, double (&Pa)[13], const double (&ar)[10], const double (&br)[4],
                                            const bool (&fa)[4], const double rh, const double wq, double* wt, double* sb,
-                                           double (&Kp)[4]) {
+                                           double (&Kp)[4], const double is13 = 0.0, const double qv = 0.0, const double g = 0.0) {
     // (1) W = Pa A (row form), (2) V = Pa B
     double W[13], V[4];
     SFOR(j, 0, 3, { W[j] = Pa[j]; });
@@ -107,11 +111,13 @@ __device__ __forceinline__ void sens_stage(const Lane& t, double (&Pa)[13], cons
     double S[10], Si[10];
     SFOR(a, 0, 4, { SFOR(c, a, 4, { S[s4(a, c)] = bc<a>(Srow[c]); }); });
     SFOR(l, 0, 13, { pin(Wt[l]); });
+    if (AFF) SFOR(l, 0, 13, { Wt[l] = t.L == 13 ? Pa[l] : Wt[l]; });
     Chol4 ch;
     chol4_pivot<0>(S, ch);
     // (5) M = Q + Wt A
     double M[13];
     SFOR(j, 0, 13, { M[j] = (t.L == j) ? wq : 0.0; });
+    if (AFF) rank1bc<13>(M, is13, qv);
     SFOR(j, 0, 3, { M[j] += Wt[j]; });
     dot3bc<6>(M[3], M[4], M[5], Wt, ar[0], ar[1], ar[2]);
     chol4_pivot<1>(S, ch);
@@ -123,6 +129,7 @@ __device__ __forceinline__ void sens_stage(const Lane& t, double (&Pa)[13], cons
     double Gp[4];
     SFOR(a, 0, 4, { Gp[a] = 0.0; });
     dot4bc<13>(Gp[0], Gp[1], Gp[2], Gp[3], Wt, br[0], br[1], br[2], br[3]);
+    if (AFF) rank1bc<4>(Gp, is13, g);
     chol4_finish(ch, Si);
     // (7) K' = G' Sinv, active columns exactly zero
     double nGp[4];

@@ -308,6 +308,24 @@ struct SensArgs {
 void launch_sens_eval(const Params& P, const SensArgs& A, hipStream_t st);
 // forward propagation for the rows [A.b0, A.b0 + A.nb) into A.du / A.dx
 void launch_sens_fwd(const Params& P, const SensArgs& A, hipStream_t st);
+// adjoint solution sensitivities (cfnmpc_eval_adjoint / cfnmpc_get_adjoint / cfnmpc_get_adjoint_cost; kernels: cfnmpc_adj.hpp,
+// DESIGN.md section 5.24): buffers owned by the solver, allocated at its first evaluation (not part of Params: no RTI kernel
+// sees them).  Every output is instance-major in the public state order, as the getters hand it out.
+struct AdjArgs {
+    const double *gx, *gu;     // the loss gradients [B][n_gx][13], [B][n_gu][4] (public order); NULL: zero
+    int n_gx, n_gu;            // stages they cover, <= N + 1 / <= N (zero behind)
+    const signed char* mask;   // SensArgs.mask, kst, K of the evaluation this one belongs to
+    const int* kst;
+    const double* K;
+    const int* status;         // [B] status of the last solve (4: NaN outputs)
+    double* kap;               // [B][N][4] feed-forward of the first sweep (written for the stages it covers)
+    double* wuni;              // [32] the uniform effective weights as one row of Params.wtab's layout (read while wtab is NULL)
+    double *dq, *dr;           // [B][N + 1][13], [B][N][4]: dl/dq_k = ax_k, dl/dr_k = au_k
+    double *dx0, *db, *dbox;   // [B][13], [B][N][13], [B][N][4]
+    double *dW, *dWN, *dyref, *dyref_e;   // [B][17], [B][13], [B][N][17], [B][13]
+    double stage_scale, terminal_scale;   // cfnmpc_set_cost_scaling: dW / dWN are with respect to the unscaled rows
+};
+void launch_adjoint(const Params& P, const AdjArgs& A, hipStream_t st);
 // uncertainty propagation and robust input-bound tightening (cfnmpc_eval_uncertainty / cfnmpc_tighten_box; kernels:
 // cfnmpc_unc.hpp): buffers owned by the solver, allocated at the first call that needs them
 struct UncArgs {

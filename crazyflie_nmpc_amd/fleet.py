@@ -259,6 +259,34 @@ class MixedHorizonFleet(UncertaintyCalls, PolyCalls):
         return sens_x0_call(self, self.Nmin, self._L.cfnmpc_fleet_get_sens_x0, "cfnmpc_fleet_get_sens_x0", stage, n_stages,
                             out_u, out_x)
 
+    def eval_adjoint(self, gx=None, gu=None, stream=None):
+        """cfnmpc_fleet_eval_adjoint: adjoint sensitivities of every bucket's last QP, after eval_sens_x0.  gx [B, n_g, 13],
+        gu [B, n_g, 4] (numpy or device tensors, one n_g <= Nmin; one of them may be None): the loss gradients for the
+        stages [0, n_g), in the fleet's vehicle order"""
+        if gx is None and gu is None:
+            raise ValueError("gx or gu must be given")
+        n_g = int((gx if gx is not None else gu).shape[1])
+        px, pu, dev, st, keep = None, None, 0, None, []
+        if gx is not None:
+            px, dev, st, k = _arg(gx, (self.B, n_g, NX), device=self._device); keep.append(k)
+        if gu is not None:
+            pu, devu, st, k = _arg(gu, (self.B, n_g, NU), device=self._device); keep.append(k)
+            if gx is not None and devu != dev:
+                raise ValueError("gx and gu must both be host arrays or both device tensors")
+            dev = devu
+        if stream:
+            st = C.c_void_p(stream)
+        _check(self._L.cfnmpc_fleet_eval_adjoint(self._h, px, pu, n_g, dev, st), "cfnmpc_fleet_eval_adjoint")
+
+    def adjoint(self):
+        """-> (dl_dx0 [B, 13], dl_dW [B, 17], dl_dWN [B, 13]) of the last eval_adjoint, in the fleet's vehicle order (the
+        per-stage outputs: through the buckets' solvers)"""
+        d0, dW, dWN = np.empty((self.B, NX)), np.empty((self.B, NY)), np.empty((self.B, NX))
+        vp = C.c_void_p
+        _check(self._L.cfnmpc_fleet_get_adjoint(self._h, d0.ctypes.data_as(vp), dW.ctypes.data_as(vp), dWN.ctypes.data_as(vp), 0,
+                                                _launch_stream(None, self._device)), "cfnmpc_fleet_get_adjoint")
+        return d0, dW, dWN
+
     def get_x(self, stage, out=None):
         if out is None:
             out = np.empty((self.B, NX))

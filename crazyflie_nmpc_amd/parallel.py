@@ -241,6 +241,26 @@ class MultiGpuFleet:
                                                      dx.ctypes.data_as(C.c_void_p)), "cfnmpc_multi_get_sens_x0")
         return du, dx
 
+    def eval_adjoint(self, gx=None, gu=None):
+        """cfnmpc_multi_eval_adjoint: adjoint sensitivities of every shard's last QP, after eval_sens_x0 (synchronous).  Host
+        arrays gx [B, n_g, 13], gu [B, n_g, 4] in the caller's order (one of them may be None), one n_g <= the shortest
+        horizon"""
+        if gx is None and gu is None:
+            raise ValueError("gx or gu must be given")
+        vp = self._C.c_void_p
+        n_g = int(np.shape(gx if gx is not None else gu)[1])
+        a = None if gx is None else self._p(gx, (self.B, n_g, 13))
+        b = None if gu is None else self._p(gu, (self.B, n_g, 4))
+        self._check(self._L.cfnmpc_multi_eval_adjoint(self._h, a[1] if a else vp(0), b[1] if b else vp(0), n_g), "cfnmpc_multi_eval_adjoint")
+
+    def adjoint(self):
+        """-> (dl_dx0 [B, 13], dl_dW [B, 17], dl_dWN [B, 13]) of the last eval_adjoint, host arrays in the caller's order"""
+        vp = self._C.c_void_p
+        d0, dW, dWN = np.empty((self.B, 13)), np.empty((self.B, 17)), np.empty((self.B, 13))
+        self._check(self._L.cfnmpc_multi_get_adjoint(self._h, d0.ctypes.data_as(vp), dW.ctypes.data_as(vp), dWN.ctypes.data_as(vp)),
+                    "cfnmpc_multi_get_adjoint")
+        return d0, dW, dWN
+
     # ---- uncertainty propagation and bound tightening (BatchSolver.set_uncertainty ...; host arrays over the whole fleet, synchronous;
     # the full covariance is read through the shards' own solvers)
     def set_uncertainty(self, Sigma0=None, W=None):

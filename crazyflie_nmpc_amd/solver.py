@@ -531,6 +531,60 @@ class BatchSolver(UncertaintyCalls, PolyCalls):
                "cfnmpc_get_sens_active")
         return a
 
+    def eval_adjoint(self, gx=None, gu=None, stream=None):
+        """Adjoint sensitivities of the last QP (include/cfnmpc.h: cfnmpc_eval_adjoint), after eval_sens_x0: gx [B, n_gx, 13] =
+        dl/dx_k for the stages k < n_gx <= N + 1, gu [B, n_gu, 4] = dl/du_k for k < n_gu <= N (numpy or torch device tensors;
+        None or stages behind: zero).  Read with adjoint() / adjoint_cost()."""
+        if gx is not None and gu is not None and _is_torch(gx) != _is_torch(gu):
+            raise ValueError("gx and gu must both be host arrays or both device tensors")
+        px, pu, nx, nu, dev, st, keep = None, None, 0, 0, 0, _launch_stream(stream, self._device), []
+        if gx is not None:
+            nx = int(gx.shape[1]) if len(gx.shape) == 3 else -1
+            px, dev, st, k = _arg(gx, (self.B, nx, NX), device=self._device); keep.append(k)
+        if gu is not None:
+            nu = int(gu.shape[1]) if len(gu.shape) == 3 else -1
+            pu, dev, st, k = _arg(gu, (self.B, nu, NU), device=self._device); keep.append(k)
+        if stream:
+            st = C.c_void_p(stream)
+        _check(self._L.cfnmpc_eval_adjoint(self._h, px, nx, pu, nu, dev, st), "cfnmpc_eval_adjoint")
+
+    def _adjoint_get(self, fn, what, shapes, out):
+        """shared body of adjoint() / adjoint_cost(): out = None -> new host arrays; else a tuple of numpy arrays or torch device
+        tensors of those shapes (None entries are not read; device tensors are filled on torch's current stream)"""
+        if out is None:
+            out = tuple(np.empty(sh) for sh in shapes)
+        if len(out) != len(shapes):
+            raise ValueError(f"expected {len(shapes)} outputs")
+        ptrs, dev, st, keep = [], None, _launch_stream(None, self._device), []
+        for o, sh in zip(out, shapes):
+            if o is None:
+                ptrs.append(None)
+                continue
+            if not _is_torch(o) and not (isinstance(o, np.ndarray) and o.dtype == np.float64 and o.flags.c_contiguous):
+                raise ValueError("outputs must be contiguous float64 numpy arrays or torch device tensors")
+            p, d, s_, k = _arg(o, sh, device=self._device)
+            if dev is not None and d != dev:
+                raise ValueError("outputs must all be host arrays or all device tensors")
+            dev, st = d, s_
+            ptrs.append(p); keep.append(k)
+        _check(fn(self._h, *ptrs, dev or 0, st), what)
+        return tuple(out)
+
+    def adjoint(self, out=None):
+        """-> (dl_dx0 [B, 13], dl_dq [B, N + 1, 13], dl_dr [B, N, 4], dl_db [B, N, 13], dl_dbox [B, N, 4]) of the last
+        eval_adjoint: the gradients with respect to x0, the QP's linear cost terms, its defects and the bounds of the active
+        inputs (public state order)."""
+        B, N = self.B, self.N
+        return self._adjoint_get(self._L.cfnmpc_get_adjoint, "cfnmpc_get_adjoint",
+                                 ((B, NX), (B, N + 1, NX), (B, N, NU), (B, N, NX), (B, N, NU)), out)
+
+    def adjoint_cost(self, out=None):
+        """-> (dl_dW [B, 17], dl_dWN [B, 13], dl_dyref [B, N, 17], dl_dyref_e [B, 13]) of the last eval_adjoint; the weight
+        gradients are with respect to the unscaled rows of weights_batch()."""
+        B, N = self.B, self.N
+        return self._adjoint_get(self._L.cfnmpc_get_adjoint_cost, "cfnmpc_get_adjoint_cost",
+                                 ((B, NY), (B, NX), (B, N, NY), (B, NX)), out)
+
     def step_host(self, x0, yref, yref_e, stream=None):
         """cfnmpc_step_host: host arrays in (x0 [B,13], yref [B,N,17], yref_e [B,13]), one RTI step,
         host arrays out -> (u [B,N,4], x [B,N+1,13], status, qp_iter, res); one synchronisation."""
@@ -585,10 +639,14 @@ class BatchSolver(UncertaintyCalls, PolyCalls):
         return K, d, Pc, st
 
     # ---- outputs
-    def get_iterate(self):
-        x = np.empty((self.B, self.N + 1, NX)); u = np.empty((self.B, self.N, NU))
-        _check(self._L.cfnmpc_get_iterate(self._h, x.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p), 0,
-                                          _launch_stream(None, self._device)), "cfnmpc_get_iterate")
+    def get_iterate(self, out=None):
+        """-> (x [B, N + 1, 13], u [B, N, 4]); out: a pair of numpy arrays or torch device tensors of those shapes"""
+        x, u = out if out is not None else (np.empty((self.B, self.N + 1, NX)), np.empty((self.B, self.N, NU)))
+        px, dev, st, _k = _arg(x, (self.B, self.N + 1, NX), device=self._device)
+        pu, devu, _s, _k2 = _arg(u, (self.B, self.N, NU), device=self._device)
+        if dev != devu or (dev == 0 and not (x.flags.c_contiguous and u.flags.c_contiguous and x.dtype == u.dtype == np.float64)):
+            raise ValueError("x and u must both be contiguous float64 host arrays or both device tensors")
+        _check(self._L.cfnmpc_get_iterate(self._h, px, pu, dev, st), "cfnmpc_get_iterate")
         return x, u
 
     def get_u(self, stage, out=None):

@@ -504,6 +504,31 @@ int cfnmpc_get_sens_x0(cfnmpc_solver *s, int stage, int n_stages, double *du /*[
                        double *dx /*[B][n_stages][13][13] or NULL*/, int on_device, void *stream);
 int cfnmpc_get_sens_active(cfnmpc_solver *s, signed char *act /*[B][N][4]*/, int on_device, void *stream);
 
+/* Adjoint solution sensitivities (acados' eval_solution_sens_adjoint for a whole fleet): the gradient of
+ * a caller's loss l on the last QP's solution z = (x_0..x_N, u_0..u_{N-1}) with respect to that QP's data, with the active set
+ * of cfnmpc_eval_sens_x0 held.  In an RTI step A_k, B_k, b_k belong to the previous iterate, so this is the exact gradient of
+ * the RTI map on its active set.  One evaluation = three sweeps over the stored blocks, whatever the number of outputs read.
+ *   cfnmpc_eval_adjoint: gx [B][n_gx][13] = dl/dx_k for the stages k < n_gx (<= N + 1), gu [B][n_gu][4] = dl/du_k for k < n_gu
+ *     (<= N), public state order; gradients behind are zero, a NULL array is all zero.  Needs a valid cfnmpc_eval_sens_x0 of the
+ *     same solve (the one source of the active set and of act_tol): CFNMPC_EINVAL wherever that call is refused or has been
+ *     invalidated (no solve, data changed since, cond_N2 > 0, start_solve = 2, a globalised cfnmpc_solve_sqp) and for
+ *     n_gx / n_gu outside their ranges.  Device arrays are read on `stream` (keep them until it has passed); host arrays are
+ *     copied first.  Writes nothing that a solve, getter or option reads; its buffers are allocated at the first call
+ *     (cfnmpc_workspace_bytes counts them from then on).  A row whose status is 4 gets NaN in every output.
+ *   cfnmpc_get_adjoint (any output may be NULL), with q_k / r_k the linear cost terms of the QP, b_k its defects:
+ *     dl_dx0 [B][13]; dl_dq [B][N + 1][13] and dl_dr [B][N][4] (dl_dr is exactly 0 on active inputs); dl_db [B][N][13];
+ *     dl_dbox [B][N][4]: with respect to the bound an active input sits on, exactly 0 on free inputs.
+ *   cfnmpc_get_adjoint_cost (any may be NULL): dl_dW [B][17] and dl_dWN [B][13] with respect to the UNSCALED weights
+ *     (cfnmpc_get_weights_batch's rows, or the uniform ones: then the row of every vehicle with respect to its own copy);
+ *     dl_dyref [B][N][17], dl_dyref_e [B][13].
+ * CFNMPC_EINVAL for both getters without an evaluation since the last cfnmpc_eval_sens_x0. */
+int cfnmpc_eval_adjoint(cfnmpc_solver *s, const double *gx /*[B][n_gx][13] or NULL*/, int n_gx /*<= N+1*/,
+                        const double *gu /*[B][n_gu][4] or NULL*/, int n_gu /*<= N*/, int on_device, void *stream);
+int cfnmpc_get_adjoint(cfnmpc_solver *s, double *dl_dx0 /*[B][13]*/, double *dl_dq /*[B][N+1][13]*/, double *dl_dr /*[B][N][4]*/,
+                       double *dl_db /*[B][N][13]*/, double *dl_dbox /*[B][N][4]*/, int on_device, void *stream);
+int cfnmpc_get_adjoint_cost(cfnmpc_solver *s, double *dl_dW /*[B][17]*/, double *dl_dWN /*[B][13]*/,
+                            double *dl_dyref /*[B][N][17]*/, double *dl_dyref_e /*[B][13]*/, int on_device, void *stream);
+
 /* Uncertainty propagation and robust input-bound tightening (zero-order robust optimisation, acados' zoRO custom update;
  * DESIGN.md section 5.21).  A state covariance is carried along the horizon through the closed-loop linearisation of the LAST QP
  * (the "last QP" rule of cfnmpc_eval_sens_x0: its stored blocks A_k, B_k), and every input bound is backed off by a multiple of
@@ -725,6 +750,13 @@ int cfnmpc_fleet_get_sqp_ls_stats(cfnmpc_fleet *f, double *alpha, double *mu, in
 int cfnmpc_fleet_eval_sens_x0(cfnmpc_fleet *f, double act_tol, void *stream);
 int cfnmpc_fleet_get_sens_x0(cfnmpc_fleet *f, int stage, int n_stages, double *du /*[B][n_stages][4][13] or NULL*/,
                              double *dx /*[B][n_stages][13][13] or NULL*/, int on_device, void *stream);
+/* Adjoint sensitivities of every bucket's last QP (cfnmpc_eval_adjoint), rows in the fleet's vehicle order: gx [B][n_g][13] and
+ * gu [B][n_g][4] (either may be NULL, not both) for the stages [0, n_g), n_g <= the shortest horizon -- no terminal-stage
+ * gradient, which would sit at another stage in every bucket.  The getter returns the per-vehicle outputs dl_dx0 [B][13],
+ * dl_dW [B][17], dl_dWN [B][13] (any may be NULL, not all); the per-stage outputs are read from the bucket solvers
+ * (cfnmpc_fleet_bucket).  A fleet's rows equal its bucket solvers' bit for bit. */
+int cfnmpc_fleet_eval_adjoint(cfnmpc_fleet *f, const double *gx, const double *gu, int n_g, int on_device, void *stream);
+int cfnmpc_fleet_get_adjoint(cfnmpc_fleet *f, double *dl_dx0, double *dl_dW, double *dl_dWN, int on_device, void *stream);
 /* Uncertainty propagation and bound tightening on every bucket (cfnmpc_set_uncertainty ...), rows in the fleet's vehicle order.
  * Host arrays are validated as a whole first.  beta has [B][Nmax][4] with NaN behind a vehicle's own horizon;
  * cfnmpc_fleet_get_uncertainty's range is limited by the shortest horizon (stage + n_stages <= Nmin + 1). */
@@ -806,6 +838,10 @@ int cfnmpc_multi_set_weights_batch(cfnmpc_multi *m, const double *W, const doubl
  * synchronous; for cfnmpc_multi_create_horizons the range is limited by the shortest horizon, as for a fleet. */
 int cfnmpc_multi_eval_sens_x0(cfnmpc_multi *m, double act_tol);
 int cfnmpc_multi_get_sens_x0(cfnmpc_multi *m, int stage, int n_stages, double *du /*host or NULL*/, double *dx /*host or NULL*/);
+/* Adjoint sensitivities over the whole fleet (cfnmpc_eval_adjoint per shard; cfnmpc_fleet_eval_adjoint's arguments): host arrays
+ * in the caller's order, synchronous; n_g <= the (shortest) horizon. */
+int cfnmpc_multi_eval_adjoint(cfnmpc_multi *m, const double *gx, const double *gu, int n_g);
+int cfnmpc_multi_get_adjoint(cfnmpc_multi *m, double *dl_dx0, double *dl_dW, double *dl_dWN);
 /* Uncertainty propagation and bound tightening per shard (both create variants): host arrays of the whole fleet in the caller's
  * order, synchronous, validated as a whole first; beta [B][N][4] (N: the longest horizon; NaN behind a vehicle's own).  The full
  * covariance is read through the shards' solvers (cfnmpc_multi_shard / cfnmpc_multi_shard_fleet). */
