@@ -16,6 +16,7 @@
 #include "../../include/cfnmpc.h"
 #include "cfnmpc_host.hpp"
 #include "cfnmpc_model.hpp"
+#include "cfnmpc_plan.hpp"
 #include "cfnmpc_ws.hpp"
 #include "cfnmpc_sqp.h"
 #ifdef CFN_DEV
@@ -23,85 +24,85 @@
 #endif
 
 struct cfnmpc_solver {
-    cfn::Params P;
-    int device;
+    cfn::Params P{};
+    int device = 0;
     std::vector<void*> allocs;
-    double* stage_buf;  // device staging buffer for AoS transfers (largest AoS array)
-    size_t stage_doubles;
+    double* stage_buf = nullptr;  // device staging buffer for AoS transfers (largest AoS array)
+    size_t stage_doubles = 0;
     // cfnmpc_step_host: pinned host mirror + device buffers of one step's inputs / outputs (lazy)
-    double *h_io, *d_io;
-    size_t io_doubles;
-    unsigned long long bytes;
+    double *h_io = nullptr, *d_io = nullptr;
+    size_t io_doubles = 0;
+    unsigned long long bytes = 0;
     // optional per-kernel timing with HIP events on the launch stream (cfnmpc_set_profiling)
-    int profiling;
+    int profiling = 0;
     std::vector<hipEvent_t> ev;  // EV_PER_STEP events per timed RTI step: start | linearise | factor | forward | compaction | active set | end
-    size_t ev_used;
+    size_t ev_used = 0;
     // preparation-phase overlap (development builds, CFNMPC_OVERLAP=1; always 0 in the product): the linearisation for the NEXT
     // step is written to the alternate (AR, BR, b) set while the interior-point kernel still
     // reads the current one
-    int overlap;
-    double *AR2, *BR2, *b2;
-    hipStream_t aux;             // low-priority stream of the early linearisation pass
-    hipEvent_t ev_start, ev_aux; // start solve done (on the caller's stream) / early pass done (on aux)
-    bool lin_valid;              // (P.AR, P.BR, P.b) hold the linearisation of the current iterate
-    int chunks_all, chunks_list; // workgroups per 64-instance group in the two linearisation passes
+    int overlap = 0;
+    double *AR2 = nullptr, *BR2 = nullptr, *b2 = nullptr;
+    hipStream_t aux = nullptr;   // low-priority stream of the early linearisation pass
+    hipEvent_t ev_start = nullptr, ev_aux = nullptr; // start solve done (on the caller's stream) / early pass done (on aux)
+    bool lin_valid = false;   // (P.AR, P.BR, P.b) hold the linearisation of the current iterate
+    int chunks_all = 1, chunks_list = 10; // workgroups per 64-instance group in the two linearisation passes
     // captured step (cfnmpc_opts.step_graph): the launches of one RTI step as a hipGraph, one per parity of
     // the iterate buffers (kernel arguments are by value and the host swaps xit / xitn after every step)
-    int use_graph;
-    hipStream_t cap;             // capture stream
-    hipGraphExec_t gexec[2];
-    hipEvent_t glaunched[2];     // recorded behind the last launch of gexec[p]: waited for before that exec is destroyed
-    bool gvalid[2];
-    int parity;                  // which of the two argument sets the NEXT step uses
-    int reinit_failed;           // cfnmpc_opts.reinit_failed
-    double *lbs_keep, *ubs_keep; // per-stage boxes (cfnmpc_set_box_stages), allocated at the first call
-    double* box_blk[4];          // ... the four blocks behind them (home lb / ub, compact lb / ub); a failed attempt keeps what it got
+    int use_graph = 0;
+    hipStream_t cap = nullptr;   // capture stream
+    hipGraphExec_t gexec[2] = {nullptr, nullptr};
+    hipEvent_t glaunched[2] = {nullptr, nullptr};   // recorded behind the last launch of gexec[p]: waited for before that exec is destroyed
+    bool gvalid[2] = {false, false};
+    int parity = 0;   // which of the two argument sets the NEXT step uses
+    int reinit_failed = 0;   // cfnmpc_opts.reinit_failed
+    double *lbs_keep = nullptr, *ubs_keep = nullptr; // per-stage boxes (cfnmpc_set_box_stages), allocated at the first call
+    double* box_blk[4] = {nullptr, nullptr, nullptr, nullptr};   // ... the four blocks behind them (home lb / ub, compact lb / ub); a failed attempt keeps what it got
     // full SQP solve (cfnmpc_solve_sqp): per-instance results and counters of k_sqp_check (sqp.j / max_iter / tolerances of the
     // running solve), the pinned word the host reads the count of open rows through, and the event it waits for
-    cfn::SqpArgs sqp;
-    unsigned* h_sqp_cnt;
-    hipEvent_t sqp_ev;
+    cfn::SqpArgs sqp{};
+    unsigned* h_sqp_cnt = nullptr;
+    hipEvent_t sqp_ev = nullptr;
     // globalisation of the SQP solve (cfnmpc_set_sqp_globalization): the setting (mode, alpha_min; eta / reduction / T in ls),
     // k_sqp_ls's per-instance state (allocated at the first globalised solve), whether the RUNNING solve is globalised, and
     // what the last solve was (-1: none yet, else its mode) for cfnmpc_get_sqp_ls_stats
-    int glob_mode;
-    double glob_alpha_min;
-    cfn::LsArgs ls;
-    bool ls_active;
-    int ls_last;
+    int glob_mode = CFNMPC_SQP_FULL_STEP;
+    double glob_alpha_min = 1.0 / 1024.0;
+    cfn::LsArgs ls = {nullptr, nullptr, nullptr, nullptr, /* eta */ 1e-4, /* reduction */ 0.5, /* T */ 10};
+    bool ls_active = false;
+    int ls_last = -1;
     // stage-cost scaling (cfnmpc_set_cost_scaling): the weights as the caller set them; P.W = stage_scale * W_set,
     // P.WN = terminal_scale * WN_set
-    double W_set[17], WN_set[13];
-    double stage_scale, terminal_scale;
+    double W_set[17] = {}, WN_set[13] = {};
+    double stage_scale = 1.0, terminal_scale = 1.0;
     // per-instance model parameters (cfnmpc_set_model_params): the caller's rows [B][NPAR] while set (empty: nominal) and the
     // device block of derived constants P.mpar points to while set (allocated at the first call, kept for later ones)
     std::vector<double> mp_rows;
-    double* mpar_buf;
+    double* mpar_buf = nullptr;
     // per-instance disturbance rows (cfnmpc_set_disturbance): the device table P.dist points to while set (allocated at the first
     // call, kept for later ones).  While set, P.mpar is set too: the caller's rows, or the nominal ones if there are none
-    double* dist_buf;
+    double* dist_buf = nullptr;
     // per-instance cost weights (cfnmpc_set_weights_batch): the caller's unscaled rows [B][17] / [B][13] while set (empty: the
     // uniform W_set / WN_set) and the device table P.wtab points to while set (allocated at the first call, kept for later ones)
     std::vector<double> w_rows, wn_rows;
-    double* wtab_buf;
+    double* wtab_buf = nullptr;
     // solution sensitivities (cfnmpc_eval_sens_x0): what the last QP was (0: none, or its data changed since; 1: an RTI step;
     // 2: an SQP iteration, whose status is sqp.status), whether an evaluation belongs to it, the buffers (allocated at the
     // first evaluation) and the staging buffer of host reads
-    int sens_src;
-    bool sens_valid;
-    cfn::SensArgs sens;
-    double* sens_stage;
-    size_t sens_stage_doubles;
+    int sens_src = 0;
+    bool sens_valid = false;
+    cfn::SensArgs sens{};
+    double* sens_stage = nullptr;
+    size_t sens_stage_doubles = 0;
     // adjoint sensitivities (cfnmpc_eval_adjoint): the buffers (allocated at the first evaluation; adj_gx / adj_gu hold the
     // gradients a caller hands over as host arrays) and whether an evaluation belongs to the sensitivity evaluation in force
-    cfn::AdjArgs adj;
-    double *adj_gx, *adj_gu;
-    bool adj_valid;
+    cfn::AdjArgs adj{};
+    double *adj_gx = nullptr, *adj_gu = nullptr;
+    bool adj_valid = false;
     // NLP evaluation (cfnmpc_eval_nlp): cost [B] and residuals [B][3] (allocated with the solver), costates and reduced gradient
     // (allocated at the first evaluation that keeps them), and what the last evaluation left (0: none yet, 1: cost and residuals,
     // 2: the multipliers too)
-    cfn::NlpArgs nlp;
-    int nlp_state;
+    cfn::NlpArgs nlp{};
+    int nlp_state = 0;
     // uncertainty propagation and robust input-bound tightening (cfnmpc_eval_uncertainty / cfnmpc_tighten_box; DESIGN.md
     // section 5.21); every buffer is allocated at the first call that needs it
     struct Unc {
@@ -137,35 +138,6 @@ using cfn::is_host;
 
 constexpr size_t MAX_PROFILED_STEPS = 4096;   // cfnmpc_get_profile resets the count
 constexpr size_t EV_PER_STEP = 7;
-// Kernel choices that depend on how the fleet fills the device, in units of its SIMDs (S = 4 x compute units = wave slots at
-// one wave per SIMD; MI355X: 1024) -- measured per horizon, profiles/r04_thresholds.md (tools/threshold_sweep.py):
-//   * forward sweep on the stored blocks (row groups, B / 4 waves) instead of the matrix-free one (B / 64 waves of N
-//     sequential stages): while B / 4 waves fit about twice on the SIMDs; the row-group sweep streams 240 N doubles per
-//     instance, so long horizons leave it earlier (cross-over 7000 instances at N = 30 and 50, 5500 at N = 100);
-//   * active-set solves + commit kernel instead of the monolithic kernel: while the ~8 % constrained rows make fewer
-//     waves than there are SIMDs by a margin (roll-out = latency chain); re-measured after the 4-vector layout change:
-//     N = 50: -3.5 % at 24 S, -0.5 % at 32 S, equal at 48 S; N = 100: -3.6 % up to 32 S, equal at 48 S; N = 30: +4.7 % from 24 S on;
-//   * fall-back rows compacted before the interior point: from 16 S instances;
-//   * head-condensed dense active-set solves (k_as_dense) for the rows with heads of at most 16 stages: below 18 S instances
-//     (round 5, one box, A/B per size: 2 S +20.6 %, 4 S +8.5 %, 8 S +9.6 %, 12 S +1.8 %, 16 S +1.1 %, 20 S -1.8 %, 24 S -1.4 %,
-//     28 S -0.5 %, 32 S -5 %: one row per wavefront and SIMD -- while the ~8 % constrained rows fit the SIMDs once the kernel lasts
-//     as long as its hardest row, 50 - 90 us instead of 220; beyond that its ~47 us per row are rounds of waves and the four
-//     rows per wavefront of k_as_solves / k_as win on throughput), profiles/r05_as_dense.md;
-//   * split forward sweep (k_forward_p1 | k_forward_p2 beside the constrained rows' kernels): wherever that structure runs with the
-//     matrix-free sweep (one box: 6144 instances +3.5 % against the unsplit matrix-free sweep and +2 % against the row-group one,
-//     8192: +7.2 %, 12 288: +1.2 %, 16 384: +0.7 %; at 4096 the row-group sweep stays ahead, 7.33 against 6.75 M).
-struct Choice { bool forward_rg, as_commit, ipm_listed, as_dense, forward_split; };
-inline Choice choose_kernels(int batch, int N, int simds) {
-    const long S = simds > 0 ? simds : 1024;
-    Choice c;
-    c.forward_rg = (long)batch < 6 * S;   // (round 5: 8 S -> 6 S for N <= 64 too -- the split matrix-free sweep beats the row-group one from 6 S on: 9.37 against 9.18 M at 6144 instances)
-    c.as_commit = (long)batch < (N <= 40 ? 20 : 36) * S;
-    c.ipm_listed = (long)batch >= 16 * S;
-    c.as_dense = (long)batch < 18 * S;
-    c.forward_split = true;
-    return c;
-}
-
 template <typename T>
 int dev_alloc(cfnmpc_solver* s, T** p, size_t count) {
     void* q = nullptr;
@@ -257,16 +229,41 @@ int host_row_chunks(cfnmpc_solver* s, size_t per, F chunk) {
     return CFNMPC_OK;
 }
 
-// Q may be positive SEMI-definite (the reference's dynamic_reconfigure ranges start at 0.0,
-// config/crazyflie_params.cfg:19-35): state weights >= 0, input weights > 0 (R must be definite:
-// S = R + B'PB is what the Riccati recursion inverts); no NaN.
-bool weights_ok(const double* W, const double* WN) {
-    if (W) {
-        for (int i = 0; i < 13; i++) if (!(W[i] >= 0.0)) return false;
-        for (int i = 13; i < 17; i++) if (!(W[i] > 0.0)) return false;
+using cfn::weights_ok;
+static_assert(cfn::PLAN_COND_MMAX == cfn::COND_MMAX, "cfnmpc_plan.hpp states the longest condensed block of cfnmpc_ws.hpp");
+
+// The environment of the development build (make DEV=1; the shipped library reads no environment variable).  Before the options
+// are resolved (plan == nullptr): CFNMPC_OVERLAP, the overlapped preparation -- the next step's linearisation beside the
+// constrained rows' kernels, double-buffered A / B / b; measured slower at every fleet size, since round 6
+// an experiment and not an option of the product.  Behind it: CFNMPC_LIN_CHUNKS=a,b, CFNMPC_AS_PASSES (internal encoding) and
+// CFNMPC_AS_GRID replace what the plan chose.  A forced scheduling drops the dense structure, which lives in the solves + commit
+// one only, and is refused beside the fused start solve, which lives in the monolithic one.
+int dev_env(cfn::Plan* plan) {
+#ifdef CFN_DEV
+    if (!plan) {
+        const char* e = std::getenv("CFNMPC_OVERLAP");
+        return e && std::atoi(e) ? 1 : 0;
     }
-    if (WN) for (int i = 0; i < 13; i++) if (!(WN[i] >= 0.0)) return false;
-    return true;
+    if (const char* e = std::getenv("CFNMPC_LIN_CHUNKS")) {
+        int a = 0, b = 0;
+        if (std::sscanf(e, "%d,%d", &a, &b) == 2 && a > 0 && b > 0) { plan->chunks_all = a; plan->chunks_list = b; }
+    }
+    if (const char* e = std::getenv("CFNMPC_AS_PASSES")) {
+        const int v = std::atoi(e);
+        if (v >= -2 && v <= 12 && v != plan->as_passes) {
+            if (plan->fused == 1) return CFNMPC_EINVAL;
+            plan->as_passes = v;
+            plan->as_dense = plan->wants_side_streams = plan->fwd_split = 0;
+        }
+    }
+    if (const char* e = std::getenv("CFNMPC_AS_GRID")) {
+        const int v = std::atoi(e);
+        if (v > 0) { plan->as_grid = v; plan->as_sparse_max = v / 2; }
+    }
+#else
+    (void)plan;
+#endif
+    return 0;
 }
 
 }  // namespace
@@ -320,166 +317,62 @@ int cfnmpc_abi_version(void) { return CFNMPC_ABI_VERSION; }
 
 int cfnmpc_create(cfnmpc_solver** out, int batch, const cfnmpc_opts* opts) {
     if (!out || batch <= 0) return CFNMPC_EINVAL;
+    // 1. the options -> the plan (cfnmpc_plan.hpp): every refusal happens here, before anything is owned
     cfnmpc_opts o;
     RC_TRY(cfn::take_opts(opts, &o));
-    // Overlapped preparation (the next step's linearisation beside the constrained rows' kernels, double-buffered A / B / b):
-    // measured slower at every fleet size -- since round 6 an experiment of the development build
-    // (make DEV=1; CFNMPC_OVERLAP=1 in the environment), not an option of the product.
-    int overlap_linearise = 0;
-#ifdef CFN_DEV
-    if (const char* e = std::getenv("CFNMPC_OVERLAP")) overlap_linearise = std::atoi(e) ? 1 : 0;
-#endif
-    if (o.N < 5 || o.N > 4096 || !(o.dt > 0) || !(o.u_max > o.u_min) || o.max_iter < 0 ||
-        !(o.ah_margin >= 0.0 && o.ah_margin < 0.5) || o.ah_extra < 0) return CFNMPC_EINVAL;
-    // QP parameters that would otherwise only show up as NaN / status 4 at run time
-    if (!(o.tol > 0.0) || !(o.tau > 0.0 && o.tau < 1.0) || !(o.thr0 > 0.0) || !(o.lam0_min > 0.0) ||
-        !(o.mu0_scale >= 0.0) || !(o.ipm_clip_viol >= 0.0) || !(o.ipm_clip_margin > 0.0 && o.ipm_clip_margin < 0.5) ||
-        !(o.as_skip_viol >= 0.0)) return CFNMPC_EINVAL;
-    if (!weights_ok(o.W, o.WN)) return CFNMPC_EINVAL;
-    // partial condensing: cond_N2 blocks of at most COND_MMAX stages; not combined with the overlapped preparation
-    if (o.cond_N2 < 0 || o.cond_N2 > o.N) return CFNMPC_EINVAL;
-    const int cond_N2 = (o.cond_N2 == 0 || o.cond_N2 == o.N) ? 0 : o.cond_N2;
-    if (cond_N2 && ((o.N + cond_N2 - 1) / cond_N2 > cfn::COND_MMAX || overlap_linearise)) return CFNMPC_EINVAL;
+    int device = 0, simds = 1024;   // SIMDs of the device the solver is created on
+    hipDeviceProp_t prop;
+    const bool have_device = hipGetDevice(&device) == hipSuccess;
+    if (have_device && hipGetDeviceProperties(&prop, device) == hipSuccess) simds = 4 * prop.multiProcessorCount;
+    cfn::Plan plan;
+    RC_TRY(cfn::resolve_plan(o, batch, simds, dev_env(nullptr), &plan));
+    RC_TRY(dev_env(&plan));
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         std::fprintf(stderr, "cfnmpc: no HIP device available (this library has no CPU path)\n");
         return CFNMPC_EHIP;
     }
+    if (!have_device) return CFNMPC_EHIP;
+    // 2. the solver, with the plan copied into it and into the kernels' parameters
     cfnmpc_solver* s = new (std::nothrow) cfnmpc_solver();
     if (!s) return CFNMPC_ENOMEM;
-    s->bytes = 0;
-    s->h_io = s->d_io = nullptr;
-    s->io_doubles = 0;
-    s->profiling = 0;
-    s->ev_used = 0;
-    s->overlap = overlap_linearise ? 1 : 0;
-    s->AR2 = s->BR2 = s->b2 = nullptr;
-    s->aux = nullptr;
-    s->ev_start = s->ev_aux = nullptr;
-    s->lin_valid = false;
-    s->use_graph = o.step_graph ? 1 : 0;
-    s->cap = nullptr;
-    s->gexec[0] = s->gexec[1] = nullptr;
-    s->glaunched[0] = s->glaunched[1] = nullptr;
-    s->gvalid[0] = s->gvalid[1] = false;
-    s->parity = 0;
-    s->lbs_keep = s->ubs_keep = nullptr;
-    for (double*& q : s->box_blk) q = nullptr;
-    s->reinit_failed = o.reinit_failed ? 1 : 0;
-    std::memset(&s->sqp, 0, sizeof s->sqp);
-    s->h_sqp_cnt = nullptr;
-    s->sqp_ev = nullptr;
-    s->glob_mode = CFNMPC_SQP_FULL_STEP;
-    s->glob_alpha_min = 1.0 / 1024.0;
-    std::memset(&s->ls, 0, sizeof s->ls);
-    s->ls.eta = 1e-4; s->ls.reduction = 0.5; s->ls.T = 10;
-    s->ls_active = false;
-    s->ls_last = -1;
-    std::memset(&s->nlp, 0, sizeof s->nlp);
-    s->nlp_state = 0;
-    int simds = 1024;   // SIMDs of the device the solver is created on
-    {
-        hipDeviceProp_t prop;
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) simds = 4 * prop.multiProcessorCount;
-    }
-    const Choice pick = choose_kernels(batch, o.N, simds);
-    // the shooting intervals of a 64-instance group are independent: spread them over enough
-    // workgroups to fill the 1024 SIMDs when the batch alone does not (a single instance then
-    // linearises its 50 intervals in parallel instead of one after the other)
-    {
-        // k_linearise runs one wavefront per SIMD: a launch of groups x c workgroups takes ceil(groups c / SIMDs) rounds of
-        // ceil(N / c) stages each (+ a prologue per workgroup) -- take the c that minimises it (rounding groups c UP past the
-        // number of SIMDs would cost a whole second round: 255 groups x 5 chunks = 1275 workgroups ran 35 % slower than x 4)
-        const int groups = (batch + 63) / 64;
-        int c = 1;
-        if (s->overlap) {
-            c = 5;
-            if (groups * c < simds) c = (simds + groups - 1) / groups;
-        } else {
-            double best = 1e300;
-            for (int cc = 1; cc <= o.N; cc++) {
-                const long rounds = ((long)groups * cc + simds - 1) / simds;
-                const double cost = (double)rounds * ((o.N + cc - 1) / cc + 0.35);   // 0.35 stage-equivalents of prologue per workgroup
-                if (cost < best - 1e-9) { best = cost; c = cc; }
-            }
-        }
-        s->chunks_all = c < 1 ? 1 : (c > o.N ? o.N : c);
-    }
-    s->chunks_list = 10;
-#ifdef CFN_DEV   // development builds only (make DEV=1): the shipped library reads no environment variables
-    if (const char* e = std::getenv("CFNMPC_LIN_CHUNKS")) {
-        int a = 0, b = 0;
-        if (std::sscanf(e, "%d,%d", &a, &b) == 2 && a > 0 && b > 0) { s->chunks_all = a; s->chunks_list = b; }
-    }
-#endif
-    if (hipGetDevice(&s->device) != hipSuccess) { delete s; return CFNMPC_EHIP; }
+    s->device = device;
+    s->overlap = plan.overlap;
+    s->use_graph = plan.use_graph;
+    s->reinit_failed = plan.reinit_failed;
+    s->chunks_all = plan.chunks_all;
+    s->chunks_list = plan.chunks_list;
     cfn::Params& P = s->P;
-    std::memset(&P, 0, sizeof P);
     P.B = batch;
     P.NW = (batch + 3) / 4;
     P.N = o.N;
     P.dt = o.dt;
     for (int i = 0; i < 17; i++) P.W[i] = s->W_set[i] = o.W[i];
     for (int i = 0; i < 13; i++) P.WN[i] = s->WN_set[i] = o.WN[i];
-    s->stage_scale = s->terminal_scale = 1.0;
     P.erk_steps = 1;
     P.u_min = o.u_min; P.u_max = o.u_max; P.tol = o.tol; P.tau = o.tau; P.thr0 = o.thr0;
     P.lam0_min = o.lam0_min; P.mu0_scale = o.mu0_scale; P.max_iter = o.max_iter;
     P.clip_viol = o.ipm_clip_viol; P.clip_margin = o.ipm_clip_margin; P.as_skip_viol = o.as_skip_viol;
-    P.active_horizon = o.active_horizon ? 1 : 0;
+    P.active_horizon = plan.active_horizon;
     P.ah_margin = o.ah_margin;
     P.ah_extra = o.ah_extra;
-    P.active_set = o.active_set ? 1 : 0;
-    P.as_warm = (o.as_warm && o.active_set) ? 1 : 0;
-    if (o.forward_sweep < 0 || o.forward_sweep > 2 || (o.step_graph && overlap_linearise) ||
-        (o.reinit_failed && overlap_linearise)) { delete s; return CFNMPC_EINVAL; }
-#ifdef CFN_DEV   // (development builds: also -2 and 1..12, the instance-contiguous store / level-synchronous passes of round 3)
-    if (o.as_passes < -3 || o.as_passes > 12) { delete s; return CFNMPC_EINVAL; }
-#else
-    if (o.as_passes != 0 && o.as_passes != -1 && o.as_passes != -3) { delete s; return CFNMPC_EINVAL; }
-#endif
-    // internal: 0 = monolithic k_as, -1 = every solve in one launch on the compact z store + commit, -2 = the monolithic
-    // kernel's solves + commit, p > 0 = p single-solve passes
-    P.as_passes = o.as_passes > 0 ? o.as_passes : (o.as_passes == -2 ? -1 : (o.as_passes == -3 ? -2 : 0));
-    if (o.as_passes == 0 && pick.as_commit && o.start_solve != 2) P.as_passes = -2;   // small fleets: solves + commit kernel (measured); the commit kernel reads stored blocks
-#ifdef CFN_DEV
-    if (const char* e = std::getenv("CFNMPC_AS_PASSES")) {   // (internal encoding)
-        const int v = std::atoi(e);
-        if (v >= -2 && v <= 12) P.as_passes = v;
-    }
-#endif
-    {   // pass launches: two wavefronts per SIMD of this device
-        P.as_grid = 2 * simds;
-#ifdef CFN_DEV
-        if (const char* e = std::getenv("CFNMPC_AS_GRID")) { const int v = std::atoi(e); if (v > 0) P.as_grid = v; }
-#endif
-    }
-    // one fall-back row per wave is as fast as four while those waves fit one per SIMD (1024 rows: 1.6 % of 65 536 instances,
-    // 2.5 % fall back at three times the bench's disturbances): only large fleets pay the compaction's extra launch
-    P.as_sparse_max = P.as_grid / 2;   // = the SIMDs of the device: one constrained row per wave while they all fit at once
-    P.ipm_listed = pick.ipm_listed ? 1 : 0;
-    // head-condensed dense active-set solves (cfnmpc_asdense.hip) beside the solves + commit structure; scalar box, stored blocks
-    // (every option is validated BEFORE the side streams below are created: the refusals here own nothing but `s`)
-    if (o.as_dense < -1 || o.as_dense > 1 || o.start_solve < 0 || o.start_solve > 3 || o.forward_split < -1 || o.forward_split > 1) { delete s; return CFNMPC_EINVAL; }
-    if (o.as_dense == 1 && (P.as_passes != -2 && o.as_passes != 0)) { delete s; return CFNMPC_EINVAL; }
-    if (o.as_dense == 1 && o.as_passes == 0 && o.start_solve != 2 && !cond_N2) P.as_passes = -2;   // asked for: the structure it lives in
-    P.as_dense = (P.as_passes == -2 && P.active_set && !P.as_warm && o.as_dense != -1 && (o.as_dense == 1 || pick.as_dense)) ? 1 : 0;
-    // an EXPLICIT request that cannot be honoured is refused, not dropped (as_dense = 1 beside start_solve = 2, cond_N2, as_warm or
-    // active_set = 0; forward_split = 1 outside the dense structure, with the row-group sweep, short horizons or the overlapped
-    // preparation -- whose early pass would read the iterate while part two of the sweep is still writing it)
-    if (o.as_dense == 1 && !P.as_dense) { delete s; return CFNMPC_EINVAL; }
-    const bool split_ok = P.as_dense && !cond_N2 && o.start_solve != 2 && o.start_solve != 3 && o.N >= 40 && !overlap_linearise &&
-                          o.forward_sweep != 2 && o.forward_split != -1;
-    if (o.forward_split == 1 && !split_ok) { delete s; return CFNMPC_EINVAL; }
-    // forward sweep on the stored blocks (row groups) below 6 S instances where the split matrix-free sweep takes over from there;
-    // where it cannot run (short horizons, no dense structure, ...) the unsplit matrix-free sweep wins from 8 S on only
-    // (an explicitly fused start solve stores no stage blocks: the automatic choice then stays with the matrix-free sweep)
-    {
-        const bool auto_rg = split_ok ? pick.forward_rg : (long)batch < 8L * simds;
-        P.forward_rg = o.forward_sweep == 2 || (o.forward_sweep == 0 && auto_rg && o.start_solve != 2 && !(o.forward_split == 1)) ? 1 : 0;
-    }
-    if (P.as_dense) {   // side stream of the rows with long heads (launch_qp_ipm); without it the two kernels simply run one after the other
+    P.active_set = plan.active_set;
+    P.as_warm = plan.as_warm;
+    P.as_passes = plan.as_passes;
+    P.as_grid = plan.as_grid;
+    P.as_sparse_max = plan.as_sparse_max;
+    P.ipm_listed = plan.ipm_listed;
+    P.as_dense = plan.as_dense;
+    P.forward_rg = plan.forward_rg;
+    P.fused = plan.fused;
+    P.clist_chunks = plan.clist_chunks;
+    P.cond_N2 = plan.cond_N2;
+    P.cond_M = plan.cond_M;
+    P.cond_rem = plan.cond_rem;
+    P.ab16 = plan.ab16;
+    P.v4b = plan.v4b;
+    // 3. side streams, workspace, iterate: from here on every failure is cfnmpc_free(s)
+    if (plan.wants_side_streams) {   // without them the kernels simply run one after the other
         hipStream_t side = nullptr;
         hipEvent_t ef = nullptr, ej = nullptr;
         if (hipStreamCreateWithFlags(&side, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&ef, hipEventDisableTiming) == hipSuccess &&
@@ -499,24 +392,8 @@ int cfnmpc_create(cfnmpc_solver** out, int batch, const cfnmpc_opts* opts) {
             (void)hipGetLastError();
         }
     }
-    // start solve: the fused kernel replaces k_linearise + k_factor where nothing but the constrained instances' QP kernels
-    // reads the stage blocks afterwards (matrix-free forward sweep, monolithic active-set kernel, no partial condensing,
-    // no overlapped preparation); per-stage boxes (cfnmpc_set_box_stages) switch a solver back at launch time
-    {
-        const bool can_fuse = !cond_N2 && !overlap_linearise && !P.forward_rg && P.as_passes == 0;
-        if (o.start_solve == 2 && !can_fuse) { cfnmpc_free(s); return CFNMPC_EINVAL; }
-        if (o.start_solve == 3 && (cond_N2 || overlap_linearise)) { cfnmpc_free(s); return CFNMPC_EINVAL; }
-        P.fused = o.start_solve == 2 ? 1 : (o.start_solve == 3 ? 2 : 0);
-        P.clist_chunks = o.N >= 10 ? 10 : o.N;
-    }
-    // split forward sweep: lives in the dense structure (two side streams), matrix-free sweep, horizons that reach well behind H
     // (without the second side stream -- its creation failed -- the sweep stays in one launch)
-    P.fwd_split = (split_ok && P.as_side2 && !P.forward_rg && P.fused == 0 && (o.forward_split == 1 || pick.forward_split)) ? 24 : 0;
-    P.cond_N2 = cond_N2;
-    P.ab16 = 1;                // home A, B, b grouped by 16 blocks (cfnmpc_rg.hpp: abidx)
-    P.v4b = cond_N2 ? 0 : 1;   // home 4-vectors wave-blocked (the condensed kernels index theirs instance-major)
-    P.cond_M = cond_N2 ? o.N / cond_N2 : 0;
-    P.cond_rem = cond_N2 ? o.N % cond_N2 : 0;
+    P.fwd_split = P.as_side2 ? plan.fwd_split : 0;
     // one spare workspace block (index P.NW) parks the idle rows of compacted interior-point waves
     const size_t NW = P.NW + 1, N = P.N;
     int rc = CFNMPC_OK;
@@ -546,7 +423,7 @@ int cfnmpc_create(cfnmpc_solver** out, int batch, const cfnmpc_opts* opts) {
     if (P.as_warm) { ALLOC(wcls, NW * 4 * N * 4); ALLOC(wvalid, NW * 4); }
     if (P.fwd_split) { ALLOC(fs_dx, ((size_t)(batch + 63) / 64) * 13 * 64); ALLOC(fs_st, ((size_t)(batch + 63) / 64) * 4 * 64); }
     if (P.as_passes != 0) ALLOC(aslist, (size_t)3 * 7 * NW * 4);
-    if (cond_N2) ALLOC(cb, NW * 4 * (size_t)cond_N2 * cfn::cb_size(cfn::cond_mmax(P)));
+    if (P.cond_N2) ALLOC(cb, NW * 4 * (size_t)P.cond_N2 * cfn::cb_size(cfn::cond_mmax(P)));
     // full SQP solve (cfnmpc_solve_sqp): residuals, status, sqp_iter, done flags, the two counters of open rows
     if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->sqp.res, (size_t)batch * 3);
     if (rc == CFNMPC_OK) rc = dev_alloc(s, &s->sqp.status, (size_t)batch);
