@@ -15,7 +15,7 @@ SYMBOLS = [
     "cfnmpc_workspace_bytes", "cfnmpc_set_x0", "cfnmpc_set_yref", "cfnmpc_set_weights", "cfnmpc_set_box", "cfnmpc_get_cmd", "cfnmpc_set_yref_windows", "cfnmpc_init_iterate",
     "cfnmpc_set_iterate", "cfnmpc_get_iterate", "cfnmpc_solve", "cfnmpc_solve_sqp", "cfnmpc_get_sqp_stats", "cfnmpc_set_sqp_globalization", "cfnmpc_get_sqp_globalization", "cfnmpc_get_sqp_ls_stats", "cfnmpc_step_host", "cfnmpc_get_u", "cfnmpc_get_x",
     "cfnmpc_get_stats", "cfnmpc_sim", "cfnmpc_estimate", "cfnmpc_debug_get_linearisation", "cfnmpc_debug_linearise", "cfnmpc_debug_start_factor", "cfnmpc_debug_get_factor",
-    "cfnmpc_debug_get_head", "cfnmpc_debug_get_viol", "cfnmpc_debug_get_list_counts", "cfnmpc_debug_get_condensed", "cfnmpc_set_box_stages", "cfnmpc_set_profiling", "cfnmpc_get_profile", "cfnmpc_get_profile_kernels", "cfnmpc_get_profile_steps", "cfnmpc_version",
+    "cfnmpc_debug_get_head", "cfnmpc_debug_get_viol", "cfnmpc_debug_get_list_counts", "cfnmpc_debug_get_yref_uniform", "cfnmpc_debug_get_condensed", "cfnmpc_set_box_stages", "cfnmpc_set_profiling", "cfnmpc_get_profile", "cfnmpc_get_profile_kernels", "cfnmpc_get_profile_steps", "cfnmpc_version",
     "cfnmpc_fleet_create", "cfnmpc_fleet_free", "cfnmpc_fleet_batch", "cfnmpc_fleet_min_horizon", "cfnmpc_fleet_max_horizon",
     "cfnmpc_fleet_num_buckets", "cfnmpc_fleet_bucket", "cfnmpc_fleet_workspace_bytes", "cfnmpc_fleet_set_x0",
     "cfnmpc_fleet_set_yref", "cfnmpc_fleet_set_weights", "cfnmpc_fleet_init_iterate", "cfnmpc_fleet_solve",
@@ -162,6 +162,7 @@ def lib():
     L.cfnmpc_debug_get_linearisation.argtypes = [vp, vp, vp, vp]
     L.cfnmpc_debug_get_head.argtypes = [vp, vp]
     L.cfnmpc_debug_get_list_counts.argtypes = [vp, vp]
+    L.cfnmpc_debug_get_yref_uniform.argtypes = [vp, vp]
     L.cfnmpc_debug_get_condensed.argtypes = [vp, i32, vp, vp, vp]
     L.cfnmpc_set_profiling.argtypes = [vp, i32]
     L.cfnmpc_get_profile.argtypes = [vp, vp, vp, vp]

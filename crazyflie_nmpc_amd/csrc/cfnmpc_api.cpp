@@ -54,6 +54,12 @@ struct cfnmpc_solver {
     hipEvent_t glaunched[2] = {nullptr, nullptr};   // recorded behind the last launch of gexec[p]: waited for before that exec is destroyed
     bool gvalid[2] = {false, false};
     int parity = 0;   // which of the two argument sets the NEXT step uses
+    // stage-invariant references (Params.yuni): cfnmpc_set_yref launches k_yref_uniform behind its k_put; the
+    // verdict travels through yvaries (device word -> pinned host word, both allocated with the first call) with yuni_ev behind the
+    // copy, and the first step that follows waits for it once (resolve_yuni).  Every other writer of P.yref clears the flag unasked.
+    int *yvaries = nullptr, *h_yvaries = nullptr;
+    hipEvent_t yuni_ev = nullptr;
+    bool yuni_pending = false;   // a verdict is on its way
     int reinit_failed = 0;   // cfnmpc_opts.reinit_failed
     double *lbs_keep = nullptr, *ubs_keep = nullptr; // per-stage boxes (cfnmpc_set_box_stages), allocated at the first call
     double* box_blk[4] = {nullptr, nullptr, nullptr, nullptr};   // ... the four blocks behind them (home lb / ub, compact lb / ub); a failed attempt keeps what it got
@@ -478,6 +484,8 @@ int cfnmpc_free(cfnmpc_solver* s) {
     if (s->ev_start) (void)hipEventDestroy(s->ev_start);
     if (s->ev_aux) (void)hipEventDestroy(s->ev_aux);
     if (s->sqp_ev) (void)hipEventDestroy(s->sqp_ev);
+    if (s->yuni_ev) { (void)hipEventSynchronize(s->yuni_ev); (void)hipEventDestroy(s->yuni_ev); }
+    if (s->h_yvaries) (void)hipHostFree(s->h_yvaries);
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->h_io) (void)hipHostFree(s->h_io);
     if (s->h_sqp_cnt) (void)hipHostFree(s->h_sqp_cnt);
@@ -497,12 +505,46 @@ int cfnmpc_set_x0(cfnmpc_solver* s, const double* x0, int on_device, void* strea
     return put_field(s, x0, on_device, 1, 13, 1, s->P.x0, (hipStream_t)stream);
 }
 
+// kernel arguments or the choice of a kernel changed (weights, box, Params.yuni): the captured steps hold the old ones
+static void invalidate_graphs(cfnmpc_solver* s) { s->gvalid[0] = s->gvalid[1] = false; }
+
+// ---- stage-invariant references (Params.yuni) ----------------------------------------------------------------------------------
+static void set_yuni(cfnmpc_solver* s, int yuni) {
+    s->yuni_pending = false;
+    if (s->P.yuni != yuni) { s->P.yuni = yuni; invalidate_graphs(s); }
+}
+// a writer of P.yref other than cfnmpc_set_yref (windows, polynomial rows, cfnmpc_step_host): the rows vary, no detection
+static void yref_rows_vary(cfnmpc_solver* s) { set_yuni(s, 0); }
+// behind the k_put of cfnmpc_set_yref on `st`: does any instance's row k >= 1 differ from its row 0?  Nothing waits here.
+static int detect_yuni(cfnmpc_solver* s, hipStream_t st) {
+    if (!s->yvaries) RC_TRY(dev_alloc(s, &s->yvaries, 1));
+    if (!s->h_yvaries) HIP_TRY(hipHostMalloc((void**)&s->h_yvaries, sizeof(int), hipHostMallocDefault));
+    if (!s->yuni_ev) HIP_TRY(hipEventCreateWithFlags(&s->yuni_ev, hipEventDisableTiming));
+    HIP_TRY(hipMemsetAsync(s->yvaries, 0, sizeof(int), st));
+    cfn::launch_yref_uniform(s->P, s->yvaries, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(s->h_yvaries, s->yvaries, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(s->yuni_ev, st));
+    s->yuni_pending = true;
+    return CFNMPC_OK;
+}
+// in front of whatever launches the start solve's factorisation: the one wait for a verdict on its way (none per step)
+static int resolve_yuni(cfnmpc_solver* s) {
+    if (!s->yuni_pending) return CFNMPC_OK;
+    HIP_TRY(hipEventSynchronize(s->yuni_ev));
+    set_yuni(s, *s->h_yvaries ? 0 : 1);
+    return CFNMPC_OK;
+}
+
 int cfnmpc_set_yref(cfnmpc_solver* s, const double* yref, const double* yref_e, int on_device, void* stream) {
     if (!s || !yref || !yref_e) return CFNMPC_EINVAL;
     DeviceGuard dg(s->device);
     s->unc.inputs_moved = true;
     int rc = put_field(s, yref, on_device, s->P.N, 17, 1, s->P.yref, (hipStream_t)stream);
     if (rc != CFNMPC_OK) return rc;
+    // (the flag in force stays until the verdict is read: a caller that sends stage-invariant rows every step keeps its captured graphs)
+    rc = detect_yuni(s, (hipStream_t)stream);
+    if (rc != CFNMPC_OK) { yref_rows_vary(s); return rc; }
     return put_field(s, yref_e, on_device, 1, 13, 1, s->P.yref_e, (hipStream_t)stream);
 }
 
@@ -513,6 +555,7 @@ int cfnmpc_set_yref_windows(cfnmpc_solver* s, const double* traj, int n_rows, in
     if (n_rows > 0 && (!traj || n_rows < s->P.N + 1)) return CFNMPC_EINVAL;
     if (n_rows <= 0 && traj) return CFNMPC_EINVAL;
     s->unc.inputs_moved = true;
+    yref_rows_vary(s);
     cfn::launch_windows(s->P, traj, n_rows > 0 ? n_rows : 0, mode, iter, des_xyz, uss, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return CFNMPC_OK;
@@ -592,6 +635,7 @@ int cfnmpc_set_yref_poly(cfnmpc_solver* s, double t, int flags, void* stream) {
     if (!s || s->poly.n_traj == 0 || !std::isfinite(t) || (flags & ~(CFNMPC_POLY_LOOP | CFNMPC_POLY_KINEMATIC))) return CFNMPC_EINVAL;
     DeviceGuard dg(s->device);
     s->unc.inputs_moved = true;
+    yref_rows_vary(s);
     cfn::launch_poly_rows(s->P, poly_args(s, t, flags), (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return CFNMPC_OK;
@@ -627,8 +671,6 @@ int cfnmpc_eval_poly(cfnmpc_solver* s, double t, int n_stages, int flags, double
     return CFNMPC_OK;
 }
 
-// kernel arguments changed (weights, box): the captured steps hold the old ones
-static void invalidate_graphs(cfnmpc_solver* s) { s->gvalid[0] = s->gvalid[1] = false; }
 // the QP's data changed since the last solve: no sensitivities until the next one
 static void invalidate_sens(cfnmpc_solver* s) { s->sens_src = 0; s->sens_valid = false; s->adj_valid = false; s->unc.current = false; }
 
@@ -1069,6 +1111,7 @@ void launch_sqp_close(cfnmpc_solver* s, const cfn::SqpArgs& chk, hipStream_t st)
 int rti_step(cfnmpc_solver* s, hipStream_t st, bool reinit, const cfn::SqpArgs* chk) {
     invalidate_sens(s);   // (until the step is through)
     s->unc.inputs_moved = false;
+    RC_TRY(resolve_yuni(s));
     hipEvent_t* e = nullptr;
     if (s->profiling && s->ev_used < EV_PER_STEP * MAX_PROFILED_STEPS) {   // bounded: later steps go untimed
         while (s->ev.size() < s->ev_used + EV_PER_STEP) {
@@ -1365,6 +1408,7 @@ int cfnmpc_step_host(cfnmpc_solver* s, const double* x0, const double* yref, con
     std::memcpy(h + n_x0 + n_yr, yref_e, n_ye * sizeof(double));
     HIP_TRY(hipMemcpyAsync(d, h, n_in * sizeof(double), hipMemcpyHostToDevice, st));
     cfn::launch_put(P.B, 1, 13, 1, d, P.x0, st);
+    yref_rows_vary(s);   // (the shim's per-stage setter fills this array: no detection on the one-vehicle path)
     cfn::launch_put(P.B, P.N, 17, 1, d + n_x0, P.yref, st);
     cfn::launch_put(P.B, 1, 13, 1, d + n_x0 + n_yr, P.yref_e, st);
     int rc = cfnmpc_solve(s, 1, stream);
@@ -1956,6 +2000,7 @@ int cfnmpc_debug_chunked_pair(cfnmpc_solver* s, int chunk, int reps, double* ms,
     if (!s || chunk < 0 || reps < 1 || !ms) return CFNMPC_EINVAL;
     DeviceGuard dg(s->device);
     hipStream_t st = (hipStream_t)stream;
+    RC_TRY(resolve_yuni(s));
     cfn::Params P = s->P;
     if (chunk > 0 && !P.Ppark) {
         int rc = dev_alloc(s, &s->P.Ppark, ((size_t)P.NW + 1) * 13 * 64);
@@ -2021,6 +2066,7 @@ int cfnmpc_debug_start_factor(cfnmpc_solver* s, int mode, int reps, double* ms, 
     if (mode == 2 && (s->P.mpar || s->P.dist || s->P.wtab)) return CFNMPC_EINVAL;   // (k_linfactor: folded model constants, no disturbance, uniform weights)
     DeviceGuard dg(s->device);
     invalidate_sens(s);   // (rewrites KR / Pchk: they no longer belong to the last QP)
+    RC_TRY(resolve_yuni(s));
     hipStream_t st = (hipStream_t)stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (hipEventCreate(&e0) != hipSuccess) return CFNMPC_EHIP;
@@ -2215,6 +2261,17 @@ int cfnmpc_debug_get_list_counts(cfnmpc_solver* s, int* counts) {
     int h[64];
     HIP_TRY(hipMemcpy(h, s->P.nipm, sizeof h, hipMemcpyDeviceToHost));
     counts[0] = h[0]; counts[1] = s->P.ipm_listed ? h[cfn::NI_LISTED] : 0; counts[2] = h[cfn::NI_LONG16]; counts[3] = s->P.fwd_split ? h[cfn::NI_LATE] : 0;
+    return CFNMPC_OK;
+}
+
+// Whether the start solve's factorisation reads every instance's reference row once (1: cfnmpc_set_yref found rows 1 .. N - 1 equal
+// to row 0 bit for bit in every instance; 0: some row differs, or another writer filled the references).  Waits for a detection
+// that is still on its way, as the next step would.
+int cfnmpc_debug_get_yref_uniform(cfnmpc_solver* s, int* uniform) {
+    if (!s || !uniform) return CFNMPC_EINVAL;
+    DeviceGuard dg(s->device);
+    RC_TRY(resolve_yuni(s));
+    *uniform = s->P.yuni;
     return CFNMPC_OK;
 }
 

@@ -558,11 +558,12 @@ __global__ __launch_bounds__(64) void k_linearise_clist(Params P, int which) {
 // QTAB: diagonal weights through the LDS table of factor_stage (frees the ~34 registers of their hoisted selects);
 // DEEP: three rotating stage buffers -- the loads of stage k - 2 are issued before the arithmetic of stage k (the start
 // solve streams 1.75 KB per stage and wave from HBM; with two buffers its waves wait a quarter of their time).
+// YUNI: stage-invariant references (cfnmpc_rg.hpp: load_stage) -- row 0 is read once, in front of the stage loop.
 __device__ __forceinline__ double lds_w(const double* wl, const Lane& t, const int off) {   // entry off + L of the staged row, 0 in lanes 13..15
     const double v = wl[off + imin(t.L, 12)];
     return t.L < 13 ? v : 0.0;
 }
-template <bool ABSOLUTE, bool QTAB = false, bool DEEP = false, bool WROW = false, int WR = WR_TEST>
+template <bool ABSOLUTE, bool QTAB = false, bool DEEP = false, bool WROW = false, int WR = WR_TEST, bool YUNI = false>
 __device__ __forceinline__ bool sweep_factor(const Params& P, const Lane& t, const int head, const int chk,
                                              double* wt, double* sb, const int klo = 0, gdouble* park = nullptr,
                                              const bool from_park = false, const double* qtab = nullptr) {
@@ -598,6 +599,8 @@ __device__ __forceinline__ bool sweep_factor(const Params& P, const Lane& t, con
     // per-lane constants: state weight of this lane's row, indicator of the affine row
     const double wq = WR == WR_TABLE ? lds_w(qtab, t, 0) : lane_wq<WR>(P, t);
     const double is13 = t.L == 13 ? 1.0 : 0.0;
+    YrefLane y0{};
+    if constexpr (ABSOLUTE && YUNI) y0 = ld_yref0(P, t);
     auto after = [&](int k) {
         if (ABSOLUTE) {
             // checkpoints of the unconstrained cost-to-go (matrix part only); one store block with a run-time checkpoint
@@ -612,19 +615,19 @@ __device__ __forceinline__ bool sweep_factor(const Params& P, const Lane& t, con
     };
     if constexpr (DEEP) {
         StageIn<ABSOLUTE> b0, b1, b2;
-        load_stage<ABSOLUTE>(P, t, head - 1, wq, b0);
-        load_stage<ABSOLUTE>(P, t, imax(head - 2, 0), wq, b1);
+        load_stage<ABSOLUTE, YUNI>(P, t, head - 1, wq, b0, y0);
+        load_stage<ABSOLUTE, YUNI>(P, t, imax(head - 2, 0), wq, b1, y0);
         int k = head - 1;
         while (k >= klo) {
-            load_stage<ABSOLUTE>(P, t, imax(k - 2, 0), wq, b2);
+            load_stage<ABSOLUTE, YUNI>(P, t, imax(k - 2, 0), wq, b2, y0);
             ok = factor_stage<ABSOLUTE, false, false, QTAB, WROW>(P, t, k, Pa, b0, wq, is13, wt, sb, true, qtab) && ok;
             after(k);
             if (--k < klo) break;
-            load_stage<ABSOLUTE>(P, t, imax(k - 2, 0), wq, b0);
+            load_stage<ABSOLUTE, YUNI>(P, t, imax(k - 2, 0), wq, b0, y0);
             ok = factor_stage<ABSOLUTE, false, false, QTAB, WROW>(P, t, k, Pa, b1, wq, is13, wt, sb, true, qtab) && ok;
             after(k);
             if (--k < klo) break;
-            load_stage<ABSOLUTE>(P, t, imax(k - 2, 0), wq, b1);
+            load_stage<ABSOLUTE, YUNI>(P, t, imax(k - 2, 0), wq, b1, y0);
             ok = factor_stage<ABSOLUTE, false, false, QTAB, WROW>(P, t, k, Pa, b2, wq, is13, wt, sb, true, qtab) && ok;
             after(k);
             --k;
@@ -633,15 +636,15 @@ __device__ __forceinline__ bool sweep_factor(const Params& P, const Lane& t, con
     // two stage buffers used alternately (no hand-over copies): while stage k is computed from
     // one, stage k-1 is being loaded into the other
     StageIn<ABSOLUTE> bufA, bufB;
-    load_stage<ABSOLUTE>(P, t, head - 1, wq, bufA);
+    load_stage<ABSOLUTE, YUNI>(P, t, head - 1, wq, bufA, y0);
     int k = head - 1;
     while (k >= klo) {
-        load_stage<ABSOLUTE>(P, t, imax(k - 1, 0), wq, bufB);
+        load_stage<ABSOLUTE, YUNI>(P, t, imax(k - 1, 0), wq, bufB, y0);
         ok = factor_stage<ABSOLUTE, false, false, QTAB, WROW>(P, t, k, Pa, bufA, wq, is13, wt, sb, true, qtab) && ok;
         after(k);
         k--;
         if (k < klo) break;
-        load_stage<ABSOLUTE>(P, t, imax(k - 1, 0), wq, bufA);
+        load_stage<ABSOLUTE, YUNI>(P, t, imax(k - 1, 0), wq, bufA, y0);
         ok = factor_stage<ABSOLUTE, false, false, QTAB, WROW>(P, t, k, Pa, bufB, wq, is13, wt, sb, true, qtab) && ok;
         after(k);
         k--;
@@ -1000,29 +1003,46 @@ __device__ __forceinline__ int sweep_forward_as(const Params& P, const Lane& t, 
 //  gain by triangular substitutions, M accumulated into the new cost-to-go, scalar base addresses; 5 spilled registers --
 //  passes the parity tests and runs SLOWER: 1.60 - 1.66 against 1.56 - 1.58 ms at 65 536 instances, 0.152 against 0.126 ms at
 //  4096.  Occupancy is not what this kernel lacks; three stage buffers are worth 2.5 %.  profiles/r04_factor_variants.md)
-KALIGN __global__ __launch_bounds__(64, 2) void k_factor(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    __shared__ __attribute__((aligned(16))) double qtab[16 * QT_ROW];
-    const Lane t = lane_id<WR_ARGS>(P);   // (launched for the uniform weights only: k_factor_w)
-    qtab_fill(P, qtab);
-    __syncthreads();
-    bool ok = sweep_factor<true, true, CFN_FACTOR_DEEP != 0, false, WR_ARGS>(P, t, P.N, -1, wtile[t.row], btile[t.row], 0, nullptr, false, qtab);
-    ok = row_min(ok ? 1.0 : 0.0) > 0.0;
-    if (t.L == 0 && t.valid) gm(P.status)[t.inst] = ok ? 0 : 4;
-}
-
-// The same sweep for per-instance cost weights (Params.wtab): the LDS weight table of k_factor is shared by the four rows of a
-// wavefront, so this twin takes the diagonal of Q and R from the row's own registers (wq, Lane::wu) instead.
-KALIGN __global__ __launch_bounds__(64, 2) void k_factor_w(Params P) {
-    __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];
-    __shared__ double btile[4][64];
-    // (launched with the table set only; with WR_TABLE in place of the run-time test the compiler spills 36 B here)
-    const Lane t = lane_id(P);
-    bool ok = sweep_factor<true, false, CFN_FACTOR_DEEP != 0, true>(P, t, P.N, -1, wtile[t.row], btile[t.row]);
-    ok = row_min(ok ? 1.0 : 0.0) > 0.0;
-    if (t.L == 0 && t.valid) gm(P.status)[t.inst] = ok ? 0 : 4;
-}
+// Start-solve factorisation: weights x references.  Row: name, weights (Params.wtab set), references (Params.yuni: stage-invariant
+// per instance, the _u twins read row 0 once -- sweep_factor's YUNI); the macro that heads a row is its LDS shape.
+//   QTAB: the uniform weights through the LDS table of factor_stage.
+//   WROWS: per-instance cost weights -- that table is shared by the four rows of a wavefront, so these take the diagonal of Q and R
+//   from the row's own registers (wq, Lane::wu) instead (launched with the table set only; with WR_TABLE in place of the run-time
+//   test the compiler spills 36 B here).
+#define CFN_FACTOR_KERNELS(QTAB, WROWS)                                                                 \
+    QTAB(k_factor,     0, 0, false)                                                                     \
+    QTAB(k_factor_u,   0, 1, true)                                                                      \
+    WROWS(k_factor_w,  1, 0, false)                                                                     \
+    WROWS(k_factor_wu, 1, 1, true)
+#define CFN_FACTOR_QTAB(name, w, yuni, ...)                                                             \
+    KALIGN __global__ __launch_bounds__(64, 2) void name(Params P) {                                    \
+        __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];                               \
+        __shared__ double btile[4][64];                                                                 \
+        __shared__ __attribute__((aligned(16))) double qtab[16 * QT_ROW];                               \
+        const Lane t = lane_id<WR_ARGS>(P);                                                             \
+        qtab_fill(P, qtab);                                                                             \
+        __syncthreads();                                                                                \
+        bool ok = sweep_factor<true, true, CFN_FACTOR_DEEP != 0, false, WR_ARGS, __VA_ARGS__>(P, t, P.N, -1, wtile[t.row], btile[t.row], 0, nullptr, false, qtab); \
+        ok = row_min(ok ? 1.0 : 0.0) > 0.0;                                                             \
+        if (t.L == 0 && t.valid) gm(P.status)[t.inst] = ok ? 0 : 4;                                     \
+    }
+#define CFN_FACTOR_WROWS(name, w, yuni, ...)                                                            \
+    KALIGN __global__ __launch_bounds__(64, 2) void name(Params P) {                                    \
+        __shared__ __attribute__((aligned(16))) double wtile[4][WT_TILE];                               \
+        __shared__ double btile[4][64];                                                                 \
+        const Lane t = lane_id(P);                                                                      \
+        bool ok = sweep_factor<true, false, CFN_FACTOR_DEEP != 0, true, WR_TEST, __VA_ARGS__>(P, t, P.N, -1, wtile[t.row], btile[t.row]); \
+        ok = row_min(ok ? 1.0 : 0.0) > 0.0;                                                             \
+        if (t.L == 0 && t.valid) gm(P.status)[t.inst] = ok ? 0 : 4;                                     \
+    }
+CFN_FACTOR_KERNELS(CFN_FACTOR_QTAB, CFN_FACTOR_WROWS)
+#undef CFN_FACTOR_QTAB
+#undef CFN_FACTOR_WROWS
+struct FactorTab { Kernel k[2][2]; };
+#define CFN_CELL(name, w, yuni, ...) t.k[w][yuni] = name;
+static constexpr FactorTab factor_tab = [] { FactorTab t{}; CFN_FACTOR_KERNELS(CFN_CELL, CFN_CELL) return t; }();
+#undef CFN_CELL
+static_assert(filled(factor_tab.k), "a start-solve factorisation variant has no kernel");
 
 #ifdef CFN_DEV
 // Stage-chunked hand-over experiment (cfnmpc_debug_chunked_pair): the stages [fk_lo, fk_hi) of
@@ -3413,6 +3433,18 @@ __global__ void k_get(int B, int S, int E, int perm13, int s0, int Stot, const d
         aos[idx] = blkp[blk_index(i, s0 + s, ei, Stot, E, v4b)];
     }
 }
+// Behind the k_put of cfnmpc_set_yref: *varies = 1 if some instance's reference row k >= 1 differs from its row 0 in any bit (the
+// caller clears the word in front); one workgroup per workspace block, a stage's 68 doubles read as one run.  Padding instances
+// of the last block are not looked at: no kernel reads their rows.
+__global__ __launch_bounds__(256) void k_yref_uniform(int B, int N, const double* __restrict__ yref, int* __restrict__ varies) {
+    const unsigned long long* y = (const unsigned long long*)yref + (size_t)blockIdx.x * N * SZ_Y;
+    bool diff = false;
+    for (int idx = threadIdx.x; idx < (N - 1) * SZ_Y; idx += blockDim.x) {
+        const int e = idx % SZ_Y;
+        if ((int)blockIdx.x * 4 + e / 17 < B) diff = diff || y[SZ_Y + idx] != y[e];
+    }
+    if (diff) *varies = 1;
+}
 // Reference windows of the reference node generated on the device (acados_mpc.cpp:430-516), so
 // that a tracking fleet needs no per-step host -> device reference traffic.
 //   mode[i] 0 Regulation   : rows = [des_xyz(i), 1,0,0,0, 0 x 6, uss x 4]                 (:435-454)
@@ -4225,7 +4257,7 @@ void launch_factor_only(const Params& P, hipStream_t st) {
     // the start-solve kernels index the home 4-vectors in the wave-blocked layout unconditionally (cfnmpc_rg.hpp: load_stage,
     // factor_stage); solvers without it (partial condensing) have no path that leads here -- refuse rather than corrupt
     if (!P.v4b) { std::fprintf(stderr, "cfnmpc: k_factor needs the wave-blocked 4-vector layout (not a cond_N2 solver)\n"); return; }
-    hipLaunchKernelGGL(P.wtab ? k_factor_w : k_factor, dim3(P.NW), dim3(64), 0, st, P);
+    launch_variant(factor_tab.k[wtab_of(P)][P.yuni ? 1 : 0], "start-solve factorisation", dim3(P.NW), st, P);
 }
 void launch_cforward(const Params& P, hipStream_t st) { launch_forward(P, S_COND, st); }
 // ev (optional): event recorded after the active-set kernels (before the interior-point launch for what they left)
@@ -4346,6 +4378,9 @@ static inline int grid_for(size_t n) {
 }
 void launch_put(int B, int S, int E, int perm13, const double* aos, double* blkp, hipStream_t st, int v4b) {
     hipLaunchKernelGGL(k_put, dim3(grid_for((size_t)B * S * E)), dim3(256), 0, st, B, S, E, perm13, aos, blkp, v4b);
+}
+void launch_yref_uniform(const Params& P, int* varies, hipStream_t st) {
+    hipLaunchKernelGGL(k_yref_uniform, dim3(P.NW), dim3(256), 0, st, P.B, P.N, P.yref, varies);
 }
 void launch_get(int B, int S, int E, int perm13, int s0, int Stot, const double* blkp, double* aos, hipStream_t st, int v4b) {
     hipLaunchKernelGGL(k_get, dim3(grid_for((size_t)B * S * E)), dim3(256), 0, st, B, S, E, perm13, s0, Stot, blkp, aos, v4b);

@@ -323,23 +323,38 @@ struct StageIn {
     double Rh, g;            // lanes a < 4: input Hessian diagonal / gradient element a
     double bv, qv;           // ABSOLUTE: b_k[i] and q_k[i] = Q_i (x_k[i] - yref_k[i]) in lane i
 };
+// Row 0 of an instance's stage references as its lanes use it: yk = yref_0[i] in lane i < 13, yr = yref_0[13 + a] for the lane's
+// input slot a = L & 3 (two doubles per lane, held over the whole sweep by the uniform-reference twins).
+struct YrefLane {
+    double yk, yr;
+};
+__device__ __forceinline__ YrefLane ld_yref0(const Params& P, const Lane& t) {
+    const gdouble* yb = blk(P.yref, t, P.N, 0, SZ_Y);
+    YrefLane y;
+    y.yr = yb[t.q * 17 + 13 + (t.L & 3)];
+    y.yk = yb[t.q * 17 + imin(t.L, 12)];
+    return y;
+}
 // wq: this lane's state weight Q_i (lane i < 13), computed once per kernel
-template <bool ABSOLUTE>
+// YUNI (the _u twins of the start solve, Params.yuni: every instance's reference rows 1 .. N - 1 equal its row 0 bit for bit): the
+// stage reads no reference row, y0 (ld_yref0, in front of the stage loop) stands in for it -- the same operands in the same
+// order, so the same bits.
+template <bool ABSOLUTE, bool YUNI = false>
 __device__ __forceinline__ void load_stage(const Params& P, const Lane& t, const int k, const double wq,
-                                           StageIn<ABSOLUTE>& in) {
+                                           StageIn<ABSOLUTE>& in, const YrefLane& y0 = YrefLane{}) {
     ld_ar_raw(blkab(P, P.AR, t, k, SZ_A), t, in.ar);
     ld_rows4_raw(blkab(P, P.BR, t, k, SZ_B), t, in.br);
     const int a = t.L & 3;
     if (ABSOLUTE) {
         const double uk = blk(P.uit, t, P.N, k, SZ_V4)[t.q * 4 + a];   // (start solve: home arrays, wave-blocked)
         const gdouble* yb = blk(P.yref, t, P.N, k, SZ_Y);
-        const double yr = yb[t.q * 17 + 13 + a];
+        const double yr = YUNI ? y0.yr : yb[t.q * 17 + 13 + a];
         const double wa = t.wu;
         in.Rh = wa;                 // read in lanes a < 4 only
         in.g = wa * (uk - yr);
         in.bv = blkab(P, P.b, t, k, SZ_V13)[t.q * 13 + imin(t.L, 12)];
         const double xk = blk(P.xit, t, P.N + 1, k, SZ_V13)[t.q * 13 + imin(t.L, 12)];
-        const double yk = yb[t.q * 17 + imin(t.L, 12)];
+        const double yk = YUNI ? y0.yk : yb[t.q * 17 + imin(t.L, 12)];
         in.qv = wq * (xk - yk);     // q_k[i] in lane i < 13
     } else {
         in.Rh = gm(P.Rh)[i4(P, t, k, a)];

@@ -181,6 +181,9 @@ struct Params {
     double *cb;                  // condensed blocks, [instance][block][cb_size(w_max)] (layout: cfnmpc_pcond.hip)
     int erk_steps;               // M: classic RK4 steps of dt / M per shooting interval (cfnmpc_set_erk_steps; 1 = k_linearise / k_forward,
                                  // M > 1 = their _erk variants; k_sqp_check reads it either way)
+    int yuni;                    // host-only (selects the kernel, never read on the device): 1 = every instance's reference rows 1 .. N - 1
+                                 // equal its row 0 bit for bit (k_yref_uniform behind cfnmpc_set_yref found it so): the start solve's
+                                 // factorisation runs its _u twins, which read row 0 once per instance (launch_factor_only)
     double* mpar;                // per-instance model constants (cfnmpc_set_model_params), [NK][(NW + 1) * 4] structure-of-arrays
                                  // (cfnmpc_model.hpp: derive_k; the spare block's rows nominal); NULL = the folded constants
     double* wtab;                // per-instance cost weights (cfnmpc_set_weights_batch), [(NW + 1) * 4][32]: state weights in the internal
@@ -255,6 +258,7 @@ void launch_dist_get(int B, int S, const double* tab, double* d, hipStream_t st)
 // row are states and are permuted to the internal order.
 void launch_put(int B, int S, int E, int perm13, const double* aos, double* blk, hipStream_t st, int v4b = 0);   // v4b: E = 4 fields in the wave-blocked layout (Params.v4b)
 void launch_get(int B, int S, int E, int perm13, int s0, int Stot, const double* blk, double* aos, hipStream_t st, int v4b = 0);
+void launch_yref_uniform(const Params& P, int* varies, hipStream_t st);   // *varies = 1 if an instance's reference rows differ over the stages (device word, cleared by the caller)
 void launch_windows(const Params& P, const double* traj, int n_rows, int* mode, int* iter, const double* des,
                     double uss, hipStream_t st);
 void launch_init_iterate(const Params& P, int mode, hipStream_t st);

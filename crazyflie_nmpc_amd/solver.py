@@ -714,6 +714,13 @@ class BatchSolver(UncertaintyCalls, PolyCalls):
         _check(self._L.cfnmpc_debug_get_list_counts(self._h, c.ctypes.data_as(C.c_void_p)), "cfnmpc_debug_get_list_counts")
         return tuple(int(v) for v in c)
 
+    def yref_uniform(self):
+        """-> True while the start solve reads every vehicle's stage reference once per step (set_yref found the rows of each
+        vehicle equal over the stages); waits for a detection still on its way"""
+        u = C.c_int(0)
+        _check(self._L.cfnmpc_debug_get_yref_uniform(self._h, C.byref(u)), "cfnmpc_debug_get_yref_uniform")
+        return bool(u.value)
+
     def heads(self):
         h = np.empty(self.B, dtype=np.int32)
         _check(self._L.cfnmpc_debug_get_head(self._h, h.ctypes.data_as(C.c_void_p)), "cfnmpc_debug_get_head")

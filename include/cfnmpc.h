@@ -222,7 +222,9 @@ unsigned long long cfnmpc_workspace_bytes(const cfnmpc_solver *s);
 
 /* ocp_nlp_constraints_model_set(.., 0, "lbx"/"ubx", x0) equivalent (acados_mpc.cpp:581-582) */
 int cfnmpc_set_x0(cfnmpc_solver *s, const double *x0, int on_device, void *stream);
-/* ocp_nlp_cost_model_set(.., k, "yref", ..) for k = 0..N (acados_mpc.cpp:590-594) */
+/* ocp_nlp_cost_model_set(.., k, "yref", ..) for k = 0..N (acados_mpc.cpp:590-594).  Behind the copy the solver checks on the device
+ * whether every vehicle's rows 0 .. N-1 are one row (a setpoint): the start solve then reads it once per vehicle and step, with the
+ * same results bit for bit.  The call itself does not wait for that verdict; the first step that follows does, once. */
 int cfnmpc_set_yref(cfnmpc_solver *s, const double *yref, const double *yref_e, int on_device, void *stream);
 /* Reference windows generated ON THE DEVICE with the reference node's state machine
  * (NMPC::iteration, acados_mpc.cpp:430-516) -- replaces the host-side fill of yref_sign and the
@@ -685,6 +687,11 @@ int cfnmpc_debug_get_head(cfnmpc_solver *s, int *head);
 /* work-list counts of the last step (host, four ints): constrained rows listed | rows listed for the interior-point fall-back
  * (fleets that compact them; else 0) | listed rows with heads of more than 16 stages | late rows of a split forward sweep */
 int cfnmpc_debug_get_list_counts(cfnmpc_solver *s, int *counts /*[4]*/);
+/* *uniform = 1 while the start solve's factorisation reads every vehicle's stage reference once per step instead of once per stage:
+ * the last writer of the references was cfnmpc_set_yref and every vehicle's rows 1 .. N - 1 equalled its row 0 bit for bit (the rows
+ * may differ between vehicles); 0 otherwise.  The solver finds this out on the device behind cfnmpc_set_yref; the first step that
+ * follows (or this call) waits for the verdict once.  The results are the same bits either way. */
+int cfnmpc_debug_get_yref_uniform(cfnmpc_solver *s, int *uniform);
 
 /* ---- mixed-horizon fleets (BASELINE.json config C5: N in {30, 50, 100} side by side) ----------
  * The reference fixes N when the solver is generated (generate_c_code.py:41-42; one process per
