@@ -1885,6 +1885,81 @@ int cfnmpc_sim_dist(int batch, const double* x, const double* u, const double* p
     return sim_impl(batch, x, u, p, d, T, steps, xn, on_device, stream);
 }
 
+int cfnmpc_sim_rollout(int batch, int L, const double* x0, const double* u, const double* p, const double* d, double T, int steps,
+                       double* xs, int on_device, void* stream) {
+    if (batch <= 0 || L < 1 || !x0 || !u || !xs || steps < 1 || !(T > 0)) return CFNMPC_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (p && is_host(on_device) && !cfn::model_params_ok(p, (size_t)batch * cfn::NPAR)) return CFNMPC_EINVAL;
+    if (d && is_host(on_device) && !cfn::dist_rows_ok(d, (size_t)batch * cfn::ND)) return CFNMPC_EINVAL;
+    if (!is_host(on_device)) {
+        cfn::launch_sim_rollout(batch, L, x0, u, p, d, T, steps, xs, st);
+        HIP_TRY(hipGetLastError());
+        return CFNMPC_OK;
+    }
+    const size_t B = batch, nx = B * 13, nu = B * L * 4, ns = B * (L + 1) * 13;
+    std::unique_lock<std::mutex> lock;
+    double* dx = nullptr;
+    RC_TRY(host_scratch(nx + nu + ns + (p ? B * cfn::NPAR : 0) + (d ? B * cfn::ND : 0), &dx, lock));
+    double *du = dx + nx, *ds = du + nu, *dp = nullptr, *dd = nullptr, *next = ds + ns;
+    HIP_TRY(hipMemcpyAsync(dx, x0, nx * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(du, u, nu * 8, hipMemcpyHostToDevice, st));
+    if (p) {
+        dp = next; next += B * cfn::NPAR;
+        HIP_TRY(hipMemcpyAsync(dp, p, B * cfn::NPAR * 8, hipMemcpyHostToDevice, st));
+    }
+    if (d) {
+        dd = next;
+        HIP_TRY(hipMemcpyAsync(dd, d, B * cfn::ND * 8, hipMemcpyHostToDevice, st));
+    }
+    cfn::launch_sim_rollout(batch, L, dx, du, dp, dd, T, steps, ds, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(xs, ds, ns * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
+
+int cfnmpc_sim_rollout_vjp(int batch, int L, const double* xs, const double* u, const double* p, const double* d, double T, int steps,
+                           const double* gxs, double* gx0, double* gu, double* gp, double* gd, int on_device, void* stream) {
+    if (batch <= 0 || L < 1 || !xs || !u || !gxs || !gx0 || steps < 1 || !(T > 0)) return CFNMPC_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (p && is_host(on_device) && !cfn::model_params_ok(p, (size_t)batch * cfn::NPAR)) return CFNMPC_EINVAL;
+    if (d && is_host(on_device) && !cfn::dist_rows_ok(d, (size_t)batch * cfn::ND)) return CFNMPC_EINVAL;
+    if (!is_host(on_device)) {
+        cfn::launch_sim_rollout_vjp(batch, L, xs, u, p, d, T, steps, gxs, gx0, gu, gp, gd, st);
+        HIP_TRY(hipGetLastError());
+        return CFNMPC_OK;
+    }
+    const size_t B = batch, nx = B * 13, nu = B * L * 4, ns = B * (L + 1) * 13, np = B * cfn::NPAR, nd = B * cfn::ND;
+    std::unique_lock<std::mutex> lock;
+    double* dxs = nullptr;
+    RC_TRY(host_scratch(2 * ns + nu + (p ? np : 0) + (d ? nd : 0) + nx + (gu ? nu : 0) + (gp ? np : 0) + (gd ? nd : 0), &dxs, lock));
+    double *dg = dxs + ns, *du = dg + ns, *next = du + nu, *dp = nullptr, *dd = nullptr;
+    HIP_TRY(hipMemcpyAsync(dxs, xs, ns * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dg, gxs, ns * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(du, u, nu * 8, hipMemcpyHostToDevice, st));
+    if (p) {
+        dp = next; next += np;
+        HIP_TRY(hipMemcpyAsync(dp, p, np * 8, hipMemcpyHostToDevice, st));
+    }
+    if (d) {
+        dd = next; next += nd;
+        HIP_TRY(hipMemcpyAsync(dd, d, nd * 8, hipMemcpyHostToDevice, st));
+    }
+    double *ogx = next, *ogu = nullptr, *ogp = nullptr, *ogd = nullptr;
+    next += nx;
+    if (gu) { ogu = next; next += nu; }
+    if (gp) { ogp = next; next += np; }
+    if (gd) { ogd = next; next += nd; }
+    cfn::launch_sim_rollout_vjp(batch, L, dxs, du, dp, dd, T, steps, dg, ogx, ogu, ogp, ogd, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(gx0, ogx, nx * 8, hipMemcpyDeviceToHost, st));
+    if (gu) HIP_TRY(hipMemcpyAsync(gu, ogu, nu * 8, hipMemcpyDeviceToHost, st));
+    if (gp) HIP_TRY(hipMemcpyAsync(gp, ogp, np * 8, hipMemcpyDeviceToHost, st));
+    if (gd) HIP_TRY(hipMemcpyAsync(gd, ogd, nd * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
+
 int cfnmpc_estimate_disturbance(int batch, const double* x_prev, const double* u_prev, const double* x_meas, const double* p,
                                 double* d, double T, int steps, double gain_a, double gain_w, int on_device, void* stream) {
     if (batch <= 0 || !x_prev || !u_prev || !x_meas || !d || steps < 1 || !(T > 0)) return CFNMPC_EINVAL;

@@ -4416,3 +4416,5 @@ void launch_init_iterate(const Params& P, int mode, hipStream_t st) {
 #include "cfnmpc_adj.hpp"
 #include "cfnmpc_unc.hpp"
 #include "cfnmpc_poly.hpp"
+#define CFNMPC_SIMVJP_KERNELS
+#include "cfnmpc_simvjp.hpp"

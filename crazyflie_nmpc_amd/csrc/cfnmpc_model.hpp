@@ -48,14 +48,14 @@ struct NomK {
 };
 struct ParK {
     double c[8];   // g0, KT, KA, KB, KC, KWX, KWY, KWZ
-    __device__ double g0() const { return c[0]; }
-    __device__ double kt() const { return c[1]; }
-    __device__ double ka() const { return c[2]; }
-    __device__ double kb() const { return c[3]; }
-    __device__ double kc() const { return c[4]; }
-    __device__ double kwx() const { return c[5]; }
-    __device__ double kwy() const { return c[6]; }
-    __device__ double kwz() const { return c[7]; }
+    __host__ __device__ double g0() const { return c[0]; }
+    __host__ __device__ double kt() const { return c[1]; }
+    __host__ __device__ double ka() const { return c[2]; }
+    __host__ __device__ double kb() const { return c[3]; }
+    __host__ __device__ double kc() const { return c[4]; }
+    __host__ __device__ double kwx() const { return c[5]; }
+    __host__ __device__ double kwy() const { return c[6]; }
+    __host__ __device__ double kwz() const { return c[7]; }
 };
 // ---- external disturbance (cfnmpc_set_disturbance) ----------------------------------------------
 // A disturbance row d = [ax, ay, az | alx, aly, alz]: a_w = d[0:3] an acceleration in the WORLD frame [m/s^2], al_b = d[3:6] an
@@ -68,12 +68,12 @@ template <class K, class = void> struct has_dist : std::false_type {};
 template <class K> struct has_dist<K, std::void_t<decltype(std::declval<const K&>().dax())>> : std::true_type {};
 struct DstK : ParK {
     double d[ND];
-    __device__ double dax() const { return d[0]; }
-    __device__ double day() const { return d[1]; }
-    __device__ double daz() const { return d[2]; }
-    __device__ double dlx() const { return d[3]; }
-    __device__ double dly() const { return d[4]; }
-    __device__ double dlz() const { return d[5]; }
+    __host__ __device__ double dax() const { return d[0]; }
+    __host__ __device__ double day() const { return d[1]; }
+    __host__ __device__ double daz() const { return d[2]; }
+    __host__ __device__ double dlx() const { return d[3]; }
+    __host__ __device__ double dly() const { return d[4]; }
+    __host__ __device__ double dlz() const { return d[5]; }
 };
 // every entry finite, any sign (cfnmpc_set_disturbance, cfnmpc_sim_dist, cfnmpc_estimate_disturbance)
 inline bool dist_rows_ok(const double* d, size_t n) {
@@ -142,8 +142,10 @@ __host__ __device__ constexpr int s4(int i, int j) {
 }
 
 // ---- continuous dynamics ----------------------------------------------------------------
+// (f_expl, jac_point and jtvp also compile for the host, with the K types' accessors: the reverse RK4 sub-step of
+//  cfnmpc_simvjp.hpp is checked there under the host sanitizers, tools/sim_vjp_check.cpp)
 template <class K = NomK>
-__device__ __forceinline__ void f_expl(const double* __restrict__ x, const double* __restrict__ u,
+__host__ __device__ __forceinline__ void f_expl(const double* __restrict__ x, const double* __restrict__ u,
                                        double* __restrict__ dx, const K& mk = K()) {
     const double q1 = x[3], q2 = x[4], q3 = x[5], q4 = x[6];
     const double vbx = x[7], vby = x[8], vbz = x[9];
@@ -183,7 +185,7 @@ struct JacPoint {
     double Jpq[12];
 };
 
-__device__ __forceinline__ void jac_point(const double* __restrict__ x, JacPoint& J) {
+__host__ __device__ __forceinline__ void jac_point(const double* __restrict__ x, JacPoint& J) {
     const double q1 = x[3], q2 = x[4], q3 = x[5], q4 = x[6];
     const double vx = x[7], vy = x[8], vz = x[9];
     J.q[0] = q1; J.q[1] = q2; J.q[2] = q3; J.q[3] = q4;
@@ -257,7 +259,7 @@ __device__ __forceinline__ void jvp(const JacPoint& J, const double* __restrict_
 // out = (df/dx)(point)' v: the transposed product of jvp<true, true> at the same Jacobian point (reverse mode, k_nlp_eval).
 // v, out: 13 entries; out[0..2] = 0 (nothing depends on position).
 template <class K = NomK>
-__device__ __forceinline__ void jtvp(const JacPoint& J, const double* __restrict__ v, double* __restrict__ o, const K& mk = K()) {
+__host__ __device__ __forceinline__ void jtvp(const JacPoint& J, const double* __restrict__ v, double* __restrict__ o, const K& mk = K()) {
     const double q1 = J.q[0], q2 = J.q[1], q3 = J.q[2], q4 = J.q[3];
     const double vx = J.v[0], vy = J.v[1], vz = J.v[2];
     const double wx = J.w[0], wy = J.w[1], wz = J.w[2];

@@ -248,6 +248,12 @@ void launch_sim_par(int B, const double* x, const double* u, const double* p, do
 // ... and per-instance disturbance rows d [B][ND] (cfnmpc_sim_dist; p may be NULL = the nominal row)
 void launch_sim_dst(int B, const double* x, const double* u, const double* p, const double* d, double T, int steps, double* xn,
                     hipStream_t st);
+// open-loop rollout xs [B][L + 1][13] of the same plant step and its reverse sweep (cfnmpc_sim_rollout / cfnmpc_sim_rollout_vjp;
+// kernels: cfnmpc_simvjp.hpp).  p, d: rows or NULL, choosing the twin as above; gu, gp, gd: NULL = not written
+void launch_sim_rollout(int B, int L, const double* x0, const double* u, const double* p, const double* d, double T, int steps,
+                        double* xs, hipStream_t st);
+void launch_sim_rollout_vjp(int B, int L, const double* xs, const double* u, const double* p, const double* d, double T, int steps,
+                            const double* gxs, double* gx0, double* gu, double* gp, double* gd, hipStream_t st);
 // disturbance observer (cfnmpc_estimate_disturbance): d [B][ND] updated in place from the one-step prediction error
 void launch_dist_observe(int B, const double* x_prev, const double* u_prev, const double* x_meas, const double* p, double* d,
                          double T, int steps, double gain_a, double gain_w, hipStream_t st);

@@ -794,6 +794,82 @@ def sim(x, u, T=0.06, steps=4, out=None, params=None, dist=None):
     return out
 
 
+def _rollout_args(x, named):
+    """arrays of one rollout call on x's side: named = ((array or None, shape), ...) -> (pointers, on_device, stream, keepalives);
+    all torch device tensors (checked by _arg) or all numpy (converted, except None)"""
+    if _is_torch(x):
+        ptrs, keep, st = [], [], _stream_ptr(x)
+        for a, sh in named:
+            if a is None:
+                ptrs.append(None)
+                continue
+            p, _d, _s, k = _arg(a, sh, device=_torch_device())
+            ptrs.append(p); keep.append(k)
+        return ptrs, 1, st, keep
+    ptrs, keep = [], []
+    for a, sh in named:
+        if a is None:
+            ptrs.append(None)
+            continue
+        if _is_torch(a):
+            raise ValueError("expected numpy arrays beside a numpy array")
+        arr = np.ascontiguousarray(a, dtype=np.float64)
+        if arr.shape != tuple(sh):
+            raise ValueError(f"expected shape {tuple(sh)}, got {arr.shape}")
+        ptrs.append(arr.ctypes.data_as(C.c_void_p)); keep.append(arr)
+    return ptrs, 0, None, keep
+
+
+def _out_like(x, out, shape, what):
+    """an output array on x's side: the caller's (checked: written in place) or a new one"""
+    if out is None:
+        return _torch_like(x, shape) if _is_torch(x) else np.empty(shape)
+    if not _is_torch(x) and not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous
+                                 and out.shape == tuple(shape)):
+        raise ValueError(f"{what}: expected a contiguous float64 array {tuple(shape)} (written in place)")
+    return out
+
+
+def sim_rollout(x0, u, T=0.015, steps=1, out=None, params=None, dist=None):
+    """Open-loop rollout of the plant (cfnmpc_sim_rollout): x0 [B][13], u [B][L][4] -> xs [B][L + 1][13] with xs[:, 0] = x0 and
+    xs[:, t + 1] = sim(xs[:, t], u[:, t], T, steps, params=params, dist=dist), bit for bit.  numpy arrays or torch device
+    tensors, like sim; params [B][NP] and dist [B][ND] as there (host rows beside device tensors are uploaded)."""
+    L_ = _lib.lib()
+    B, L = x0.shape[0], u.shape[1]
+    if _is_torch(x0):
+        import torch
+        params, dist = (r if r is None or _is_torch(r) else torch.as_tensor(np.ascontiguousarray(r, dtype=np.float64), device=x0.device)
+                        for r in (params, dist))
+    out = _out_like(x0, out, (B, L + 1, NX), "out")
+    (px, pu, pp, pd, po), dev, st, _keep = _rollout_args(
+        x0, ((x0, (B, NX)), (u, (B, L, NU)), (params, (B, NP)), (dist, (B, ND)), (out, (B, L + 1, NX))))
+    _check(L_.cfnmpc_sim_rollout(B, L, px, pu, pp, pd, float(T), int(steps), po, dev, st), "cfnmpc_sim_rollout")
+    return out
+
+
+def sim_rollout_vjp(xs, u, gxs, T=0.015, steps=1, params=None, dist=None, out=None):
+    """Gradient of a loss on a rollout (cfnmpc_sim_rollout_vjp): xs [B][L + 1][13] as sim_rollout returned it, u [B][L][4],
+    gxs = dl/dxs [B][L + 1][13] -> (gx0 [B][13], gu [B][L][4], gp [B][NP], gd [B][ND]); gp / gd are None when params / dist
+    is None.  out: (gx0, gu, gp, gd) arrays to write into, None entries are allocated."""
+    L_ = _lib.lib()
+    B, L = xs.shape[0], u.shape[1]
+    if _is_torch(xs):
+        import torch
+        params, dist = (r if r is None or _is_torch(r) else torch.as_tensor(np.ascontiguousarray(r, dtype=np.float64), device=xs.device)
+                        for r in (params, dist))
+    o = tuple(out) if out is not None else (None, None, None, None)
+    gx0 = _out_like(xs, o[0], (B, NX), "gx0")
+    gu = _out_like(xs, o[1], (B, L, NU), "gu")
+    gp = None if params is None else _out_like(xs, o[2], (B, NP), "gp")
+    gd = None if dist is None else _out_like(xs, o[3], (B, ND), "gd")
+    (pxs, pu, pp, pd, pg, p0, p1, p2, p3), dev, st, _keep = _rollout_args(
+        xs, ((xs, (B, L + 1, NX)), (u, (B, L, NU)), (params, (B, NP)), (dist, (B, ND)), (gxs, (B, L + 1, NX)),
+             (gx0, (B, NX)), (gu, (B, L, NU)), (gp, (B, NP)), (gd, (B, ND))))
+    _check(L_.cfnmpc_sim_rollout_vjp(B, L, pxs, pu, pp, pd, float(T), int(steps), pg, p0, p1, p2, p3, dev, st),
+           "cfnmpc_sim_rollout_vjp")
+    return gx0, gu, gp, gd
+
+
 def estimate_disturbance(x_prev, u_prev, x_meas, d, T=0.015, steps=1, gain_a=0.5, gain_w=0.5, params=None):
     """Disturbance observer (cfnmpc_estimate_disturbance), in place on d [B][ND]: the one-step prediction error of the disturbed
     model from (x_prev, u_prev) against x_meas, fed back with gains in (0, 1].  All torch device tensors or all numpy, like sim;

@@ -643,6 +643,24 @@ int cfnmpc_sim_params(int batch, const double *x, const double *u, const double 
  * cfnmpc_sim_params, or NULL = the nominal row.  Host arrays are validated (d: finite); device arrays are taken as they are. */
 int cfnmpc_sim_dist(int batch, const double *x, const double *u, const double *p, const double *d, double T, int steps,
                     double *xn, int on_device, void *stream);
+/* Differentiable plant rollouts, solver-free like the calls above.
+ *   cfnmpc_sim_rollout: the open-loop rollout xs[:,0] = x0, xs[:,t+1] = Phi(xs[:,t], u[:,t]; p, d), Phi = `steps` classic RK4
+ *     steps over T.  Step t has the bits of cfnmpc_sim (p = d = NULL), cfnmpc_sim_params (p alone) or cfnmpc_sim_dist (d set; p or
+ *     NULL = the nominal row) for (xs[:,t], u[:,t]).  The single plant step is L = 1.
+ *   cfnmpc_sim_rollout_vjp: the gradient of a loss l on that rollout from gxs = dl/dxs (reverse mode through RK4; it reads the
+ *     stored xs).  gx0 = dl/dx0 includes gxs[:,0]; gu = dl/du; gp = dl/dp with respect to the public parameter row (p = NULL: at the
+ *     nominal row); gd = dl/dd (d = NULL: at the zero row).  gu, gp, gd may be NULL: not computed, the other outputs keep their
+ *     bits.  No atomics: two calls agree bit for bit.
+ * Any steps >= 1.  Device arrays: one launch on `stream`, no synchronisation.  Host arrays are validated (p: finite, > 0; d: finite)
+ * and staged; the call returns when the results are in place.  CFNMPC_EINVAL (nothing written): batch <= 0, L < 1, steps < 1,
+ * !(T > 0), a NULL x0 / u / xs / gxs / gx0, host rows that fail the validation. */
+int cfnmpc_sim_rollout(int batch, int L, const double *x0 /*[B][13]*/, const double *u /*[B][L][4]*/,
+                       const double *p /*[B][CFNMPC_NP] or NULL = nominal*/, const double *d /*[B][CFNMPC_ND] or NULL = none*/,
+                       double T, int steps, double *xs /*[B][L+1][13]*/, int on_device, void *stream);
+int cfnmpc_sim_rollout_vjp(int batch, int L, const double *xs /*[B][L+1][13], as returned above*/, const double *u,
+                           const double *p, const double *d, double T, int steps, const double *gxs /*[B][L+1][13]*/,
+                           double *gx0 /*[B][13]*/, double *gu /*[B][L][4] or NULL*/, double *gp /*[B][CFNMPC_NP] or NULL*/,
+                           double *gd /*[B][CFNMPC_ND] or NULL*/, int on_device, void *stream);
 /* Disturbance observer, stateless, one lane per instance: with x^ = Phi(x_prev, u_prev; p, d) (`steps` RK4 sub-steps over T, the
  * map of cfnmpc_sim_dist) and e = x_meas - x^,
  *   d[0:3] += gain_a / T * R(q_prev) e[7:10],      d[3:6] += gain_w / T * e[10:13]       (d [batch][CFNMPC_ND], in place).
