@@ -1960,7 +1960,56 @@ int cfnmpc_sim_rollout_vjp(int batch, int L, const double* xs, const double* u, 
     return CFNMPC_OK;
 }
 
-int cfnmpc_estimate_disturbance(int batch, const double* x_prev, const double* u_prev, const double* x_meas, const double* p,
+int cfnmpc_ekf_step(int batch, const double* x, const double* P, const double* u, const double* p, const double* d, double T,
+                    int steps, const double* Q, const double* z, const double* r, double gate, int flags, double* x_new,
+                    double* P_new, double* nis, int* counts, int on_device, void* stream) {
+    if (batch <= 0 || steps < 1 || !(T > 0) || !x || !P || !u || !x_new || !P_new || (z && !r)) return CFNMPC_EINVAL;
+    if (!(gate >= 0.0 && gate <= 1.7976931348623157e308) || (flags & ~CFNMPC_EKF_NORMALIZE_Q)) return CFNMPC_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    cfn::EkfArgs A{};
+    A.B = batch; A.steps = steps; A.flags = flags; A.T = T; A.gate = gate;
+    if (!is_host(on_device)) {
+        A.x = x; A.P = P; A.u = u; A.p = p; A.d = d; A.Q = Q; A.z = z; A.r = z ? r : nullptr;
+        A.xn = x_new; A.Pn = P_new; A.nis = nis; A.counts = counts;
+        cfn::launch_ekf(A, st);
+        HIP_TRY(hipGetLastError());
+        return CFNMPC_OK;
+    }
+    // host arrays: validated as a whole before anything runs (x, u, z, r, d: finite -- dist_rows_ok's rule)
+    const size_t B = batch, nx = B * 13, nP = B * 169, nu = B * 4, np = B * cfn::NPAR, nd = B * cfn::ND;
+    if (!cfn::dist_rows_ok(x, nx) || !cfn::dist_rows_ok(u, nu) || !cfn::unc_sym_ok(P, B) || (Q && !cfn::unc_sym_ok(Q, B))) return CFNMPC_EINVAL;
+    if (z && (!cfn::dist_rows_ok(z, nx) || !cfn::dist_rows_ok(r, nx))) return CFNMPC_EINVAL;
+    if ((p && !cfn::model_params_ok(p, np)) || (d && !cfn::dist_rows_ok(d, nd))) return CFNMPC_EINVAL;
+    std::unique_lock<std::mutex> lock;
+    double* base = nullptr;
+    // inputs x P u [p] [d] [Q] [z r] | outputs xn Pn nis counts (B ints in B doubles' room)
+    RC_TRY(host_scratch(nx + nP + nu + (p ? np : 0) + (d ? nd : 0) + (Q ? nP : 0) + (z ? 2 * nx : 0) + nx + nP + 2 * B, &base, lock));
+    double* next = base;
+    auto up = [&](const double* src, size_t n, const double** dst) -> int {
+        *dst = nullptr;
+        if (!src) return CFNMPC_OK;
+        *dst = next;
+        HIP_TRY(hipMemcpyAsync(next, src, n * 8, hipMemcpyHostToDevice, st));
+        next += n;
+        return CFNMPC_OK;
+    };
+    RC_TRY(up(x, nx, &A.x)); RC_TRY(up(P, nP, &A.P)); RC_TRY(up(u, nu, &A.u)); RC_TRY(up(p, np, &A.p)); RC_TRY(up(d, nd, &A.d));
+    RC_TRY(up(Q, nP, &A.Q)); RC_TRY(up(z, nx, &A.z)); RC_TRY(up(z ? r : nullptr, nx, &A.r));
+    A.xn = next; next += nx;
+    A.Pn = next; next += nP;
+    A.nis = next; next += B;
+    A.counts = (int*)next;
+    cfn::launch_ekf(A, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(x_new, A.xn, nx * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(P_new, A.Pn, nP * 8, hipMemcpyDeviceToHost, st));
+    if (nis) HIP_TRY(hipMemcpyAsync(nis, A.nis, B * 8, hipMemcpyDeviceToHost, st));
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, A.counts, B * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
+
+int cfnmpc_estimate_disturbance(int batch, const double* x_prev,const double* u_prev, const double* x_meas, const double* p,
                                 double* d, double T, int steps, double gain_a, double gain_w, int on_device, void* stream) {
     if (batch <= 0 || !x_prev || !u_prev || !x_meas || !d || steps < 1 || !(T > 0)) return CFNMPC_EINVAL;
     if (!(gain_a > 0 && gain_a <= 1) || !(gain_w > 0 && gain_w <= 1)) return CFNMPC_EINVAL;

@@ -4418,3 +4418,5 @@ void launch_init_iterate(const Params& P, int mode, hipStream_t st) {
 #include "cfnmpc_poly.hpp"
 #define CFNMPC_SIMVJP_KERNELS
 #include "cfnmpc_simvjp.hpp"
+#define CFNMPC_EKF_KERNELS
+#include "cfnmpc_ekf.hpp"

@@ -254,6 +254,17 @@ void launch_sim_rollout(int B, int L, const double* x0, const double* u, const d
                         double* xs, hipStream_t st);
 void launch_sim_rollout_vjp(int B, int L, const double* xs, const double* u, const double* p, const double* d, double T, int steps,
                             const double* gxs, double* gx0, double* gu, double* gp, double* gd, hipStream_t st);
+// extended Kalman filter step (cfnmpc_ekf_step; kernels: cfnmpc_ekf.hpp), instance-major device arrays in the public order.
+// p, d: rows or NULL, choosing the twin as above; Q: NULL = zero; z: NULL = predict only (r is read with z only); nis, counts:
+// NULL = not written.  xn may be x, Pn may be P.
+struct EkfArgs {
+    int B, steps, flags;
+    double T, gate;
+    const double *x, *P, *u, *p, *d, *Q, *z, *r;
+    double *xn, *Pn, *nis;
+    int* counts;
+};
+void launch_ekf(const EkfArgs& A, hipStream_t st);
 // disturbance observer (cfnmpc_estimate_disturbance): d [B][ND] updated in place from the one-step prediction error
 void launch_dist_observe(int B, const double* x_prev, const double* u_prev, const double* x_meas, const double* p, double* d,
                          double T, int steps, double gain_a, double gain_w, hipStream_t st);

@@ -895,6 +895,48 @@ def estimate_disturbance(x_prev, u_prev, x_meas, d, T=0.015, steps=1, gain_a=0.5
     return d
 
 
+def ekf_step(x, P, u, z=None, r=None, Q=None, T=0.015, steps=1, gate=0.0, normalize=True, params=None, dist=None, out=None):
+    """One extended Kalman filter step for every vehicle (cfnmpc_ekf_step; the rules are in include/cfnmpc.h): the estimate
+    x [B][13] and its covariance P [B][13][13] through the RK4 plant of sim(x, u, T, steps, params=params, dist=dist) with process
+    noise Q [B][13][13] (None: zero), then the sequential update with the measurement z [B][13] of variances r [B][13] (r < 0: the
+    component is not measured; z = None: predict only) behind a gate of `gate` standard deviations per component (0: none).
+    normalize: q <- q / |q| after an update.  numpy arrays or torch device tensors, like sim; out: (x, P, nis, counts) arrays to
+    write into, None entries are allocated -- out = (x, P) updates the filter in place.
+    -> (x [B][13], P [B][13][13], nis [B], counts [B][2] int32 = components used, rejected); (P, Q) are the (Sigma0, W) of
+    BatchSolver.set_uncertainty."""
+    L_ = _lib.lib()
+    B = x.shape[0]
+    if z is not None and r is None:
+        raise ValueError("ekf_step: a measurement z needs its variances r")
+    if _is_torch(x):
+        import torch
+        params, dist = (a if a is None or _is_torch(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=x.device)
+                        for a in (params, dist))
+    o = tuple(out) + (None,) * (4 - len(out)) if out is not None else (None, None, None, None)
+    xn = _out_like(x, o[0], (B, NX), "x")
+    Pn = _out_like(x, o[1], (B, NX, NX), "P")
+    nis = _out_like(x, o[2], (B,), "nis")
+    counts = o[3]
+    if _is_torch(x):
+        import torch
+        if counts is None:
+            counts = torch.empty((B, 2), dtype=torch.int32, device=x.device)
+        pc, _d, _s, _kc = _arg(counts, (B, 2), dtype=np.int32, device=_torch_device())
+    else:
+        if counts is None:
+            counts = np.empty((B, 2), dtype=np.int32)
+        if not (isinstance(counts, np.ndarray) and counts.dtype == np.int32 and counts.flags.c_contiguous and counts.shape == (B, 2)):
+            raise ValueError(f"counts: expected a contiguous int32 array {(B, 2)} (written in place)")
+        pc = counts.ctypes.data_as(C.c_void_p)
+    (px, pP, pu, pp, pd, pQ, pz, pr, pxn, pPn, pn), dev, st, _keep = _rollout_args(
+        x, ((x, (B, NX)), (P, (B, NX, NX)), (u, (B, NU)), (params, (B, NP)), (dist, (B, ND)), (Q, (B, NX, NX)), (z, (B, NX)),
+            (r if z is not None else None, (B, NX)), (xn, (B, NX)), (Pn, (B, NX, NX)), (nis, (B,))))
+    flags = 1 if normalize else 0
+    _check(L_.cfnmpc_ekf_step(B, px, pP, pu, pp, pd, float(T), int(steps), pQ, pz, pr, float(gate), flags, pxn, pPn, pn, pc, dev, st),
+           "cfnmpc_ekf_step")
+    return xn, Pn, nis, counts
+
+
 def estimate(meas, filt, u, dt=0.015, use_lpf=True, delay=0.06, steps=4):
     """Batched ESTIMATOR::predictor (acados_estimator.cpp:521-634) on torch device tensors:
     meas [B][9], filt [B][9] (updated in place), u [B][4] -> (x_est, x_pred) [B][13]."""

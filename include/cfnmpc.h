@@ -670,6 +670,41 @@ int cfnmpc_sim_rollout_vjp(int batch, int L, const double *xs /*[B][L+1][13], as
 int cfnmpc_estimate_disturbance(int batch, const double *x_prev, const double *u_prev, const double *x_meas, const double *p,
                                 double *d, double T, int steps, double gain_a, double gain_w, int on_device, void *stream);
 
+/* Extended Kalman filter step for a fleet, solver-free: the state estimate and its covariance through the RK4 plant above and a
+ * measurement of some or all of the 13 states.  Everything in the public state order.  Per instance:
+ *   1. Predict.  h = T / steps; the state goes through `steps` classic RK4 sub-steps, the map of cfnmpc_sim (p = d = NULL),
+ *      cfnmpc_sim_params (p alone) or cfnmpc_sim_dist (d set; p or NULL = the nominal row): with z = NULL, x_new has that call's
+ *      bits.  The covariance goes through the exact derivative of each sub-step, A_s = d x_{s+1} / d x_s at (x_s, u; p, d) -- the
+ *      derivative of the discrete RK4 map, not I + h df/dx --: P <- A_s P A_s', s = 0 .. steps - 1; then P^- = P + Q, once per
+ *      call (the convention of W in cfnmpc_set_uncertainty: one array serves both).
+ *   2. Quaternion sign.  If sum_{j = 3..6, r_j >= 0} z_j x^-_j < 0, z_3 .. z_6 are negated (q and -q are one attitude).
+ *   3. Update, sequential, component j = 0 .. 12 in index order, on the current (x, P).  r_j < 0: not measured, skipped.  Else
+ *      s = P_jj + r_j, nu = z_j - x_j; if gate > 0 and nu^2 > gate^2 s the component is rejected (counted, nothing changes); else
+ *      x_i += P_ij nu / s,  P_ab -= (P_aj P_jb) / s,  nis += nu^2 / s, and it is counted as used.  The product P_aj P_jb is formed
+ *      before it meets 1 / s: an exactly symmetric P stays exactly symmetric.  With the diagonal R = diag(r) this is the joint
+ *      Kalman update.
+ *   4. With CFNMPC_EKF_NORMALIZE_Q, and only in a call with z, q <- q / |q| after the update; P is left as it is.
+ *   5. z = NULL (predict only): nis = 0, counts = (0, 0), no normalisation.
+ *   6. A NaN in an instance's (device) inputs stays in that instance's outputs and touches no other instance.
+ * x_new may be x and P_new may be P: an instance's inputs are read completely before its outputs are written.  nis [B] and
+ * counts [B][2] = (used, rejected) may be NULL.  CFNMPC_EINVAL, with nothing written: batch <= 0, steps < 1, !(T > 0), gate negative
+ * or not finite, unknown flags, a NULL x / P / u / x_new / P_new, z without r.  Host arrays are validated as a whole before anything
+ * runs (x, u, z, r, d finite, r of any sign; P and Q by cfnmpc_set_uncertainty's rule for Sigma0 / W; p finite and > 0), staged,
+ * and the call returns when the results are in place.  Device arrays are taken as they are: one launch on `stream`, no
+ * synchronisation -- cfnmpc_ekf_step -> cfnmpc_set_x0 -> solve -> get_u never touches the host, and (P_new, Q) are the
+ * (Sigma0, W) of cfnmpc_set_uncertainty. */
+#define CFNMPC_EKF_NORMALIZE_Q 1   /* flags */
+int cfnmpc_ekf_step(int batch,
+    const double *x /*[B][13]*/, const double *P /*[B][13][13]*/, const double *u /*[B][4]*/,
+    const double *p /*[B][CFNMPC_NP] or NULL = nominal*/, const double *d /*[B][CFNMPC_ND] or NULL = none*/,
+    double T, int steps,
+    const double *Q /*[B][13][13] or NULL = zero*/,
+    const double *z /*[B][13] or NULL = predict only*/, const double *r /*[B][13]; required with z*/,
+    double gate, int flags,
+    double *x_new /*[B][13]*/, double *P_new /*[B][13][13]*/,
+    double *nis /*[B] or NULL*/, int *counts /*[B][2] = used, rejected; or NULL*/,
+    int on_device, void *stream);
+
 /* ESTIMATOR::predictor() for a fleet (acados_estimator.cpp:521-634), DEVICE pointers only:
  * assembles the 13-state from mocap position, onboard Euler angles [deg, as published by the
  * driver; the pitch sign flip of :495 is applied inside] and gyro rates, estimates the world
