@@ -29,7 +29,7 @@ SYMBOLS = [
     "cfnmpc_set_model_params", "cfnmpc_get_model_params", "cfnmpc_fleet_set_model_params", "cfnmpc_multi_set_model_params",
     "cfnmpc_sim_params",
     "cfnmpc_set_disturbance", "cfnmpc_get_disturbance", "cfnmpc_sim_dist", "cfnmpc_estimate_disturbance",
-    "cfnmpc_sim_rollout", "cfnmpc_sim_rollout_vjp", "cfnmpc_ekf_step",
+    "cfnmpc_sim_rollout", "cfnmpc_sim_rollout_vjp", "cfnmpc_ekf_step", "cfnmpc_ekf_aug_step",
     "cfnmpc_fleet_set_disturbance", "cfnmpc_fleet_get_disturbance", "cfnmpc_multi_set_disturbance",
     "cfnmpc_set_weights_batch", "cfnmpc_get_weights_batch", "cfnmpc_fleet_set_weights_batch", "cfnmpc_multi_set_weights_batch",
     "cfnmpc_eval_sens_x0", "cfnmpc_get_sens_x0", "cfnmpc_get_sens_active", "cfnmpc_fleet_eval_sens_x0", "cfnmpc_fleet_get_sens_x0",
@@ -194,6 +194,7 @@ def lib():
     L.cfnmpc_sim_rollout.argtypes = [i32, i32, vp, vp, vp, vp, dbl, i32, vp, i32, vp]
     L.cfnmpc_sim_rollout_vjp.argtypes = [i32, i32, vp, vp, vp, vp, dbl, i32, vp, vp, vp, vp, vp, i32, vp]
     L.cfnmpc_ekf_step.argtypes = [i32, vp, vp, vp, vp, vp, dbl, i32, vp, vp, vp, dbl, i32, vp, vp, vp, vp, i32, vp]
+    L.cfnmpc_ekf_aug_step.argtypes = [i32, vp, vp, vp, vp, vp, vp, dbl, i32, vp, vp, vp, vp, dbl, i32, vp, vp, vp, vp, vp, vp, i32, vp]
     L.cfnmpc_fleet_set_disturbance.argtypes = [vp, vp, i32, vp]
     L.cfnmpc_fleet_get_disturbance.argtypes = [vp, vp, i32, vp]
     L.cfnmpc_multi_set_disturbance.argtypes = [vp, vp]

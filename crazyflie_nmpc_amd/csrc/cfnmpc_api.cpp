@@ -2009,6 +2009,68 @@ int cfnmpc_ekf_step(int batch, const double* x, const double* P, const double* u
     return CFNMPC_OK;
 }
 
+int cfnmpc_ekf_aug_step(int batch, const double* x, const double* d, const double* Pa, const double* u, const double* p, const int* sel,
+                        double T, int steps, const double* Q, const double* Qd, const double* z, const double* r, double gate,
+                        int flags, double* x_new, double* d_new, double* Pa_new, double* Pxx_new, double* nis, int* counts,
+                        int on_device, void* stream) {
+    if (batch <= 0 || steps < 1 || !(T > 0) || !x || !d || !Pa || !u || !sel || !x_new || !d_new || !Pa_new || (z && !r)) return CFNMPC_EINVAL;
+    if (!(gate >= 0.0 && gate <= 1.7976931348623157e308) || (flags & ~CFNMPC_EKF_NORMALIZE_Q)) return CFNMPC_EINVAL;
+    if (!cfn::ekf_sel_ok(sel)) return CFNMPC_EINVAL;   // (sel is a host array in every call)
+    hipStream_t st = (hipStream_t)stream;
+    cfn::EkfAugArgs A{};
+    A.B = batch; A.steps = steps; A.flags = flags; A.T = T; A.gate = gate;
+    for (int k = 0; k < 3; k++) A.sel[k] = sel[k];
+    if (!is_host(on_device)) {
+        A.x = x; A.d = d; A.Pa = Pa; A.u = u; A.p = p; A.Q = Q; A.Qd = Qd; A.z = z; A.r = z ? r : nullptr;
+        A.xn = x_new; A.dn = d_new; A.Pan = Pa_new; A.Pxx = Pxx_new; A.nis = nis; A.counts = counts;
+        cfn::launch_ekf_aug(A, st);
+        HIP_TRY(hipGetLastError());
+        return CFNMPC_OK;
+    }
+    // host arrays: validated as a whole before anything runs, by cfnmpc_ekf_step's rules (Pa: the same rule at size 16, and zero
+    // rows and columns for the unused slots; Qd: finite, >= 0)
+    const size_t B = batch, nx = B * 13, nP = B * 169, nA = B * 256, nu = B * 4, np = B * cfn::NPAR, nd = B * cfn::ND, nq = B * 3;
+    if (!cfn::dist_rows_ok(x, nx) || !cfn::dist_rows_ok(u, nu) || !cfn::unc_sym_ok<16>(Pa, B) || !cfn::ekf_unused_zero(Pa, B, sel) ||
+        (Q && !cfn::unc_sym_ok(Q, B))) return CFNMPC_EINVAL;
+    if (Qd)
+        for (size_t e = 0; e < nq; e++)
+            if (sel[e % 3] >= 0 && !(Qd[e] >= 0.0 && Qd[e] <= 1.7976931348623157e308)) return CFNMPC_EINVAL;
+    if (z && (!cfn::dist_rows_ok(z, nx) || !cfn::dist_rows_ok(r, nx))) return CFNMPC_EINVAL;
+    if ((p && !cfn::model_params_ok(p, np)) || !cfn::dist_rows_ok(d, nd)) return CFNMPC_EINVAL;
+    std::unique_lock<std::mutex> lock;
+    double* base = nullptr;
+    // inputs x d Pa u [p] [Q] [Qd] [z r] | outputs xn dn Pan [Pxx] nis counts (B ints in B doubles' room)
+    RC_TRY(host_scratch(nx + nd + nA + nu + (p ? np : 0) + (Q ? nP : 0) + (Qd ? nq : 0) + (z ? 2 * nx : 0) + nx + nd + nA +
+                        (Pxx_new ? nP : 0) + 2 * B, &base, lock));
+    double* next = base;
+    auto up = [&](const double* src, size_t n, const double** dst) -> int {
+        *dst = nullptr;
+        if (!src) return CFNMPC_OK;
+        *dst = next;
+        HIP_TRY(hipMemcpyAsync(next, src, n * 8, hipMemcpyHostToDevice, st));
+        next += n;
+        return CFNMPC_OK;
+    };
+    RC_TRY(up(x, nx, &A.x)); RC_TRY(up(d, nd, &A.d)); RC_TRY(up(Pa, nA, &A.Pa)); RC_TRY(up(u, nu, &A.u)); RC_TRY(up(p, np, &A.p));
+    RC_TRY(up(Q, nP, &A.Q)); RC_TRY(up(Qd, nq, &A.Qd)); RC_TRY(up(z, nx, &A.z)); RC_TRY(up(z ? r : nullptr, nx, &A.r));
+    A.xn = next; next += nx;
+    A.dn = next; next += nd;
+    A.Pan = next; next += nA;
+    if (Pxx_new) { A.Pxx = next; next += nP; }
+    A.nis = next; next += B;
+    A.counts = (int*)next;
+    cfn::launch_ekf_aug(A, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(x_new, A.xn, nx * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(d_new, A.dn, nd * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(Pa_new, A.Pan, nA * 8, hipMemcpyDeviceToHost, st));
+    if (Pxx_new) HIP_TRY(hipMemcpyAsync(Pxx_new, A.Pxx, nP * 8, hipMemcpyDeviceToHost, st));
+    if (nis) HIP_TRY(hipMemcpyAsync(nis, A.nis, B * 8, hipMemcpyDeviceToHost, st));
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, A.counts, B * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
+
 int cfnmpc_estimate_disturbance(int batch, const double* x_prev,const double* u_prev, const double* x_meas, const double* p,
                                 double* d, double T, int steps, double gain_a, double gain_w, int on_device, void* stream) {
     if (batch <= 0 || !x_prev || !u_prev || !x_meas || !d || steps < 1 || !(T > 0)) return CFNMPC_EINVAL;

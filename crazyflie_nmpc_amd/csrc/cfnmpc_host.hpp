@@ -46,23 +46,42 @@ struct DeviceGuard {
 inline bool is_host(int on_device) { return on_device == CFNMPC_ON_HOST || on_device == CFNMPC_ON_HOST_ASYNC; }
 
 // host arrays of cfnmpc_set_uncertainty, n matrices [13][13]: finite, symmetric to 1e-12 of the matrix' largest entry,
-// non-negative diagonal
+// non-negative diagonal (DIM = 16: the augmented covariance of cfnmpc_ekf_aug_step, by the same rule)
+template <int DIM = 13>
 inline bool unc_sym_ok(const double* S, size_t n) {
     for (size_t i = 0; i < n; i++) {
-        const double* m = S + i * 169;
+        const double* m = S + i * DIM * DIM;
         double big = 0.0;
-        for (int e = 0; e < 169; e++) {
+        for (int e = 0; e < DIM * DIM; e++) {
             if (!(m[e] - m[e] == 0.0)) return false;   // (NaN, +-inf)
             const double a = m[e] < 0.0 ? -m[e] : m[e];
             if (a > big) big = a;
         }
-        for (int r = 0; r < 13; r++) {
-            if (m[r * 14] < 0.0) return false;
-            for (int c = r + 1; c < 13; c++) {
-                const double d = m[r * 13 + c] - m[c * 13 + r];
+        for (int r = 0; r < DIM; r++) {
+            if (m[r * (DIM + 1)] < 0.0) return false;
+            for (int c = r + 1; c < DIM; c++) {
+                const double d = m[r * DIM + c] - m[c * DIM + r];
                 if ((d < 0.0 ? -d : d) > 1e-12 * big) return false;
             }
         }
+    }
+    return true;
+}
+// cfnmpc_ekf_aug_step: sel [3] holds -1 (slot unused) or distinct entries of 0 .. 5
+inline bool ekf_sel_ok(const int* sel) {
+    for (int k = 0; k < 3; k++) {
+        if (sel[k] < -1 || sel[k] >= CFNMPC_ND) return false;
+        for (int l = 0; l < k; l++) if (sel[k] >= 0 && sel[k] == sel[l]) return false;
+    }
+    return true;
+}
+// ... and the rows and columns of its unused slots in n matrices Pa [16][16] are zero
+inline bool ekf_unused_zero(const double* Pa, size_t n, const int* sel) {
+    for (int k = 0; k < 3; k++) {
+        if (sel[k] >= 0) continue;
+        for (size_t i = 0; i < n; i++)
+            for (int e = 0; e < 16; e++)
+                if (Pa[i * 256 + (13 + k) * 16 + e] != 0.0 || Pa[i * 256 + e * 16 + 13 + k] != 0.0) return false;
     }
     return true;
 }

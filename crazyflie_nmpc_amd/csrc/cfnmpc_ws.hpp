@@ -265,6 +265,18 @@ struct EkfArgs {
     int* counts;
 };
 void launch_ekf(const EkfArgs& A, hipStream_t st);
+// the disturbance-augmented step (cfnmpc_ekf_aug_step; k_ekf_aug): Pa [B][16][16] over a = (x, d[sel[0]], d[sel[1]], d[sel[2]]),
+// sel by value (checked by the caller: -1 or 0 .. ND - 1, distinct).  p: rows or NULL = nominal; Q, Qd [B][3]: NULL = zero;
+// z: NULL = predict only; Pxx [B][13][13], nis, counts: NULL = not written.  xn, dn, Pan may be x, d, Pa.
+struct EkfAugArgs {
+    int B, steps, flags;
+    int sel[3];
+    double T, gate;
+    const double *x, *d, *Pa, *u, *p, *Q, *Qd, *z, *r;
+    double *xn, *dn, *Pan, *Pxx, *nis;
+    int* counts;
+};
+void launch_ekf_aug(const EkfAugArgs& A, hipStream_t st);
 // disturbance observer (cfnmpc_estimate_disturbance): d [B][ND] updated in place from the one-step prediction error
 void launch_dist_observe(int B, const double* x_prev, const double* u_prev, const double* x_meas, const double* p, double* d,
                          double T, int steps, double gain_a, double gain_w, hipStream_t st);

@@ -937,6 +937,77 @@ def ekf_step(x, P, u, z=None, r=None, Q=None, T=0.015, steps=1, gate=0.0, normal
     return xn, Pn, nis, counts
 
 
+EKF_NA = 16   # include/cfnmpc.h: CFNMPC_EKF_NA, 13 states + 3 disturbance slots
+
+
+def ekf_aug_cov(P, sigma_d, B=None):
+    """The augmented covariance Pa [B][16][16] of ekf_aug_step from a state covariance P [B][13][13] (or [13][13], shared) and the
+    standard deviations sigma_d [3] (or [B][3]) of the three slots: blockdiag(P, diag(sigma_d^2)).  A slot that stays unused takes
+    sigma_d = 0 (its row and column must be zero).  The batch is that of P or of sigma_d; when both are shared it is B, and
+    without B the result is one matrix, [1][16][16].  numpy."""
+    P = np.asarray(P, dtype=np.float64)
+    sd = np.asarray(sigma_d, dtype=np.float64)
+    n = P.shape[0] if P.ndim == 3 else (sd.shape[0] if sd.ndim == 2 else None)
+    if n is not None and B is not None and int(B) != n:
+        raise ValueError(f"ekf_aug_cov: B = {B} beside arrays for {n} vehicles")
+    B = n if n is not None else (1 if B is None else int(B))
+    Pa = np.zeros((B, EKF_NA, EKF_NA))
+    Pa[:, :NX, :NX] = P
+    Pa[:, np.arange(NX, EKF_NA), np.arange(NX, EKF_NA)] = np.broadcast_to(sd, (B, 3)) ** 2
+    return Pa
+
+
+def ekf_aug_step(x, d, Pa, u, sel, z=None, r=None, Q=None, Qd=None, T=0.015, steps=1, gate=0.0, normalize=True, params=None,
+                 out=None, Pxx_out=None):
+    """One step of the disturbance-augmented extended Kalman filter for every vehicle (cfnmpc_ekf_aug_step; the rules are in
+    include/cfnmpc.h): ekf_step with the components sel [3] of the disturbance row d [B][ND] (entries of 0 .. 5, distinct; -1: the
+    slot is unused) estimated jointly with the state x [B][13], under the covariance Pa [B][16][16] of (x, d[sel]) (ekf_aug_cov
+    builds one).  The plant is sim(x, u, T, steps, params=params, dist=d); Q [B][13][13] is the state's process noise and
+    Qd [B][3] the slots' random-walk variance per call (None: zero); z, r, gate, normalize as in ekf_step.  numpy arrays or torch
+    device tensors, like ekf_step; sel is a host sequence.  out: (x, d, Pa, nis, counts) arrays to write into, None entries are
+    allocated -- out = (x, d, Pa) updates the filter in place.  Pxx_out: an array [B][13][13] that receives the state block of
+    the new covariance, the Sigma0 of BatchSolver.set_uncertainty.
+    -> (x [B][13], d [B][ND], Pa [B][16][16], nis [B], counts [B][2] int32 = components used, rejected)"""
+    L_ = _lib.lib()
+    B = x.shape[0]
+    if z is not None and r is None:
+        raise ValueError("ekf_aug_step: a measurement z needs its variances r")
+    sel_a = (C.c_int * 3)(*[int(v) for v in sel]) if len(sel) == 3 else None
+    if sel_a is None:
+        raise ValueError("ekf_aug_step: sel has three entries (-1: slot unused)")
+    if _is_torch(x):
+        import torch
+        if params is not None and not _is_torch(params):
+            params = torch.as_tensor(np.ascontiguousarray(params, dtype=np.float64), device=x.device)
+    o = tuple(out) + (None,) * (5 - len(out)) if out is not None else (None,) * 5
+    xn = _out_like(x, o[0], (B, NX), "x")
+    dn = _out_like(x, o[1], (B, ND), "d")
+    Pan = _out_like(x, o[2], (B, EKF_NA, EKF_NA), "Pa")
+    nis = _out_like(x, o[3], (B,), "nis")
+    counts = o[4]
+    if Pxx_out is not None:
+        Pxx_out = _out_like(x, Pxx_out, (B, NX, NX), "Pxx_out")
+    if _is_torch(x):
+        import torch
+        if counts is None:
+            counts = torch.empty((B, 2), dtype=torch.int32, device=x.device)
+        pc, _d, _s, _kc = _arg(counts, (B, 2), dtype=np.int32, device=_torch_device())
+    else:
+        if counts is None:
+            counts = np.empty((B, 2), dtype=np.int32)
+        if not (isinstance(counts, np.ndarray) and counts.dtype == np.int32 and counts.flags.c_contiguous and counts.shape == (B, 2)):
+            raise ValueError(f"counts: expected a contiguous int32 array {(B, 2)} (written in place)")
+        pc = counts.ctypes.data_as(C.c_void_p)
+    (px, pd, pPa, pu, pp, pQ, pQd, pz, pr, pxn, pdn, pPan, pPxx, pn), dev, st, _keep = _rollout_args(
+        x, ((x, (B, NX)), (d, (B, ND)), (Pa, (B, EKF_NA, EKF_NA)), (u, (B, NU)), (params, (B, NP)), (Q, (B, NX, NX)), (Qd, (B, 3)),
+            (z, (B, NX)), (r if z is not None else None, (B, NX)), (xn, (B, NX)), (dn, (B, ND)), (Pan, (B, EKF_NA, EKF_NA)),
+            (Pxx_out, (B, NX, NX)), (nis, (B,))))
+    flags = 1 if normalize else 0
+    _check(L_.cfnmpc_ekf_aug_step(B, px, pd, pPa, pu, pp, C.cast(sel_a, C.c_void_p), float(T), int(steps), pQ, pQd, pz, pr, float(gate),
+                                  flags, pxn, pdn, pPan, pPxx, pn, pc, dev, st), "cfnmpc_ekf_aug_step")
+    return xn, dn, Pan, nis, counts
+
+
 def estimate(meas, filt, u, dt=0.015, use_lpf=True, delay=0.06, steps=4):
     """Batched ESTIMATOR::predictor (acados_estimator.cpp:521-634) on torch device tensors:
     meas [B][9], filt [B][9] (updated in place), u [B][4] -> (x_est, x_pred) [B][13]."""

@@ -666,7 +666,8 @@ int cfnmpc_sim_rollout_vjp(int batch, int L, const double *xs /*[B][L+1][13], as
  *   d[0:3] += gain_a / T * R(q_prev) e[7:10],      d[3:6] += gain_w / T * e[10:13]       (d [batch][CFNMPC_ND], in place).
  * Gains in (0, 1], else CFNMPC_EINVAL.  A constant disturbance is a fixed point (plant and model are the same map); gain 1 is
  * dead-beat up to O(T), smaller gains filter measurement noise.  Feed d to cfnmpc_set_disturbance (device arrays: no
- * synchronisation anywhere in the loop).  p [batch][CFNMPC_NP] or NULL = nominal. */
+ * synchronisation anywhere in the loop).  p [batch][CFNMPC_NP] or NULL = nominal.  The observer needs a full 13-state x_meas and has
+ * no noise model and no covariance; cfnmpc_ekf_aug_step below estimates d jointly with the state, from a partial measurement. */
 int cfnmpc_estimate_disturbance(int batch, const double *x_prev, const double *u_prev, const double *x_meas, const double *p,
                                 double *d, double T, int steps, double gain_a, double gain_w, int on_device, void *stream);
 
@@ -704,6 +705,44 @@ int cfnmpc_ekf_step(int batch,
     double *x_new /*[B][13]*/, double *P_new /*[B][13][13]*/,
     double *nis /*[B] or NULL*/, int *counts /*[B][2] = used, rejected; or NULL*/,
     int on_device, void *stream);
+
+/* Disturbance-augmented filter step, solver-free: cfnmpc_ekf_step with up to three components of the disturbance row estimated
+ * jointly with the state, from the same measurement of some or all of the 13 states.  The augmented vector
+ * is a = [x; d[sel[0]], d[sel[1]], d[sel[2]]] (CFNMPC_EKF_NA = 16 entries; the entry of an unused slot, sel[k] = -1, is 0) with the
+ * covariance Pa [16][16].  sel [3] is a HOST array in every call.  Every rule of cfnmpc_ekf_step holds without change (the
+ * quaternion sign, the sequential update in the order j = 0 .. 12 with its skip on r_j < 0 and its gate test, the product formed
+ * before 1 / s, CFNMPC_EKF_NORMALIZE_Q, predict-only semantics, NaN isolation per instance), with x read as a[0:13] and P as Pa;
+ * the model is always the disturbed one, the map of cfnmpc_sim_dist(x, u, p, d) (p or NULL = the nominal row).  What is new:
+ *   1. Predict.  Per sub-step s, F_s = [[A_s, G_s S], [0, I]] with A_s as in cfnmpc_ekf_step, G_s = d x_{s+1} / d d at
+ *      (x_s, u; p, d) -- the exact derivative of the discrete sub-step with respect to the disturbance row -- and S [6][3] the
+ *      selector of the slots' columns (a zero column for an unused slot): Pa <- F_s Pa F_s', s = 0 .. steps - 1; d is constant.
+ *      Then, once per call, Pa[0:13][0:13] += Q and Pa[13+k][13+k] += Qd[k] for the used slots (Qd: the variance of a random walk
+ *      per call; the entry of an unused slot is ignored).  With z = NULL, x_new has the bits of cfnmpc_sim_dist(x, u, p, d) and
+ *      d_new the bits of d.
+ *   2. Update.  Only the 13 state components are measured: j = 0 .. 12, s = Pa_jj + r_j, nu = z_j - a_j, and for a used component
+ *      a_i += Pa_ij nu / s for all 16 i,  Pa_ab -= (Pa_aj Pa_jb) / s for all 16 x 16 (a, b).
+ *   3. Output.  x_new = a[0:13]; d_new is d with d_new[sel[k]] = a[13+k] for the used slots, every other component copied bit
+ *      for bit; Pa_new; Pxx_new (may be NULL) = Pa_new[0:13][0:13] bit for bit, the Sigma0 of cfnmpc_set_uncertainty.  An unused
+ *      slot takes no part: its row of F_s is the unit row and its column of G_s S is zero.
+ * x_new may be x, d_new may be d and Pa_new may be Pa.  nis, counts as in cfnmpc_ekf_step.  CFNMPC_EINVAL, with nothing written:
+ * what cfnmpc_ekf_step refuses (here x / d / Pa / u / sel / x_new / d_new / Pa_new must not be NULL), and a sel[k] outside
+ * -1 .. CFNMPC_ND - 1 or repeated among the used slots.  Host arrays are validated as a whole before anything runs: as in
+ * cfnmpc_ekf_step (Pa by the rule for P at size 16), the rows and columns of Pa that belong to unused slots must be zero, Qd finite
+ * and >= 0 in the used slots' entries; then staged, and the call returns when the results are in place.  Device arrays are taken
+ * as they are: one launch on `stream`, no synchronisation -- cfnmpc_ekf_aug_step -> cfnmpc_set_x0(x_new),
+ * cfnmpc_set_disturbance(d_new) -> solve, and (Pxx_new, Q) -> cfnmpc_set_uncertainty never touch the host. */
+#define CFNMPC_EKF_NA 16      /* 13 states + 3 disturbance slots */
+int cfnmpc_ekf_aug_step(int batch,
+    const double *x /*[B][13]*/, const double *d /*[B][CFNMPC_ND]*/, const double *Pa /*[B][16][16]*/,
+    const double *u /*[B][4]*/, const double *p /*[B][CFNMPC_NP] or NULL = nominal*/,
+    const int *sel /*[3], HOST: slot k estimates d[sel[k]], sel[k] in 0..5 and distinct, or -1 = slot unused*/,
+    double T, int steps,
+    const double *Q /*[B][13][13] or NULL*/, const double *Qd /*[B][3] or NULL: random-walk variance per slot*/,
+    const double *z /*[B][13] or NULL = predict only*/, const double *r /*[B][13]; required with z*/,
+    double gate, int flags,
+    double *x_new /*[B][13]*/, double *d_new /*[B][CFNMPC_ND]*/, double *Pa_new /*[B][16][16]*/,
+    double *Pxx_new /*[B][13][13] or NULL: the state block, as cfnmpc_set_uncertainty takes it*/,
+    double *nis /*[B] or NULL*/, int *counts /*[B][2] or NULL*/, int on_device, void *stream);
 
 /* ESTIMATOR::predictor() for a fleet (acados_estimator.cpp:521-634), DEVICE pointers only:
  * assembles the 13-state from mocap position, onboard Euler angles [deg, as published by the
