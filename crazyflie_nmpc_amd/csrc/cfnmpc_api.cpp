@@ -17,6 +17,7 @@
 #include "cfnmpc_host.hpp"
 #include "cfnmpc_model.hpp"
 #include "cfnmpc_plan.hpp"
+#include "cfnmpc_stage.hpp"
 #include "cfnmpc_ws.hpp"
 #include "cfnmpc_sqp.h"
 #ifdef CFN_DEV
@@ -1807,7 +1808,7 @@ int cfnmpc_tighten_box(cfnmpc_solver* s, double gamma, double min_width, int* n_
 }
 
 namespace {
-// Device scratch of the entry points that take host arrays without a solver (cfnmpc_sim*, cfnmpc_estimate_disturbance): cached per
+// Device scratch of the entry points that take host arrays without a solver (staged_call below), `need` doubles: cached per
 // device and grown on demand (the estimator calls cfnmpc_sim at 66 Hz with batch 1, acados_estimator.cpp:589 -- no allocation
 // per call); one caller at a time PER DEVICE (predictors on different GPUs run concurrently): `lock` is held by the caller
 // until its transfers are complete
@@ -1828,43 +1829,45 @@ int host_scratch(size_t need, double** out, std::unique_lock<std::mutex>& lock) 
     *out = scratch[devi];
     return CFNMPC_OK;
 }
+using cfn::ArrPtrs;
+// One solver-less call over the arrays of `t` (cfnmpc_stage.hpp).  Device arrays: the caller's pointers
+// go to `launch` as they are, nothing is copied or waited for.  Host arrays (validated by the caller before this): staged in
+// host_scratch -- in and in-out arrays up, launch, out and in-out arrays down -- and synchronised with the scratch still locked.
+extern "C++" template <class Launch>
+int staged_call(const cfn::Stage& t, int on_device, hipStream_t st, Launch&& launch) {
+    if (!is_host(on_device)) {
+        launch(t.own());
+        HIP_TRY(hipGetLastError());
+        return CFNMPC_OK;
+    }
+    std::unique_lock<std::mutex> lock;
+    double* base = nullptr;
+    RC_TRY(host_scratch(t.bytes / 8, &base, lock));
+    const ArrPtrs a = t.at(base);
+    for (int i = 0; i < t.n; i++)
+        if (t.copy_in(i)) HIP_TRY(hipMemcpyAsync(a.p[i], t.a[i].p, t.size(i), hipMemcpyHostToDevice, st));
+    launch(a);
+    HIP_TRY(hipGetLastError());
+    for (int i = 0; i < t.n; i++)
+        if (t.copy_out(i)) HIP_TRY(hipMemcpyAsync(t.a[i].p, a.p[i], t.size(i), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CFNMPC_OK;
+}
+// optional host rows p [B][NPAR] and d [B][ND] hold valid values (device rows are not looked at)
+bool host_rows_ok(const double* p, const double* d, size_t B, int on_device) {
+    return !is_host(on_device) || ((!p || cfn::model_params_ok(p, B * cfn::NPAR)) && (!d || cfn::dist_rows_ok(d, B * cfn::ND)));
+}
 // cfnmpc_sim (p = NULL: the folded constants), cfnmpc_sim_params (p [batch][NPAR]) and cfnmpc_sim_dist (d [batch][ND], p or NULL)
 int sim_impl(int batch, const double* x, const double* u, const double* p, const double* d, double T, int steps, double* xn,
              int on_device, void* stream) {
     if (batch <= 0 || !x || !u || !xn || steps < 1 || !(T > 0)) return CFNMPC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (p && is_host(on_device) && !cfn::model_params_ok(p, (size_t)batch * cfn::NPAR)) return CFNMPC_EINVAL;
-    if (d && is_host(on_device) && !cfn::dist_rows_ok(d, (size_t)batch * cfn::ND)) return CFNMPC_EINVAL;
-    auto launch = [&](const double* x_, const double* u_, const double* p_, const double* d_, double* xn_) {
-        if (d_) cfn::launch_sim_dst(batch, x_, u_, p_, d_, T, steps, xn_, st);
-        else if (p_) cfn::launch_sim_par(batch, x_, u_, p_, T, steps, xn_, st);
-        else cfn::launch_sim(batch, x_, u_, T, steps, xn_, st);
-    };
-    if (!is_host(on_device)) {
-        launch(x, u, p, d, xn);
-        HIP_TRY(hipGetLastError());
-        return CFNMPC_OK;
-    }
     const size_t B = batch;
-    std::unique_lock<std::mutex> lock;
-    double* dx = nullptr;
-    RC_TRY(host_scratch(B * (30 + (p ? cfn::NPAR : 0) + (d ? cfn::ND : 0)), &dx, lock));
-    double *du = dx + B * 13, *dn = du + B * 4, *dp = nullptr, *dd = nullptr, *next = dn + B * 13;
-    HIP_TRY(hipMemcpyAsync(dx, x, B * 13 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(du, u, B * 4 * 8, hipMemcpyHostToDevice, st));
-    if (p) {
-        dp = next; next += B * cfn::NPAR;
-        HIP_TRY(hipMemcpyAsync(dp, p, B * cfn::NPAR * 8, hipMemcpyHostToDevice, st));
-    }
-    if (d) {
-        dd = next;
-        HIP_TRY(hipMemcpyAsync(dd, d, B * cfn::ND * 8, hipMemcpyHostToDevice, st));
-    }
-    launch(dx, du, dp, dd, dn);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(xn, dn, B * 13 * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return CFNMPC_OK;
+    if (!host_rows_ok(p, d, B, on_device)) return CFNMPC_EINVAL;
+    using K = cfn::SimArrs;
+    return staged_call(K::of(B, x, u, xn, p, d), on_device, st, [&](const ArrPtrs& a) {
+        cfn::launch_sim(batch, a.d(K::X), a.d(K::U), a.d(K::P), a.d(K::D), T, steps, a.d(K::XN), st);
+    });
 }
 }  // namespace
 
@@ -1889,75 +1892,23 @@ int cfnmpc_sim_rollout(int batch, int L, const double* x0, const double* u, cons
                        double* xs, int on_device, void* stream) {
     if (batch <= 0 || L < 1 || !x0 || !u || !xs || steps < 1 || !(T > 0)) return CFNMPC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (p && is_host(on_device) && !cfn::model_params_ok(p, (size_t)batch * cfn::NPAR)) return CFNMPC_EINVAL;
-    if (d && is_host(on_device) && !cfn::dist_rows_ok(d, (size_t)batch * cfn::ND)) return CFNMPC_EINVAL;
-    if (!is_host(on_device)) {
-        cfn::launch_sim_rollout(batch, L, x0, u, p, d, T, steps, xs, st);
-        HIP_TRY(hipGetLastError());
-        return CFNMPC_OK;
-    }
-    const size_t B = batch, nx = B * 13, nu = B * L * 4, ns = B * (L + 1) * 13;
-    std::unique_lock<std::mutex> lock;
-    double* dx = nullptr;
-    RC_TRY(host_scratch(nx + nu + ns + (p ? B * cfn::NPAR : 0) + (d ? B * cfn::ND : 0), &dx, lock));
-    double *du = dx + nx, *ds = du + nu, *dp = nullptr, *dd = nullptr, *next = ds + ns;
-    HIP_TRY(hipMemcpyAsync(dx, x0, nx * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(du, u, nu * 8, hipMemcpyHostToDevice, st));
-    if (p) {
-        dp = next; next += B * cfn::NPAR;
-        HIP_TRY(hipMemcpyAsync(dp, p, B * cfn::NPAR * 8, hipMemcpyHostToDevice, st));
-    }
-    if (d) {
-        dd = next;
-        HIP_TRY(hipMemcpyAsync(dd, d, B * cfn::ND * 8, hipMemcpyHostToDevice, st));
-    }
-    cfn::launch_sim_rollout(batch, L, dx, du, dp, dd, T, steps, ds, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(xs, ds, ns * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return CFNMPC_OK;
+    if (!host_rows_ok(p, d, batch, on_device)) return CFNMPC_EINVAL;
+    using K = cfn::RolloutArrs;
+    return staged_call(K::of(batch, L, x0, u, xs, p, d), on_device, st, [&](const ArrPtrs& a) {
+        cfn::launch_sim_rollout(batch, L, a.d(K::X0), a.d(K::U), a.d(K::P), a.d(K::D), T, steps, a.d(K::XS), st);
+    });
 }
 
 int cfnmpc_sim_rollout_vjp(int batch, int L, const double* xs, const double* u, const double* p, const double* d, double T, int steps,
                            const double* gxs, double* gx0, double* gu, double* gp, double* gd, int on_device, void* stream) {
     if (batch <= 0 || L < 1 || !xs || !u || !gxs || !gx0 || steps < 1 || !(T > 0)) return CFNMPC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (p && is_host(on_device) && !cfn::model_params_ok(p, (size_t)batch * cfn::NPAR)) return CFNMPC_EINVAL;
-    if (d && is_host(on_device) && !cfn::dist_rows_ok(d, (size_t)batch * cfn::ND)) return CFNMPC_EINVAL;
-    if (!is_host(on_device)) {
-        cfn::launch_sim_rollout_vjp(batch, L, xs, u, p, d, T, steps, gxs, gx0, gu, gp, gd, st);
-        HIP_TRY(hipGetLastError());
-        return CFNMPC_OK;
-    }
-    const size_t B = batch, nx = B * 13, nu = B * L * 4, ns = B * (L + 1) * 13, np = B * cfn::NPAR, nd = B * cfn::ND;
-    std::unique_lock<std::mutex> lock;
-    double* dxs = nullptr;
-    RC_TRY(host_scratch(2 * ns + nu + (p ? np : 0) + (d ? nd : 0) + nx + (gu ? nu : 0) + (gp ? np : 0) + (gd ? nd : 0), &dxs, lock));
-    double *dg = dxs + ns, *du = dg + ns, *next = du + nu, *dp = nullptr, *dd = nullptr;
-    HIP_TRY(hipMemcpyAsync(dxs, xs, ns * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dg, gxs, ns * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(du, u, nu * 8, hipMemcpyHostToDevice, st));
-    if (p) {
-        dp = next; next += np;
-        HIP_TRY(hipMemcpyAsync(dp, p, np * 8, hipMemcpyHostToDevice, st));
-    }
-    if (d) {
-        dd = next; next += nd;
-        HIP_TRY(hipMemcpyAsync(dd, d, nd * 8, hipMemcpyHostToDevice, st));
-    }
-    double *ogx = next, *ogu = nullptr, *ogp = nullptr, *ogd = nullptr;
-    next += nx;
-    if (gu) { ogu = next; next += nu; }
-    if (gp) { ogp = next; next += np; }
-    if (gd) { ogd = next; next += nd; }
-    cfn::launch_sim_rollout_vjp(batch, L, dxs, du, dp, dd, T, steps, dg, ogx, ogu, ogp, ogd, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(gx0, ogx, nx * 8, hipMemcpyDeviceToHost, st));
-    if (gu) HIP_TRY(hipMemcpyAsync(gu, ogu, nu * 8, hipMemcpyDeviceToHost, st));
-    if (gp) HIP_TRY(hipMemcpyAsync(gp, ogp, np * 8, hipMemcpyDeviceToHost, st));
-    if (gd) HIP_TRY(hipMemcpyAsync(gd, ogd, nd * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return CFNMPC_OK;
+    if (!host_rows_ok(p, d, batch, on_device)) return CFNMPC_EINVAL;
+    using K = cfn::RolloutVjpArrs;
+    return staged_call(K::of(batch, L, xs, gxs, u, p, d, gx0, gu, gp, gd), on_device, st, [&](const ArrPtrs& a) {
+        cfn::launch_sim_rollout_vjp(batch, L, a.d(K::XS), a.d(K::U), a.d(K::P), a.d(K::D), T, steps, a.d(K::GXS), a.d(K::GX0),
+                                    a.d(K::GU), a.d(K::GP), a.d(K::GD), st);
+    });
 }
 
 int cfnmpc_ekf_step(int batch, const double* x, const double* P, const double* u, const double* p, const double* d, double T,
@@ -1968,45 +1919,19 @@ int cfnmpc_ekf_step(int batch, const double* x, const double* P, const double* u
     hipStream_t st = (hipStream_t)stream;
     cfn::EkfArgs A{};
     A.B = batch; A.steps = steps; A.flags = flags; A.T = T; A.gate = gate;
-    if (!is_host(on_device)) {
-        A.x = x; A.P = P; A.u = u; A.p = p; A.d = d; A.Q = Q; A.z = z; A.r = z ? r : nullptr;
-        A.xn = x_new; A.Pn = P_new; A.nis = nis; A.counts = counts;
-        cfn::launch_ekf(A, st);
-        HIP_TRY(hipGetLastError());
-        return CFNMPC_OK;
+    const size_t B = batch, nx = B * 13, nu = B * 4;
+    if (is_host(on_device)) {
+        // host arrays: validated as a whole before anything runs (x, u, z, r, d: finite -- dist_rows_ok's rule)
+        if (!cfn::dist_rows_ok(x, nx) || !cfn::dist_rows_ok(u, nu) || !cfn::unc_sym_ok(P, B) || (Q && !cfn::unc_sym_ok(Q, B))) return CFNMPC_EINVAL;
+        if (z && (!cfn::dist_rows_ok(z, nx) || !cfn::dist_rows_ok(r, nx))) return CFNMPC_EINVAL;
+        if (!host_rows_ok(p, d, B, on_device)) return CFNMPC_EINVAL;
     }
-    // host arrays: validated as a whole before anything runs (x, u, z, r, d: finite -- dist_rows_ok's rule)
-    const size_t B = batch, nx = B * 13, nP = B * 169, nu = B * 4, np = B * cfn::NPAR, nd = B * cfn::ND;
-    if (!cfn::dist_rows_ok(x, nx) || !cfn::dist_rows_ok(u, nu) || !cfn::unc_sym_ok(P, B) || (Q && !cfn::unc_sym_ok(Q, B))) return CFNMPC_EINVAL;
-    if (z && (!cfn::dist_rows_ok(z, nx) || !cfn::dist_rows_ok(r, nx))) return CFNMPC_EINVAL;
-    if ((p && !cfn::model_params_ok(p, np)) || (d && !cfn::dist_rows_ok(d, nd))) return CFNMPC_EINVAL;
-    std::unique_lock<std::mutex> lock;
-    double* base = nullptr;
-    // inputs x P u [p] [d] [Q] [z r] | outputs xn Pn nis counts (B ints in B doubles' room)
-    RC_TRY(host_scratch(nx + nP + nu + (p ? np : 0) + (d ? nd : 0) + (Q ? nP : 0) + (z ? 2 * nx : 0) + nx + nP + 2 * B, &base, lock));
-    double* next = base;
-    auto up = [&](const double* src, size_t n, const double** dst) -> int {
-        *dst = nullptr;
-        if (!src) return CFNMPC_OK;
-        *dst = next;
-        HIP_TRY(hipMemcpyAsync(next, src, n * 8, hipMemcpyHostToDevice, st));
-        next += n;
-        return CFNMPC_OK;
-    };
-    RC_TRY(up(x, nx, &A.x)); RC_TRY(up(P, nP, &A.P)); RC_TRY(up(u, nu, &A.u)); RC_TRY(up(p, np, &A.p)); RC_TRY(up(d, nd, &A.d));
-    RC_TRY(up(Q, nP, &A.Q)); RC_TRY(up(z, nx, &A.z)); RC_TRY(up(z ? r : nullptr, nx, &A.r));
-    A.xn = next; next += nx;
-    A.Pn = next; next += nP;
-    A.nis = next; next += B;
-    A.counts = (int*)next;
-    cfn::launch_ekf(A, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(x_new, A.xn, nx * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(P_new, A.Pn, nP * 8, hipMemcpyDeviceToHost, st));
-    if (nis) HIP_TRY(hipMemcpyAsync(nis, A.nis, B * 8, hipMemcpyDeviceToHost, st));
-    if (counts) HIP_TRY(hipMemcpyAsync(counts, A.counts, B * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return CFNMPC_OK;
+    using K = cfn::EkfArrs;
+    return staged_call(K::of(B, x, P, u, p, d, Q, z, r, x_new, P_new, nis, counts), on_device, st, [&](const ArrPtrs& a) {
+        A.x = a.d(K::X); A.P = a.d(K::P); A.u = a.d(K::U); A.p = a.d(K::PAR); A.d = a.d(K::D); A.Q = a.d(K::Q); A.z = a.d(K::Z);
+        A.r = a.d(K::R); A.xn = a.d(K::XN); A.Pn = a.d(K::PN); A.nis = a.d(K::NIS); A.counts = a.i(K::COUNTS);
+        cfn::launch_ekf(A, st);
+    });
 }
 
 int cfnmpc_ekf_aug_step(int batch, const double* x, const double* d, const double* Pa, const double* u, const double* p, const int* sel,
@@ -2020,55 +1945,26 @@ int cfnmpc_ekf_aug_step(int batch, const double* x, const double* d, const doubl
     cfn::EkfAugArgs A{};
     A.B = batch; A.steps = steps; A.flags = flags; A.T = T; A.gate = gate;
     for (int k = 0; k < 3; k++) A.sel[k] = sel[k];
-    if (!is_host(on_device)) {
-        A.x = x; A.d = d; A.Pa = Pa; A.u = u; A.p = p; A.Q = Q; A.Qd = Qd; A.z = z; A.r = z ? r : nullptr;
-        A.xn = x_new; A.dn = d_new; A.Pan = Pa_new; A.Pxx = Pxx_new; A.nis = nis; A.counts = counts;
-        cfn::launch_ekf_aug(A, st);
-        HIP_TRY(hipGetLastError());
-        return CFNMPC_OK;
+    const size_t B = batch, nx = B * 13, nu = B * 4, nq = B * 3;
+    if (is_host(on_device)) {
+        // host arrays: validated as a whole before anything runs, by cfnmpc_ekf_step's rules (Pa: the same rule at size 16, and
+        // zero rows and columns for the unused slots; Qd: finite, >= 0)
+        if (!cfn::dist_rows_ok(x, nx) || !cfn::dist_rows_ok(u, nu) || !cfn::unc_sym_ok<16>(Pa, B) || !cfn::ekf_unused_zero(Pa, B, sel) ||
+            (Q && !cfn::unc_sym_ok(Q, B))) return CFNMPC_EINVAL;
+        if (Qd)
+            for (size_t e = 0; e < nq; e++)
+                if (sel[e % 3] >= 0 && !(Qd[e] >= 0.0 && Qd[e] <= 1.7976931348623157e308)) return CFNMPC_EINVAL;
+        if (z && (!cfn::dist_rows_ok(z, nx) || !cfn::dist_rows_ok(r, nx))) return CFNMPC_EINVAL;
+        if (!host_rows_ok(p, d, B, on_device)) return CFNMPC_EINVAL;
     }
-    // host arrays: validated as a whole before anything runs, by cfnmpc_ekf_step's rules (Pa: the same rule at size 16, and zero
-    // rows and columns for the unused slots; Qd: finite, >= 0)
-    const size_t B = batch, nx = B * 13, nP = B * 169, nA = B * 256, nu = B * 4, np = B * cfn::NPAR, nd = B * cfn::ND, nq = B * 3;
-    if (!cfn::dist_rows_ok(x, nx) || !cfn::dist_rows_ok(u, nu) || !cfn::unc_sym_ok<16>(Pa, B) || !cfn::ekf_unused_zero(Pa, B, sel) ||
-        (Q && !cfn::unc_sym_ok(Q, B))) return CFNMPC_EINVAL;
-    if (Qd)
-        for (size_t e = 0; e < nq; e++)
-            if (sel[e % 3] >= 0 && !(Qd[e] >= 0.0 && Qd[e] <= 1.7976931348623157e308)) return CFNMPC_EINVAL;
-    if (z && (!cfn::dist_rows_ok(z, nx) || !cfn::dist_rows_ok(r, nx))) return CFNMPC_EINVAL;
-    if ((p && !cfn::model_params_ok(p, np)) || !cfn::dist_rows_ok(d, nd)) return CFNMPC_EINVAL;
-    std::unique_lock<std::mutex> lock;
-    double* base = nullptr;
-    // inputs x d Pa u [p] [Q] [Qd] [z r] | outputs xn dn Pan [Pxx] nis counts (B ints in B doubles' room)
-    RC_TRY(host_scratch(nx + nd + nA + nu + (p ? np : 0) + (Q ? nP : 0) + (Qd ? nq : 0) + (z ? 2 * nx : 0) + nx + nd + nA +
-                        (Pxx_new ? nP : 0) + 2 * B, &base, lock));
-    double* next = base;
-    auto up = [&](const double* src, size_t n, const double** dst) -> int {
-        *dst = nullptr;
-        if (!src) return CFNMPC_OK;
-        *dst = next;
-        HIP_TRY(hipMemcpyAsync(next, src, n * 8, hipMemcpyHostToDevice, st));
-        next += n;
-        return CFNMPC_OK;
-    };
-    RC_TRY(up(x, nx, &A.x)); RC_TRY(up(d, nd, &A.d)); RC_TRY(up(Pa, nA, &A.Pa)); RC_TRY(up(u, nu, &A.u)); RC_TRY(up(p, np, &A.p));
-    RC_TRY(up(Q, nP, &A.Q)); RC_TRY(up(Qd, nq, &A.Qd)); RC_TRY(up(z, nx, &A.z)); RC_TRY(up(z ? r : nullptr, nx, &A.r));
-    A.xn = next; next += nx;
-    A.dn = next; next += nd;
-    A.Pan = next; next += nA;
-    if (Pxx_new) { A.Pxx = next; next += nP; }
-    A.nis = next; next += B;
-    A.counts = (int*)next;
-    cfn::launch_ekf_aug(A, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(x_new, A.xn, nx * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(d_new, A.dn, nd * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(Pa_new, A.Pan, nA * 8, hipMemcpyDeviceToHost, st));
-    if (Pxx_new) HIP_TRY(hipMemcpyAsync(Pxx_new, A.Pxx, nP * 8, hipMemcpyDeviceToHost, st));
-    if (nis) HIP_TRY(hipMemcpyAsync(nis, A.nis, B * 8, hipMemcpyDeviceToHost, st));
-    if (counts) HIP_TRY(hipMemcpyAsync(counts, A.counts, B * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return CFNMPC_OK;
+    using K = cfn::EkfAugArrs;
+    return staged_call(K::of(B, x, d, Pa, u, p, Q, Qd, z, r, x_new, d_new, Pa_new, Pxx_new, nis, counts), on_device, st,
+                       [&](const ArrPtrs& a) {
+        A.x = a.d(K::X); A.d = a.d(K::D); A.Pa = a.d(K::PA); A.u = a.d(K::U); A.p = a.d(K::PAR); A.Q = a.d(K::Q); A.Qd = a.d(K::QD);
+        A.z = a.d(K::Z); A.r = a.d(K::R); A.xn = a.d(K::XN); A.dn = a.d(K::DN); A.Pan = a.d(K::PAN); A.Pxx = a.d(K::PXX);
+        A.nis = a.d(K::NIS); A.counts = a.i(K::COUNTS);
+        cfn::launch_ekf_aug(A, st);
+    });
 }
 
 int cfnmpc_estimate_disturbance(int batch, const double* x_prev,const double* u_prev, const double* x_meas, const double* p,
@@ -2076,28 +1972,11 @@ int cfnmpc_estimate_disturbance(int batch, const double* x_prev,const double* u_
     if (batch <= 0 || !x_prev || !u_prev || !x_meas || !d || steps < 1 || !(T > 0)) return CFNMPC_EINVAL;
     if (!(gain_a > 0 && gain_a <= 1) || !(gain_w > 0 && gain_w <= 1)) return CFNMPC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (!is_host(on_device)) {
-        cfn::launch_dist_observe(batch, x_prev, u_prev, x_meas, p, d, T, steps, gain_a, gain_w, st);
-        HIP_TRY(hipGetLastError());
-        return CFNMPC_OK;
-    }
-    const size_t B = batch;
-    if (p && !cfn::model_params_ok(p, B * cfn::NPAR)) return CFNMPC_EINVAL;
-    if (!cfn::dist_rows_ok(d, B * cfn::ND)) return CFNMPC_EINVAL;
-    std::unique_lock<std::mutex> lock;
-    double* dxp = nullptr;
-    RC_TRY(host_scratch(B * (30 + cfn::ND + (p ? cfn::NPAR : 0)), &dxp, lock));
-    double *du = dxp + B * 13, *dxm = du + B * 4, *dd = dxm + B * 13, *dp = p ? dd + B * cfn::ND : nullptr;
-    HIP_TRY(hipMemcpyAsync(dxp, x_prev, B * 13 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(du, u_prev, B * 4 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dxm, x_meas, B * 13 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dd, d, B * cfn::ND * 8, hipMemcpyHostToDevice, st));
-    if (p) HIP_TRY(hipMemcpyAsync(dp, p, B * cfn::NPAR * 8, hipMemcpyHostToDevice, st));
-    cfn::launch_dist_observe(batch, dxp, du, dxm, dp, dd, T, steps, gain_a, gain_w, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(d, dd, B * cfn::ND * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return CFNMPC_OK;
+    if (!host_rows_ok(p, d, batch, on_device)) return CFNMPC_EINVAL;
+    using K = cfn::DistObserveArrs;
+    return staged_call(K::of(batch, x_prev, u_prev, x_meas, d, p), on_device, st, [&](const ArrPtrs& a) {
+        cfn::launch_dist_observe(batch, a.d(K::XP), a.d(K::U), a.d(K::XM), a.d(K::P), a.d(K::D), T, steps, gain_a, gain_w, st);
+    });
 }
 
 int cfnmpc_estimate(int batch, const double* meas, double* filt, const double* u, double dt, int use_lpf, double delay,

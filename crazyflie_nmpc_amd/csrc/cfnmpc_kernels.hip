@@ -4347,15 +4347,12 @@ void launch_qp(const Params& P, hipStream_t st, hipEvent_t* ev) {
     launch_qp_start(P, st, ev);
     launch_qp_ipm(P, st, ev ? ev + 3 : nullptr);
 }
-void launch_sim(int B, const double* x, const double* u, double T, int steps, double* xn, hipStream_t st) {
-    hipLaunchKernelGGL(k_sim, dim3((B + 255) / 256), dim3(256), 0, st, B, x, u, T, steps, xn);
-}
-void launch_sim_par(int B, const double* x, const double* u, const double* p, double T, int steps, double* xn, hipStream_t st) {
-    hipLaunchKernelGGL(k_sim_par, dim3((B + 255) / 256), dim3(256), 0, st, B, x, u, p, T, steps, xn);
-}
-void launch_sim_dst(int B, const double* x, const double* u, const double* p, const double* d, double T, int steps, double* xn,
-                    hipStream_t st) {
-    hipLaunchKernelGGL(k_sim_dst, dim3((B + 255) / 256), dim3(256), 0, st, B, x, u, p, d, T, steps, xn);
+void launch_sim(int B, const double* x, const double* u, const double* p, const double* d, double T, int steps, double* xn,
+                hipStream_t st) {
+    const dim3 g((B + 255) / 256), b(256);
+    if (d) hipLaunchKernelGGL(k_sim_dst, g, b, 0, st, B, x, u, p, d, T, steps, xn);
+    else if (p) hipLaunchKernelGGL(k_sim_par, g, b, 0, st, B, x, u, p, T, steps, xn);
+    else hipLaunchKernelGGL(k_sim, g, b, 0, st, B, x, u, T, steps, xn);
 }
 void launch_dist_observe(int B, const double* x_prev, const double* u_prev, const double* x_meas, const double* p, double* d,
                          double T, int steps, double gain_a, double gain_w, hipStream_t st) {

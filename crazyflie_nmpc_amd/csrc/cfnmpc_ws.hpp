@@ -242,12 +242,11 @@ void launch_cipm(const Params& P, hipStream_t st);
 void launch_qp_cond(const Params& P, hipStream_t st);    // = the four above
 void launch_estimate(int B, const double* meas, double* filt, const double* u, double dt, int use_lpf, double delay,
                      int steps, double* x_est, double* x_pred, hipStream_t st);
-void launch_sim(int B, const double* x, const double* u, double T, int steps, double* xn, hipStream_t st);
-// the same with per-instance parameters p [B][NPAR] (instance-major, cfnmpc_sim_params)
-void launch_sim_par(int B, const double* x, const double* u, const double* p, double T, int steps, double* xn, hipStream_t st);
-// ... and per-instance disturbance rows d [B][ND] (cfnmpc_sim_dist; p may be NULL = the nominal row)
-void launch_sim_dst(int B, const double* x, const double* u, const double* p, const double* d, double T, int steps, double* xn,
-                    hipStream_t st);
+// plant step; p [B][NPAR] (instance-major), d [B][ND]: rows or NULL, choosing the twin: p == NULL && d == NULL: the folded
+// constants (cfnmpc_sim); d set: the disturbed twin (cfnmpc_sim_dist; p or the nominal row); else the parameter twin
+// (cfnmpc_sim_params)
+void launch_sim(int B, const double* x, const double* u, const double* p, const double* d, double T, int steps, double* xn,
+                hipStream_t st);
 // open-loop rollout xs [B][L + 1][13] of the same plant step and its reverse sweep (cfnmpc_sim_rollout / cfnmpc_sim_rollout_vjp;
 // kernels: cfnmpc_simvjp.hpp).  p, d: rows or NULL, choosing the twin as above; gu, gp, gd: NULL = not written
 void launch_sim_rollout(int B, int L, const double* x0, const double* u, const double* p, const double* d, double T, int steps,

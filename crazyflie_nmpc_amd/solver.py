@@ -727,106 +727,57 @@ class BatchSolver(UncertaintyCalls, PolyCalls):
         return h
 
 
-def _rows_like(x, rows, n):
-    """optional rows [B][n] on x's side: -> (pointer or None, keepalive); host rows beside a device x are uploaded"""
-    if rows is None:
-        return None, None
-    B = x.shape[0]
-    if _is_torch(x):
+def _call_args(x, arrays, rows=()):
+    """arrays of one solver-less call on x's side: arrays = ((array or None, shape[, dtype]), ...), then the optional
+    rows = ((rows [B][n] or None, n), ...) -> (pointers in that order, on_device, stream, keepalives); all torch device tensors
+    (checked by _arg) or all numpy (converted, except None).  Host rows beside device tensors are uploaded: the kernels read
+    device memory only."""
+    dev, B = _is_torch(x), x.shape[0]
+    if dev:
         import torch
-        if not _is_torch(rows):
-            rows = torch.as_tensor(np.ascontiguousarray(rows, dtype=np.float64), device=x.device)
-        p, _d, _s, k = _arg(rows, (B, n), device=_torch_device())
-        return p, k
-    a = np.ascontiguousarray(rows, dtype=np.float64)
-    if a.shape != (B, n):
-        raise ValueError(f"expected shape {(B, n)}, got {a.shape}")
-    return a.ctypes.data_as(C.c_void_p), a
+        rows = [(r if r is None or _is_torch(r) else torch.as_tensor(np.ascontiguousarray(r, dtype=np.float64), device=x.device), n)
+                for r, n in rows]
+    ptrs, keep = [], []
+    for a, sh, *dtype in (*arrays, *((r, (B, n)) for r, n in rows)):
+        if a is None:
+            ptrs.append(None)
+            continue
+        if not dev and _is_torch(a):
+            raise ValueError("expected numpy arrays beside a numpy array")
+        p, _d, _s, k = _arg(a, sh, *dtype)
+        ptrs.append(p); keep.append(k)
+    return ptrs, int(dev), _stream_ptr(x) if dev else None, keep
+
+
+def _out_like(x, out, shape, what, dtype=np.float64):
+    """an output array on x's side: the caller's (checked: written in place) or a new one"""
+    if out is None:
+        if not _is_torch(x):
+            return np.empty(shape, dtype=dtype)
+        import torch
+        return torch.empty(shape, dtype={np.float64: torch.float64, np.int32: torch.int32}[dtype], device=x.device)
+    if not _is_torch(x) and not (isinstance(out, np.ndarray) and out.dtype == dtype and out.flags.c_contiguous
+                                 and out.shape == tuple(shape)):
+        raise ValueError(f"{what}: expected a contiguous {np.dtype(dtype).name} array {tuple(shape)} (written in place)")
+    return out
 
 
 def sim(x, u, T=0.06, steps=4, out=None, params=None, dist=None):
     """Batched predictor / plant step (crazyflie_acados_sim_solve, acados_estimator.cpp:589).  params [B][NP]: each
     row's own model (cfnmpc_sim_params), e.g. a plant that differs from the controller's model.  dist [B][ND]: each row's
-    disturbance (cfnmpc_sim_dist; with or without params)."""
+    disturbance (cfnmpc_sim_dist; with or without params).  numpy arrays or torch device tensors (host rows of params and dist
+    beside device tensors are uploaded); out: an array [B][13] to write into."""
     L = _lib.lib()
     B = x.shape[0]
+    out = _out_like(x, out, (B, NX), "out")
+    (px, pu, po, pp, pd), dev, st, _keep = _call_args(x, ((x, (B, NX)), (u, (B, NU)), (out, (B, NX))), ((params, NP), (dist, ND)))
+    tail = (float(T), int(steps), po, dev, st)
     if dist is not None:
-        if _is_torch(x):
-            import torch
-            if out is None:
-                out = torch.empty_like(x)
-            px, _d, st, _k = _arg(x, (B, NX), device=_torch_device()); pu, _d2, _s, _k2 = _arg(u, (B, NU), device=_torch_device()); po, _d3, _s3, _k3 = _arg(out, (B, NX), device=_torch_device())
-            dev = 1
-        else:
-            xa = np.ascontiguousarray(x, dtype=np.float64); ua = np.ascontiguousarray(u, dtype=np.float64)
-            if out is None:
-                out = np.empty_like(xa)
-            px, pu, po, dev, st = xa.ctypes.data_as(C.c_void_p), ua.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), 0, None
-        pp, _kp = _rows_like(x, params, NP)
-        pd, _kd = _rows_like(x, dist, ND)
-        _check(L.cfnmpc_sim_dist(B, px, pu, pp, pd, float(T), int(steps), po, dev, st), "cfnmpc_sim_dist")
-        return out
-    if _is_torch(x):
-        import torch
-        if out is None:
-            out = torch.empty_like(x)
-        px, _d, st, _k = _arg(x, (B, NX), device=_torch_device()); pu, _d2, _s, _k2 = _arg(u, (B, NU), device=_torch_device()); po, _d3, _s3, _k3 = _arg(out, (B, NX), device=_torch_device())
-        if params is not None:
-            if not _is_torch(params):   # (host rows: uploaded beside x, the kernel reads device memory only)
-                params = torch.as_tensor(np.ascontiguousarray(params, dtype=np.float64), device=x.device)
-            pp, _d4, _s4, _k4 = _arg(params, (B, NP), device=_torch_device())
-            _check(L.cfnmpc_sim_params(B, px, pu, pp, float(T), int(steps), po, 1, st), "cfnmpc_sim_params")
-            return out
-        _check(L.cfnmpc_sim(B, px, pu, float(T), int(steps), po, 1, st), "cfnmpc_sim")
-        return out
-    xa = np.ascontiguousarray(x, dtype=np.float64); ua = np.ascontiguousarray(u, dtype=np.float64)
-    if out is None:
-        out = np.empty_like(xa)
-    if params is not None:
-        pa = np.ascontiguousarray(params, dtype=np.float64)
-        if pa.shape != (B, NP):
-            raise ValueError(f"expected shape {(B, NP)}, got {pa.shape}")
-        _check(L.cfnmpc_sim_params(B, xa.ctypes.data_as(C.c_void_p), ua.ctypes.data_as(C.c_void_p), pa.ctypes.data_as(C.c_void_p),
-                                   float(T), int(steps), out.ctypes.data_as(C.c_void_p), 0, None), "cfnmpc_sim_params")
-        return out
-    _check(L.cfnmpc_sim(B, xa.ctypes.data_as(C.c_void_p), ua.ctypes.data_as(C.c_void_p), float(T), int(steps),
-                        out.ctypes.data_as(C.c_void_p), 0, None), "cfnmpc_sim")
-    return out
-
-
-def _rollout_args(x, named):
-    """arrays of one rollout call on x's side: named = ((array or None, shape), ...) -> (pointers, on_device, stream, keepalives);
-    all torch device tensors (checked by _arg) or all numpy (converted, except None)"""
-    if _is_torch(x):
-        ptrs, keep, st = [], [], _stream_ptr(x)
-        for a, sh in named:
-            if a is None:
-                ptrs.append(None)
-                continue
-            p, _d, _s, k = _arg(a, sh, device=_torch_device())
-            ptrs.append(p); keep.append(k)
-        return ptrs, 1, st, keep
-    ptrs, keep = [], []
-    for a, sh in named:
-        if a is None:
-            ptrs.append(None)
-            continue
-        if _is_torch(a):
-            raise ValueError("expected numpy arrays beside a numpy array")
-        arr = np.ascontiguousarray(a, dtype=np.float64)
-        if arr.shape != tuple(sh):
-            raise ValueError(f"expected shape {tuple(sh)}, got {arr.shape}")
-        ptrs.append(arr.ctypes.data_as(C.c_void_p)); keep.append(arr)
-    return ptrs, 0, None, keep
-
-
-def _out_like(x, out, shape, what):
-    """an output array on x's side: the caller's (checked: written in place) or a new one"""
-    if out is None:
-        return _torch_like(x, shape) if _is_torch(x) else np.empty(shape)
-    if not _is_torch(x) and not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous
-                                 and out.shape == tuple(shape)):
-        raise ValueError(f"{what}: expected a contiguous float64 array {tuple(shape)} (written in place)")
+        _check(L.cfnmpc_sim_dist(B, px, pu, pp, pd, *tail), "cfnmpc_sim_dist")
+    elif params is not None:
+        _check(L.cfnmpc_sim_params(B, px, pu, pp, *tail), "cfnmpc_sim_params")
+    else:
+        _check(L.cfnmpc_sim(B, px, pu, *tail), "cfnmpc_sim")
     return out
 
 
@@ -836,13 +787,9 @@ def sim_rollout(x0, u, T=0.015, steps=1, out=None, params=None, dist=None):
     tensors, like sim; params [B][NP] and dist [B][ND] as there (host rows beside device tensors are uploaded)."""
     L_ = _lib.lib()
     B, L = x0.shape[0], u.shape[1]
-    if _is_torch(x0):
-        import torch
-        params, dist = (r if r is None or _is_torch(r) else torch.as_tensor(np.ascontiguousarray(r, dtype=np.float64), device=x0.device)
-                        for r in (params, dist))
     out = _out_like(x0, out, (B, L + 1, NX), "out")
-    (px, pu, pp, pd, po), dev, st, _keep = _rollout_args(
-        x0, ((x0, (B, NX)), (u, (B, L, NU)), (params, (B, NP)), (dist, (B, ND)), (out, (B, L + 1, NX))))
+    (px, pu, po, pp, pd), dev, st, _keep = _call_args(
+        x0, ((x0, (B, NX)), (u, (B, L, NU)), (out, (B, L + 1, NX))), ((params, NP), (dist, ND)))
     _check(L_.cfnmpc_sim_rollout(B, L, px, pu, pp, pd, float(T), int(steps), po, dev, st), "cfnmpc_sim_rollout")
     return out
 
@@ -853,18 +800,14 @@ def sim_rollout_vjp(xs, u, gxs, T=0.015, steps=1, params=None, dist=None, out=No
     is None.  out: (gx0, gu, gp, gd) arrays to write into, None entries are allocated."""
     L_ = _lib.lib()
     B, L = xs.shape[0], u.shape[1]
-    if _is_torch(xs):
-        import torch
-        params, dist = (r if r is None or _is_torch(r) else torch.as_tensor(np.ascontiguousarray(r, dtype=np.float64), device=xs.device)
-                        for r in (params, dist))
     o = tuple(out) if out is not None else (None, None, None, None)
     gx0 = _out_like(xs, o[0], (B, NX), "gx0")
     gu = _out_like(xs, o[1], (B, L, NU), "gu")
     gp = None if params is None else _out_like(xs, o[2], (B, NP), "gp")
     gd = None if dist is None else _out_like(xs, o[3], (B, ND), "gd")
-    (pxs, pu, pp, pd, pg, p0, p1, p2, p3), dev, st, _keep = _rollout_args(
-        xs, ((xs, (B, L + 1, NX)), (u, (B, L, NU)), (params, (B, NP)), (dist, (B, ND)), (gxs, (B, L + 1, NX)),
-             (gx0, (B, NX)), (gu, (B, L, NU)), (gp, (B, NP)), (gd, (B, ND))))
+    (pxs, pu, pg, p0, p1, p2, p3, pp, pd), dev, st, _keep = _call_args(
+        xs, ((xs, (B, L + 1, NX)), (u, (B, L, NU)), (gxs, (B, L + 1, NX)), (gx0, (B, NX)), (gu, (B, L, NU)), (gp, (B, NP)),
+             (gd, (B, ND))), ((params, NP), (dist, ND)))
     _check(L_.cfnmpc_sim_rollout_vjp(B, L, pxs, pu, pp, pd, float(T), int(steps), pg, p0, p1, p2, p3, dev, st),
            "cfnmpc_sim_rollout_vjp")
     return gx0, gu, gp, gd
@@ -876,20 +819,11 @@ def estimate_disturbance(x_prev, u_prev, x_meas, d, T=0.015, steps=1, gain_a=0.5
     feed d to BatchSolver.set_disturbance.  -> d"""
     L = _lib.lib()
     B = x_prev.shape[0]
-    if _is_torch(x_prev):
-        px, _d, st, _k = _arg(x_prev, (B, NX), device=_torch_device()); pu, _d2, _s, _k2 = _arg(u_prev, (B, NU), device=_torch_device())
-        pm, _d3, _s3, _k3 = _arg(x_meas, (B, NX), device=_torch_device()); pd, _d4, _s4, _k4 = _arg(d, (B, ND), device=_torch_device())
-        dev = 1
-    else:
-        if not (isinstance(d, np.ndarray) and d.dtype == np.float64 and d.flags.c_contiguous and d.shape == (B, ND)):
-            raise ValueError(f"d: expected a contiguous float64 array {(B, ND)} (updated in place)")
-        xa = np.ascontiguousarray(x_prev, dtype=np.float64); ua = np.ascontiguousarray(u_prev, dtype=np.float64)
-        ma = np.ascontiguousarray(x_meas, dtype=np.float64)
-        if xa.shape != (B, NX) or ua.shape != (B, NU) or ma.shape != (B, NX):
-            raise ValueError("expected x_prev, x_meas [B][13] and u_prev [B][4]")
-        px, pu, pm, pd = (a.ctypes.data_as(C.c_void_p) for a in (xa, ua, ma, d))
-        dev, st = 0, None
-    pp, _kp = _rows_like(x_prev, params, NP)
+    if d is None:
+        raise ValueError("d: expected the rows [B][ND] to update in place")
+    d = _out_like(x_prev, d, (B, ND), "d")
+    (px, pu, pm, pd, pp), dev, st, _keep = _call_args(
+        x_prev, ((x_prev, (B, NX)), (u_prev, (B, NU)), (x_meas, (B, NX)), (d, (B, ND))), ((params, NP),))
     _check(L.cfnmpc_estimate_disturbance(B, px, pu, pm, pp, pd, float(T), int(steps), float(gain_a), float(gain_w), dev, st),
            "cfnmpc_estimate_disturbance")
     return d
@@ -908,29 +842,14 @@ def ekf_step(x, P, u, z=None, r=None, Q=None, T=0.015, steps=1, gate=0.0, normal
     B = x.shape[0]
     if z is not None and r is None:
         raise ValueError("ekf_step: a measurement z needs its variances r")
-    if _is_torch(x):
-        import torch
-        params, dist = (a if a is None or _is_torch(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=x.device)
-                        for a in (params, dist))
     o = tuple(out) + (None,) * (4 - len(out)) if out is not None else (None, None, None, None)
     xn = _out_like(x, o[0], (B, NX), "x")
     Pn = _out_like(x, o[1], (B, NX, NX), "P")
     nis = _out_like(x, o[2], (B,), "nis")
-    counts = o[3]
-    if _is_torch(x):
-        import torch
-        if counts is None:
-            counts = torch.empty((B, 2), dtype=torch.int32, device=x.device)
-        pc, _d, _s, _kc = _arg(counts, (B, 2), dtype=np.int32, device=_torch_device())
-    else:
-        if counts is None:
-            counts = np.empty((B, 2), dtype=np.int32)
-        if not (isinstance(counts, np.ndarray) and counts.dtype == np.int32 and counts.flags.c_contiguous and counts.shape == (B, 2)):
-            raise ValueError(f"counts: expected a contiguous int32 array {(B, 2)} (written in place)")
-        pc = counts.ctypes.data_as(C.c_void_p)
-    (px, pP, pu, pp, pd, pQ, pz, pr, pxn, pPn, pn), dev, st, _keep = _rollout_args(
-        x, ((x, (B, NX)), (P, (B, NX, NX)), (u, (B, NU)), (params, (B, NP)), (dist, (B, ND)), (Q, (B, NX, NX)), (z, (B, NX)),
-            (r if z is not None else None, (B, NX)), (xn, (B, NX)), (Pn, (B, NX, NX)), (nis, (B,))))
+    counts = _out_like(x, o[3], (B, 2), "counts", np.int32)
+    (px, pP, pu, pQ, pz, pr, pxn, pPn, pn, pc, pp, pd), dev, st, _keep = _call_args(
+        x, ((x, (B, NX)), (P, (B, NX, NX)), (u, (B, NU)), (Q, (B, NX, NX)), (z, (B, NX)), (r if z is not None else None, (B, NX)),
+            (xn, (B, NX)), (Pn, (B, NX, NX)), (nis, (B,)), (counts, (B, 2), np.int32)), ((params, NP), (dist, ND)))
     flags = 1 if normalize else 0
     _check(L_.cfnmpc_ekf_step(B, px, pP, pu, pp, pd, float(T), int(steps), pQ, pz, pr, float(gate), flags, pxn, pPn, pn, pc, dev, st),
            "cfnmpc_ekf_step")
@@ -975,33 +894,18 @@ def ekf_aug_step(x, d, Pa, u, sel, z=None, r=None, Q=None, Qd=None, T=0.015, ste
     sel_a = (C.c_int * 3)(*[int(v) for v in sel]) if len(sel) == 3 else None
     if sel_a is None:
         raise ValueError("ekf_aug_step: sel has three entries (-1: slot unused)")
-    if _is_torch(x):
-        import torch
-        if params is not None and not _is_torch(params):
-            params = torch.as_tensor(np.ascontiguousarray(params, dtype=np.float64), device=x.device)
     o = tuple(out) + (None,) * (5 - len(out)) if out is not None else (None,) * 5
     xn = _out_like(x, o[0], (B, NX), "x")
     dn = _out_like(x, o[1], (B, ND), "d")
     Pan = _out_like(x, o[2], (B, EKF_NA, EKF_NA), "Pa")
     nis = _out_like(x, o[3], (B,), "nis")
-    counts = o[4]
+    counts = _out_like(x, o[4], (B, 2), "counts", np.int32)
     if Pxx_out is not None:
         Pxx_out = _out_like(x, Pxx_out, (B, NX, NX), "Pxx_out")
-    if _is_torch(x):
-        import torch
-        if counts is None:
-            counts = torch.empty((B, 2), dtype=torch.int32, device=x.device)
-        pc, _d, _s, _kc = _arg(counts, (B, 2), dtype=np.int32, device=_torch_device())
-    else:
-        if counts is None:
-            counts = np.empty((B, 2), dtype=np.int32)
-        if not (isinstance(counts, np.ndarray) and counts.dtype == np.int32 and counts.flags.c_contiguous and counts.shape == (B, 2)):
-            raise ValueError(f"counts: expected a contiguous int32 array {(B, 2)} (written in place)")
-        pc = counts.ctypes.data_as(C.c_void_p)
-    (px, pd, pPa, pu, pp, pQ, pQd, pz, pr, pxn, pdn, pPan, pPxx, pn), dev, st, _keep = _rollout_args(
-        x, ((x, (B, NX)), (d, (B, ND)), (Pa, (B, EKF_NA, EKF_NA)), (u, (B, NU)), (params, (B, NP)), (Q, (B, NX, NX)), (Qd, (B, 3)),
-            (z, (B, NX)), (r if z is not None else None, (B, NX)), (xn, (B, NX)), (dn, (B, ND)), (Pan, (B, EKF_NA, EKF_NA)),
-            (Pxx_out, (B, NX, NX)), (nis, (B,))))
+    (px, pd, pPa, pu, pQ, pQd, pz, pr, pxn, pdn, pPan, pPxx, pn, pc, pp), dev, st, _keep = _call_args(
+        x, ((x, (B, NX)), (d, (B, ND)), (Pa, (B, EKF_NA, EKF_NA)), (u, (B, NU)), (Q, (B, NX, NX)), (Qd, (B, 3)), (z, (B, NX)),
+            (r if z is not None else None, (B, NX)), (xn, (B, NX)), (dn, (B, ND)), (Pan, (B, EKF_NA, EKF_NA)),
+            (Pxx_out, (B, NX, NX)), (nis, (B,)), (counts, (B, 2), np.int32)), ((params, NP),))
     flags = 1 if normalize else 0
     _check(L_.cfnmpc_ekf_aug_step(B, px, pd, pPa, pu, pp, C.cast(sel_a, C.c_void_p), float(T), int(steps), pQ, pQd, pz, pr, float(gate),
                                   flags, pxn, pdn, pPan, pPxx, pn, pc, dev, st), "cfnmpc_ekf_aug_step")
